@@ -10,21 +10,29 @@ value    = QPs/s over all ranks, inputs resident in HBM when the timed region st
            setup (host analysis + first factorisation + upload) is outside and reported
            separately.  --scaling weak (default): 1024 QPs per GPU; --scaling strong: the
            1024-QP batch of the metric split over the ranks (sharding.shard_range).  For
-           N>1 the other mode is measured in the same run and reported under "strong" /
-           "weak" next to the primary numbers.
+           N>1 with --full the other mode is measured in the same run and reported under
+           "strong" / "weak" next to the primary numbers.
 roofline = iterate_kernel: the MINIMAL bytes of the algorithm the kernel implements
            (L before the dense tail twice, the inverted Schur complement once, vectors;
            unpadded) x the QP-iterations of the launches / the launch durations measured
            with HIP events on the launch stream.  The SURVEY 8(d) figure (two sweeps over
            all of L) stays as frac_survey_8d.  kernels[] holds the refactorisation kernels.
-cpu_baseline = the oracle (CPU restatement, kind "port") on a bounded sample of the
-           same workload on this box's host cores.
-secondary = BASELINE configs 2, 4, 5 and the GOMP obstacle scene (continuous driver) measured outside the headline
-           timing (rank 0, N=1).
-value_pcie_inclusive = the same step through the host-pointer boundary (H2D bounds, D2H solutions); roofline carries
-           measured_copy_GBps / measured_triad_GBps of this box next to the nominal peak.
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]       (N>1: starts the N ranks itself)
+A plain run does only what the headline needs: setup, warm-up, the timed steps, the roofline of those steps, the
+outputs (--dump-outputs) and the result line.  --full adds the measurements that take runs of their own:
+cpu_baseline = the oracle (CPU restatement, kind "port") on a bounded sample of the
+           same workload on this box's host cores (--no-cpu-baseline: off).
+secondary = BASELINE configs 2, 4, 5 and the GOMP obstacle scene (continuous driver) measured outside the headline
+           timing (rank 0, N=1; --no-secondary: off).
+value_pcie_inclusive = the same step through the host-pointer boundary (H2D bounds, D2H solutions); roofline carries
+           measured_copy_GBps / measured_triad_GBps of this box next to the nominal peak.  N>1: the other scaling mode.
+
+--dump-outputs DIR: after the timed steps, what the last step returned to its caller, as DIR/x.npy (float64, the
+           solutions; all ranks' with N>1), DIR/status.npy and DIR/iters.npy (float64, rank 0's QPs).  Inputs are
+           seeded: the same arguments give the same inputs.  Where the arrays would pass 56 MiB, a fixed seeded
+           sample of QPs is written instead, with their row indices in DIR/x_rows.npy.
+
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   (N>1: starts the N ranks itself)
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -38,6 +46,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HEADLINE_B = 1024
+DUMP_MAX_BYTES = 56 << 20               # --dump-outputs: all arrays together stay below 64 MB
 
 
 def parse():
@@ -48,9 +57,34 @@ def parse():
     ap.add_argument("--batch", type=int, default=HEADLINE_B, help="QPs of the headline batch (BASELINE config 3: 1024)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --batch QPs per GPU; strong: --batch QPs in total, split over the GPUs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip BASELINE configs 2, 4, 5")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: CPU baseline, secondary configs, PCIe-inclusive step, "
+                         "stream bandwidth, the other scaling mode (N>1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip BASELINE configs 2, 4, 5 and the scenes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (x, status, iters)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(d, x, status, iters):
+    """The last timed step's outputs as .npy (float64).  Above DUMP_MAX_BYTES: a fixed seeded sample of QPs (rows)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    x = np.asarray(x, dtype=np.float64)
+    status = np.asarray(status, dtype=np.float64); iters = np.asarray(iters, dtype=np.float64)
+    per_row = 8 * x.shape[1] + 3 * 8                # a solution, its status, its iteration count, its row index
+    if x.shape[0] * per_row > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(x.shape[0], size=DUMP_MAX_BYTES // per_row, replace=False))
+        x, own = x[rows], rows[rows < len(status)]
+        status, iters = status[own], iters[own]
+        np.save(os.path.join(d, "x_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, "x.npy"), x)
+    np.save(os.path.join(d, "status.npy"), status)
+    np.save(os.path.join(d, "iters.npy"), iters)
 
 
 def spawn_ranks(args):
@@ -178,13 +212,14 @@ def main():
             tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
+        x_out = xg.cpu().numpy() if (args.dump_outputs and rank == 0 and mode == args.scaling) else None
         avg_ms, launches = solver.kernel_time()
         peak = solver.refactor_peak()
         f_ms, d_ms, r_launches, r_qps = solver.refactor_time()
         # the same step through the HOST-pointer boundary (BASELINE.md section 2 / SURVEY 8(d): "incl. H2D bounds and D2H
         # solutions"): bounds from host memory, solutions back to host memory.  Reported beside `value`, never as it.
         pcie = None
-        if rank == 0 and mode == args.scaling:
+        if args.full and rank == 0 and mode == args.scaling:
             ksteps = max(2, min(steps, 5))
             solver.reset(); solver.update_bounds(pr["l"], pr["u"]); solver.solve(); solver.primal()      # (pinned staging allocated)
             torch.cuda.synchronize()
@@ -211,11 +246,13 @@ def main():
                     total_qps=int(tot[0]), total_iters=float(tot[1]), all_solved=bool(tot[2] == world),
                     avg_ms=avg_ms, launches=launches, f_ms=f_ms, d_ms=d_ms, r_launches=r_launches, r_qps=r_qps, peak=peak,
                     iters=iters, status=status, d_x=d_x, ls=solver.last_solve_stats(), dev_s=dev_s, ref_s=ref_s, cmp_s=cmp_s,
-                    gathered_ok=gathered_ok, pcie=pcie)
+                    gathered_ok=gathered_ok, pcie=pcie, x_out=x_out)
 
     r = run_mode(args.scaling, args.steps, args.warmup)
     other = None
-    if world > 1:                                  # the other scaling mode, measured in the same run (shorter)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r["x_out"], r["status"], r["iters"])
+    if args.full and world > 1:                    # the other scaling mode, measured in the same run (shorter)
         om = "strong" if args.scaling == "weak" else "weak"
         ro = run_mode(om, max(2, min(args.steps, 5)), 1)
         other = {"scaling": om, "value": ro["total_qps"] * ro["steps"] / ro["elapsed"], "unit": "QPs/s",
@@ -276,7 +313,8 @@ def main():
                     "tail undercuts; streamed_* = the padded streams the kernel reads; traffic = PMC bytes per launch of the "
                     "committed profile (profiles/hbm_traffic.json)",
         }
-        out["roofline"].update(measure_stream_bandwidth(torch, dev))
+        if args.full:
+            out["roofline"].update(measure_stream_bandwidth(torch, dev))
         rb = refactor_bytes(st)
         kern = []
         pk_qps, pk_f, pk_t = r["peak"]                     # the largest refactorisation of the timed steps (605 QPs at the headline batch)
@@ -303,7 +341,7 @@ def main():
                          "traffic": pmc, "traffic_over_algorithmic": (pmc / alg) if pmc else None,
                          "all_launches_ms_per_step": (r["f_ms"] if name == "factor_kernel" else r["d_ms"]) / steps})
         out["roofline"]["kernels"] = kern
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import oracle as O
             pr = r["pr"]
             cores = M.host_cores()             # min(affinity, cgroup quota): the box shows 256 CPUs, grants ~16
@@ -321,7 +359,7 @@ def main():
                                    "single_thread_qps": 8 / r1["solve_s"], "setup_seconds_sample": rc["setup_s"],
                                    "gpu_vs_cpu_max_abs_x_diff": err, "same_iteration_counts": same}
         r["solver"].close()
-        if not args.no_secondary and world == 1:
+        if args.full and not args.no_secondary and world == 1:
             try:
                 out["secondary"] = secondary(M, PR, torch, not args.no_cpu_baseline)
             except Exception as e:                          # the headline line must survive a secondary failure

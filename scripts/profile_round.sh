@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 python3 $ROOT/bench.py --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 $ROOT/bench.py --steps 5 --warmup 1 --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > $OUT/stats_bench.json 2> $OUT/stats.err
 echo "stats done"

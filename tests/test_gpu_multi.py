@@ -39,6 +39,33 @@ def test_bench_under_torchrun_nccl_world_size_1():
     assert out["config"]["total_qps_per_step"] == 64 and out["roofline"]["frac"] > 0
 
 
+def test_bench_dump_outputs_are_the_timed_solutions_and_repeat(tmp_path):
+    """--dump-outputs writes what the last timed step returned (x, status, iters); the inputs are seeded, so a second run
+    writes the same arrays, and the solutions are the oracle's on the same QPs (bench.py: QP b has value seed 1000 + b)."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                              "--batch", "64", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+        out = _last_json(res.stdout)
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and "cpu_baseline" not in out and "secondary" not in out
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("x", "status", "iters")})
+        assert not os.path.exists(d / "x_rows.npy")
+    x, status, iters = dumps[0]["x"], dumps[0]["status"], dumps[0]["iters"]
+    assert x.dtype == np.float64 and x.shape == (64, 512) and status.shape == iters.shape == (64,)
+    assert np.all(status == 1) and iters.max() == out["iters_max"] and abs(iters.mean() - out["iters_mean"]) < 1e-9
+    for n in ("x", "status", "iters"):
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+    pr = PR.random_box_qp(64, value_seed=1000)
+    for b in range(4):
+        P, A = PR.qp_matrices(pr, b)
+        o = O.OracleQPSolver(P, pr["q"][b], A, pr["l"][b], pr["u"][b])
+        st, xo = o.solve()
+        assert st == 1 and o.info().iter == iters[b]
+        assert np.max(np.abs(x[b] - xo)) <= 1e-6
+
+
 def test_bench_refuses_to_report_fewer_gpus_than_requested():
     import torch
     if torch.cuda.device_count() >= 2:
