@@ -29,7 +29,7 @@ enum { DS_C = 0, DS_CINV, DS_RHO, DS_RHO_EST, DS_PRI_RES, DS_DUA_RES, DS_OBJ, DS
 // per-QP int scalars, laid out [tile][IS_COUNT][BT]
 // (IS_CUR: iterations of the QP's current solve so far, kept by check_kernel - the continuous entry points begin the solves
 //  of a batch at different launches, and every QP counts its own iterations; IS_ITER: the count at which it finished)
-// (continuous batching: the per-QP calls prepare a QP on a second stream while the others iterate.  IS_PENDING = 1: a solve
+// (continuous batching: the per-QP calls prepare a QP between advance launches while the others iterate.  IS_PENDING = 1: a solve
 //  has been begun and joins the first advance launch that sees the mark; 2: the solve is paused for its refactorisation
 //  (IS_NEED_REFACTOR = 1 until factor_kernel has run).  A pending / paused slot reads IS_DONE = 1, so every kernel leaves it
 //  alone.  IS_EPOCH counts the solves begun in the slot: the host tells a finished solve from the previous one by it.)
@@ -53,7 +53,6 @@ struct KernelArgs {
   const double *q, *l, *u, *rho_vec, *rho_inv, *Dsc, *Dsc_inv, *Esc, *Esc_inv;
   double *dx, *dy, *out1, *out2, *dscal;
   int *iscal;
-  const int *qp_of_slot;                // slot (tile*BT + b) -> global QP id, -1 = empty (compaction during a solve)
   double *x_out, *y_out;                // QP-major [B][n], [B][m]
   double *xs_global;                    // non-null: the solve vector lives here ([tile][xs_len][BT]) instead of LDS
   int xs_len;                           // length of the solve vector: Analysis::Next >= n + m
@@ -163,9 +162,6 @@ hipError_t launch_warm_start(const KernelArgs &a, int BT, int tiles, int threads
 hipError_t launch_interleave(const double *src, double *dst, const int *ids, int nq, int len, int BT, hipStream_t st);
 hipError_t launch_scatter(const double *src, double *dst, const int *map, const int *ids, int nq, int srclen,
                           const SchedDev &sd, int BT, hipStream_t st);
-hipError_t launch_swap_plain(double *base, const int2 *pairs, int npairs, int len, int BT, hipStream_t st);
-hipError_t launch_swap_int(int *base, const int2 *pairs, int npairs, int len, int BT, hipStream_t st);
-hipError_t launch_swap_sched(double *base, const int2 *pairs, int npairs, const SchedDev &sd, int BT, hipStream_t st);
 hipError_t launch_deinterleave(const double *src, double *dst, int nq, int len, int BT, hipStream_t st);
 // Row E2 on the device (ruiz_kernel): new raw A values (and bounds) of every QP of the batch -> unscale, Ruiz rescale,
 // scaled bounds; one workgroup per QP, the arithmetic and its order are those of host_core.cpp scale_qp / unscale_qp.

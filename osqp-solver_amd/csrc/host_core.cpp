@@ -1010,10 +1010,34 @@ static void build_block_factor(Analysis &an) {
   }
 }
 
+// --------------------------------------------------------------------- tuning
+
+Tuning tuning_from_env() {
+  Tuning t;
+  if (const char *e = getenv("MI_OSQP_TILE")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) t.tile = v; }
+  if (const char *e = getenv("MI_OSQP_THREADS")) t.threads = std::max(64, std::min(1024, atoi(e) / 64 * 64));
+  t.global_xs = getenv("MI_OSQP_GLOBAL_XS") != nullptr;
+  if (const char *e = getenv("MI_OSQP_GROUPS")) t.groups = std::max(0, std::min(256, atoi(e)));
+  if (const char *e = getenv("MI_OSQP_GROUP_THREADS")) t.group_threads = std::max(64, std::min(512, atoi(e) / 64 * 64));
+  if (const char *e = getenv("MI_OSQP_ASSUME_CUS")) t.assume_cus = std::max(0, atoi(e));
+  if (const char *e = getenv("MI_OSQP_FACTOR_THREADS")) t.factor_threads = std::max(64, std::min(1024, atoi(e) / 64 * 64));
+  if (const char *e = getenv("MI_OSQP_FACTOR_GROUPS")) t.factor_groups = std::max(1, std::min(256, atoi(e)));
+  t.ruiz = getenv("MI_OSQP_HOST_RUIZ") ? 1 : getenv("MI_OSQP_DEVICE_RUIZ") ? -1 : 0;
+  if (const char *e = getenv("MI_OSQP_CONT_RING_KB")) t.cont_ring_kb = std::max(0L, atol(e));
+  if (const char *e = getenv("MI_OSQP_ANALYSIS_CACHE")) t.analysis_cache = atoi(e) != 0;
+  AnalysisTuning &a = t.analysis;
+  if (const char *e = getenv("MI_OSQP_DENSE_TAIL")) a.dense_tail = atoi(e);
+  if (const char *e = getenv("MI_OSQP_ORDERING")) a.ordering = e[0];
+  if (const char *e = getenv("MI_OSQP_ND_LEAF")) a.nd_leaf = atoi(e);
+  if (const char *e = getenv("MI_OSQP_RELAX")) a.relax = atoi(e);
+  a.serial = getenv("MI_OSQP_SERIAL_ANALYSIS") != nullptr;
+  return t;
+}
+
 // --------------------------------------------------------------------- analyze
 
 int analyze(int64_t n64, int64_t m64, const int64_t *Pp, const int64_t *Pi, const int64_t *Ap,
-            const int64_t *Ai, Analysis &an, int nwaves, int bt, int max_extra_rows, int dense_tail_max, int tri_waves, int n_tiles) {
+            const int64_t *Ai, const AnalysisTuning &tune, Analysis &an, int nwaves, int bt, int max_extra_rows, int dense_tail_max, int tri_waves, int n_tiles) {
   if (nwaves < 1 || nwaves > 16 || (bt != 1 && bt != 2 && bt != 4) || tri_waves < 0 || tri_waves > 2048) return MI_OSQP_ERR_INVALID_SETTINGS;
   if (n64 <= 0 || m64 < 0 || !Pp || !Ap || n64 + m64 > (int64_t)1 << 30) return MI_OSQP_ERR_INVALID_DATA;
   int n = (int)n64, m = (int)m64, N = n + m;
@@ -1129,8 +1153,7 @@ int analyze(int64_t n64, int64_t m64, const int64_t *Pp, const int64_t *Pi, cons
     an.dt = DenseTail();
     int64_t tail_nnz_used = 0;
     {
-      const char *e = getenv("MI_OSQP_DENSE_TAIL");
-      const int forced = e ? atoi(e) : -1;
+      const int forced = tune.dense_tail;
       const int kmax = std::min({forced == 0 ? 0 : dense_tail_max, N - 1, max_extra_rows / 2});
       int64_t tail_nnz = 0, best_gain = 0;
       int best_k = 0;
@@ -1200,7 +1223,7 @@ int analyze(int64_t n64, int64_t m64, const int64_t *Pp, const int64_t *Pi, cons
     const bool dbg_t = getenv("MI_OSQP_DEBUG_ORDER") != nullptr;
     auto now_ = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tt = now_();
-    const char *force = getenv("MI_OSQP_ORDERING");       // "md" / "nd": experiments
+    const char force = tune.ordering;                    // 'm' / 'n': experiments
     // Candidates: minimum degree (works on the explicit elimination graph - quadratic on big meshes: 0.9 s at N = 160 k, where
     // nested dissection takes 0.2 s and wins anyway - so beyond 60 k rows only on request) and nested dissections with
     // several leaf sizes (all of them while the pattern is small enough for that to cost milliseconds; MI_OSQP_ND_LEAF
@@ -1214,12 +1237,11 @@ int analyze(int64_t n64, int64_t m64, const int64_t *Pp, const int64_t *Pi, cons
       double t_order = 0.0, t_final = 0.0;
     };
     std::vector<Cand> cands;
-    const bool try_md = (N <= 60000 && !(force && force[0] == 'n')) || (force && force[0] == 'm');
+    const bool try_md = (N <= 60000 && force != 'n') || force == 'm';
     if (try_md) cands.emplace_back();
-    if (!(force && force[0] == 'm')) {
+    if (force != 'm') {
       std::vector<int> leaves;
-      const char *el = getenv("MI_OSQP_ND_LEAF");
-      if (el && atoi(el) >= 2) leaves = {atoi(el)};
+      if (tune.nd_leaf >= 2) leaves = {tune.nd_leaf};
       else if (N <= 8000) leaves = {48, 24, 12, 8, 4};
       else if (N <= 60000) leaves = {48, 12};
       else leaves = {48};
@@ -1228,8 +1250,7 @@ int analyze(int64_t n64, int64_t m64, const int64_t *Pp, const int64_t *Pi, cons
     // Relaxed supernodes are a second form of every candidate: fewer phases per sweep (and a third fewer block tasks per
     // refactorisation) against a longer factor stream.  MI_OSQP_RELAX = 0: never, = z: always, up to z zeros per supernode;
     // default: decided below.  Barrier form only.
-    const char *er = getenv("MI_OSQP_RELAX");
-    const int relax_forced = er ? atoi(er) : -1;
+    const int relax_forced = tune.relax;
     const int relax_z = relax_forced > 0 ? relax_forced : ((relax_forced < 0 && tri_waves == 0 && N <= 60000) ? 16 : 0);      // (forcing works for every form: experiments)
     auto run_cand = [&](Cand &c) {
       double t0 = now_();
@@ -1240,7 +1261,7 @@ int analyze(int64_t n64, int64_t m64, const int64_t *Pp, const int64_t *Pi, cons
       if (relax_z) { c.rel = an; finalize(c.rel, c.perm, c.cost_rel, relax_z, &c.phases_rel, &c.stream_rel); }
       c.t_final = now_() - t0;
     };
-    if (cands.size() > 1 && N >= 1000 && !getenv("MI_OSQP_SERIAL_ANALYSIS")) {
+    if (cands.size() > 1 && N >= 1000 && !tune.serial) {
       std::vector<std::thread> th;
       for (size_t c = 1; c < cands.size(); c++) th.emplace_back([&, c] { run_cand(cands[c]); });
       run_cand(cands[0]);
@@ -1286,7 +1307,7 @@ int analyze(int64_t n64, int64_t m64, const int64_t *Pp, const int64_t *Pi, cons
     double t_chk = 0.0, t_bf = 0.0;
     auto chk_part = [&] { const double t = now_(); build_chk_schedule(an, tri_waves > 0 ? tri_waves : nwaves, bt); t_chk = now_() - t; };      // (dataflow form: check_kernel runs on the whole grid too)
     auto bf_part = [&] { const double t = now_(); build_block_factor(an); t_bf = now_() - t; };
-    const bool par = N >= 1000 && !getenv("MI_OSQP_SERIAL_ANALYSIS");
+    const bool par = N >= 1000 && !tune.serial;
     std::thread th_chk;
     if (par) th_chk = std::thread(chk_part);
     build_tri_schedules(an, tri_waves > 0 ? tri_waves : nwaves, bt, tri_waves > 0);

@@ -31,6 +31,34 @@ struct Settings {
 };
 int validate_settings(const Settings &s);   // 0 ok
 
+// Tuning switches (MI_OSQP_* environment variables, README "Switches"): read by tuning_from_env() when a handle is set up and
+// kept in the handle.  Every field's default is the measured choice (0 / -1 / false = decided by the code).
+struct AnalysisTuning {            // what analyze() reads
+  int dense_tail = -1;             // MI_OSQP_DENSE_TAIL: 0 never, k > 0 exactly k rows
+  char ordering = 0;               // MI_OSQP_ORDERING: 'm' minimum degree only, 'n' nested dissection only
+  int nd_leaf = 0;                 // MI_OSQP_ND_LEAF: >= 2 the only leaf size of nested dissection
+  int relax = -1;                  // MI_OSQP_RELAX: 0 never, z > 0 always, up to z explicit zeros per supernode
+  bool serial = false;             // MI_OSQP_SERIAL_ANALYSIS: the candidates one after the other
+  bool operator==(const AnalysisTuning &o) const {
+    return dense_tail == o.dense_tail && ordering == o.ordering && nd_leaf == o.nd_leaf && relax == o.relax && serial == o.serial;
+  }
+};
+struct Tuning {
+  int tile = 0;                    // MI_OSQP_TILE: 1, 2 or 4 QPs per tile
+  int threads = 0;                 // MI_OSQP_THREADS: threads per tile of the solve kernels (64 .. 1024)
+  bool global_xs = false;          // MI_OSQP_GLOBAL_XS: the solve vector in global memory
+  int groups = -1;                 // MI_OSQP_GROUPS: workgroups of a large single QP (0 = the barrier form in one workgroup)
+  int group_threads = 0;           // MI_OSQP_GROUP_THREADS: their threads (64 .. 512)
+  int assume_cus = 0;              // MI_OSQP_ASSUME_CUS: clamp those grids as if the device had no more CUs
+  int factor_threads = 1024;       // MI_OSQP_FACTOR_THREADS: threads per workgroup of the refactorisation
+  int factor_groups = 0;           // MI_OSQP_FACTOR_GROUPS: workgroups sharing a QP of a short refactorisation list (1 .. 256)
+  int ruiz = 0;                    // MI_OSQP_HOST_RUIZ: 1 host equilibration, MI_OSQP_DEVICE_RUIZ: -1 device
+  long cont_ring_kb = -1;          // MI_OSQP_CONT_RING_KB: staging ring of the per-QP calls
+  bool analysis_cache = true;      // MI_OSQP_ANALYSIS_CACHE=0 switches the cache off
+  AnalysisTuning analysis;
+};
+Tuning tuning_from_env();
+
 // One pull-schedule: every target row t gets  xs[t] -= sum_k val[k] * xs[idx[k]]  (or xs[t] = sum, "store").
 //
 // Work is organised as PHASES separated by workgroup barriers; in every phase each of the nw waves owns one
@@ -233,8 +261,9 @@ struct Analysis {
 // dense tail): the forward / backward step streams and the check schedule are laid out for that many waves (of any number
 // of workgroups; a kernel with fewer waves walks the barrier-free check streams one after the other).  0 = the barrier form
 // (one workgroup of nwaves waves per tile).
+// `tune` = the switches of the caller's handle (Tuning::analysis).
 int analyze(int64_t n, int64_t m, const int64_t *Pp, const int64_t *Pi, const int64_t *Ap,
-            const int64_t *Ai, Analysis &an, int nwaves = 8, int bt = 1, int max_extra_rows = -1,
+            const int64_t *Ai, const AnalysisTuning &tune, Analysis &an, int nwaves = 8, int bt = 1, int max_extra_rows = -1,
             int dense_tail_max = 512, int tri_waves = 0, int n_tiles = 1);
 // `n_tiles` = tiles of the batch the analysis is for (they share the device's memory bandwidth: the decision for relaxed
 // supernodes weighs fewer phases against a longer factor stream).

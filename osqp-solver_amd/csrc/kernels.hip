@@ -1007,9 +1007,6 @@ __device__ __forceinline__ int check_body(const KernelArgs &a, double *smem, int
   double *red;
   double *xs = solve_vector<BT, GX>(a, smem, tile, red);
   const TilePtrs<BT> p = tile_ptrs<BT>(a, tile, true);
-  // global QP id of this thread's class: during a solve the QPs still iterating are
-  // compacted into the leading tiles (solver.hip), so the id comes from a table
-  const int qp = a.qp_of_slot[tile * BT + b];
   int done = p.iscal[IS_DONE * BT + b];
   if (__syncthreads_and(done)) return 0;
   const int iter = p.iscal[IS_CUR * BT + b] + n_iter;
@@ -1180,6 +1177,8 @@ __device__ __forceinline__ int check_body(const KernelArgs &a, double *smem, int
   // outputs for QPs that finished in this pass (done is uniform per class b)
   const int just_done = done && (p.iscal[IS_DONE * BT + b] == 0);
   sync();
+  // QP of this thread's class: its slot (the padding slots of the last tile have none)
+  const int slot = tile * BT + b, qp = slot < a.B ? slot : -1;
   if (just_done && qp >= 0) {
     const bool has_sol = !(status == -3 || status == 3 || status == -4 || status == 4 || status == -7);
     const double nanv = __builtin_nan("");
@@ -1236,7 +1235,7 @@ __global__ __launch_bounds__(NT) void advance_kernel(KernelArgs a, AdvanceArgs v
   extern __shared__ double smem[];
   const int tile = blockIdx.x, tid = threadIdx.x;
   int *is = a.iscal + (size_t)tile * IS_COUNT * BT;
-  // solves begun (or resumed after their refactorisation) on the handle's second stream join the first launch that sees them
+  // solves begun (or resumed after their refactorisation) since the last launch join the first launch that sees them
   if (tid < BT && __hip_atomic_load(&is[IS_PENDING * BT + tid], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 1) {
     is[IS_PENDING * BT + tid] = 0; is[IS_DONE * BT + tid] = 0;
   }
@@ -1253,8 +1252,8 @@ __global__ __launch_bounds__(NT) void advance_kernel(KernelArgs a, AdvanceArgs v
     const int ev = check_body<BT, NT, false>(a, smem, v.seg_len);
     if ((ev & 1) && v.stop && tid == 0) __hip_atomic_store(v.stop, v.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (ev & 2) {
-      // a QP whose rho changed pauses (reads "done") until the refactorisation kernels, which follow on the second stream,
-      // have given it its new factor: the other QPs of the tile and of the launch go on
+      // a QP whose rho changed pauses (reads "done") until the refactorisation kernels, which follow this launch, have
+      // given it its new factor: the other QPs of the tile and of the launch go on
       __syncthreads();
       if (tid < BT && is[IS_NEED_REFACTOR * BT + tid] == 1 && !is[IS_DONE * BT + tid]) { is[IS_DONE * BT + tid] = 1; is[IS_PENDING * BT + tid] = 2; }
     }
@@ -1451,7 +1450,7 @@ size_t spmv_fused_lds_bytes(int n, int m, int pa_len, int BT) { return ((size_t)
 hipError_t launch_spmv_fused(const KernelArgs &a, const SpmvFused &t, int BT, int tiles, int n_cus, hipStream_t st,
                              const double *x, const double *y, double *Px, double *Aty, double *Ax) {
   (void)n_cus;
-  if (t.ell && tiles % 8 == 0 && !getenv("MI_OSQP_SPMV_TILE")) {      // one QP per workgroup
+  if (t.ell && tiles % 8 == 0) {      // one QP per workgroup
     const size_t lq = spmv_fused_lds_bytes(a.n, a.m, t.pa_len, 1);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&spmv_fused_qp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lq);
     if (e != hipSuccess) return e;
@@ -2141,7 +2140,7 @@ bool factor_fits_lds(const FactorArgs &a, int threads) {
 }
 hipError_t launch_factor(const FactorArgs &a, int BT, int tiles, int threads, hipStream_t st) {
   // one QP per workgroup, no dense tail (its kernels read the block storage), everything within LDS: the LDS-resident form
-  if (BT == 1 && a.mw_groups <= 1 && !getenv("MI_OSQP_FACTOR_GLOBAL") && factor_fits_lds(a, threads)) return launch_factor_t<1, true>(a, tiles, threads, st);
+  if (BT == 1 && a.mw_groups <= 1 && factor_fits_lds(a, threads)) return launch_factor_t<1, true>(a, tiles, threads, st);
   switch (BT) {
     case 1: return launch_factor_t<1>(a, tiles, threads, st);
     case 2: return launch_factor_t<2>(a, tiles, threads, st);
@@ -2623,38 +2622,6 @@ __global__ void scatter_kernel(const double *__restrict__ src, double *dst, cons
   dst[(size_t)q * slots + s] = slot_value(map[s], src + (size_t)j * srclen, 1, 0);      // one stream per QP: [q][slot]
   (void)BT;
 }
-// Compaction support: exchange the complete per-QP contents of slot pairs (slot =
-// tile*BT + b).  Every array is [tile][len][BT].
-__global__ void swap_plain_kernel(double *base, const int2 *pairs, int npairs, int len, int BT) {
-  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (size_t)npairs * len) return;
-  const int2 pr = pairs[g / len];
-  const int i = (int)(g % len);
-  double *pa = base + ((size_t)(pr.x / BT) * len + i) * BT + pr.x % BT;
-  double *pb = base + ((size_t)(pr.y / BT) * len + i) * BT + pr.y % BT;
-  const double t = *pa; *pa = *pb; *pb = t;
-}
-__global__ void swap_int_kernel(int *base, const int2 *pairs, int npairs, int len, int BT) {
-  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (size_t)npairs * len) return;
-  const int2 pr = pairs[g / len];
-  const int i = (int)(g % len);
-  int *pa = base + ((size_t)(pr.x / BT) * len + i) * BT + pr.x % BT;
-  int *pb = base + ((size_t)(pr.y / BT) * len + i) * BT + pr.y % BT;
-  const int t = *pa; *pa = *pb; *pb = t;
-}
-__global__ void swap_sched_kernel(double *base, const int2 *pairs, int npairs, SchedDev sd, int BT) {
-  const size_t per = (size_t)sd.n_steps * 64;
-  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (size_t)npairs * per) return;
-  const int2 pr = pairs[g / per];
-  const size_t u = g % per;
-  double *pa = base + (size_t)pr.x * per + u;        // one stream per slot
-  double *pb = base + (size_t)pr.y * per + u;
-  const double t = *pa; *pa = *pb; *pb = t;
-  (void)BT;
-}
-
 // dst[q][i] = src[tile][i][b]
 __global__ void deinterleave_kernel(const double *__restrict__ src, double *dst, int nq, int len, int BT) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2676,15 +2643,15 @@ __global__ void fail_slots_kernel(KernelArgs a, const int *__restrict__ slots, i
   const int slot = slots[blockIdx.x], tid = threadIdx.x, nthr = blockDim.x;
   if (slot < 0) return;
   const size_t tile = (size_t)slot / BT, b = (size_t)slot % BT;
-  const int qp = a.qp_of_slot ? a.qp_of_slot[slot] : slot;
+  const int qp = slot < a.B ? slot : -1;
   const double nanv = __builtin_nan("");
   for (int i = tid; i < a.n; i += nthr) {
     a.x[(tile * a.n + i) * BT + b] = 0.0;
-    if (qp >= 0 && qp < a.B) a.x_out[(size_t)qp * a.n + i] = nanv;
+    if (qp >= 0) a.x_out[(size_t)qp * a.n + i] = nanv;
   }
   for (int j = tid; j < a.m; j += nthr) {
     a.z[(tile * a.m + j) * BT + b] = 0.0; a.y[(tile * a.m + j) * BT + b] = 0.0;
-    if (qp >= 0 && qp < a.B) a.y_out[(size_t)qp * a.m + j] = nanv;
+    if (qp >= 0) a.y_out[(size_t)qp * a.m + j] = nanv;
   }
   if (tid == 0) {
     int *is = a.iscal + tile * IS_COUNT * BT;
@@ -3124,8 +3091,7 @@ static hipError_t launch_ruiz_reg(const RuizArgs &a, size_t lds, hipStream_t st)
 hipError_t launch_ruiz(const RuizArgs &a, hipStream_t st) {
   if (a.B <= 0) return hipSuccess;
   const long pa_len = (long)a.nnzP + a.nnzA;
-  static const bool global_form = getenv("MI_OSQP_RUIZ_GLOBAL") != nullptr;      // (tests: the two forms give the same bits)
-  if (!global_form && (long)a.n + a.m <= 16384 && pa_len <= 32 * 512) {
+  if ((long)a.n + a.m <= 16384 && pa_len <= 32 * 512) {
     const size_t lds = ((size_t)a.n + a.m) * sizeof(double);
     if (pa_len <= 4 * 512) return launch_ruiz_reg<4>(a, lds, st);
     if (pa_len <= 8 * 512) return launch_ruiz_reg<8>(a, lds, st);
@@ -3432,22 +3398,6 @@ hipError_t launch_scatter(const double *src, double *dst, const int *map, const 
                           const SchedDev &sd, int BT, hipStream_t st) {
   if (!nq || !sd.n_slots) return hipSuccess;
   hipLaunchKernelGGL(scatter_kernel, dim3(nblk((size_t)nq * sd.n_slots, 256)), dim3(256), 0, st, src, dst, map, ids, nq, srclen, sd, BT);
-  return hipGetLastError();
-}
-hipError_t launch_swap_plain(double *base, const int2 *pairs, int npairs, int len, int BT, hipStream_t st) {
-  if (!npairs || !len) return hipSuccess;
-  hipLaunchKernelGGL(swap_plain_kernel, dim3(nblk((size_t)npairs * len, 256)), dim3(256), 0, st, base, pairs, npairs, len, BT);
-  return hipGetLastError();
-}
-hipError_t launch_swap_int(int *base, const int2 *pairs, int npairs, int len, int BT, hipStream_t st) {
-  if (!npairs || !len) return hipSuccess;
-  hipLaunchKernelGGL(swap_int_kernel, dim3(nblk((size_t)npairs * len, 256)), dim3(256), 0, st, base, pairs, npairs, len, BT);
-  return hipGetLastError();
-}
-hipError_t launch_swap_sched(double *base, const int2 *pairs, int npairs, const SchedDev &sd, int BT, hipStream_t st) {
-  if (!npairs) return hipSuccess;
-  const size_t per = (size_t)sd.n_steps * 64;
-  hipLaunchKernelGGL(swap_sched_kernel, dim3(nblk((size_t)npairs * per, 256)), dim3(256), 0, st, base, pairs, npairs, sd, BT);
   return hipGetLastError();
 }
 hipError_t launch_deinterleave(const double *src, double *dst, int nq, int len, int BT, hipStream_t st) {

@@ -262,6 +262,7 @@ struct SchedBufs {
 
 struct mi_osqp_batch {
   Settings st;
+  Tuning tune;                                // the MI_OSQP_* switches, read once at setup (tuning_from_env)
   std::shared_ptr<const Analysis> anp;        // pattern analysis: shared between the handles of one pattern (analysis cache below)
   int B = 0, BT = 1, ntiles = 0, threads = 512, device = 0, n_cus = 256;
   size_t lds = 0;
@@ -279,8 +280,7 @@ struct mi_osqp_batch {
   DevBuf<double> mw_scratch;            // partial norms / sums of the grid-wide check_kernel
   DevBuf<double> fwd_val0, bwd_val0, dinv0, rho_vec0, rho_inv0, dscal0;   // setup snapshot (reset)
   DevBuf<int> use_work;                       // per slot: the current factor is the working copy (KernelArgs::use_work)
-  DevBuf<int> iscal, qp_of_slot, flag, npos;
-  DevBuf<int2> pairs;
+  DevBuf<int> iscal, flag, npos;
   // device refactorisation (BlockFactor tables + scratch)
   DevBuf<uint32_t> bf_blk, bf_lvl, bf_utask, bf_tri, bf_dtask, bf_ttask, bf_asm_dst, bf_asm_src, bf_ubig;
   DevBuf<int32_t> fwd_srcblk, bwd_srcblk;
@@ -315,7 +315,7 @@ struct mi_osqp_batch {
   mi_osqp_stats stats{};
   // last-solve accounting
   int64_t last_total_iters = 0, last_launches = 0, last_refactors = 0;
-  double last_device_s = 0.0, last_refactor_s = 0.0, last_compact_s = 0.0, kernel_ms_sum = 0.0;
+  double last_device_s = 0.0, last_refactor_s = 0.0, kernel_ms_sum = 0.0;
   int64_t kernel_launches = 0, kernel_qp_iters = 0;
   bool solved_once = false;
   // per-QP failure isolation: QPs whose KKT factor lost its inertia (at setup, in an update or in a rho update).  They
@@ -346,29 +346,22 @@ struct mi_osqp_batch {
     DevBuf<char> ring_d;
     DevBuf<int> work;                        // device-built refactorisation work list of an advance
     // The per-QP calls (new data, equilibration, refactorisation, warm start, begin) and the refactorisations after rho
-    // updates run on a second stream next to the advance launches: a QP that iterates through hundreds of segments must not
-    // wait for the other QPs' updates.  Nothing orders the two streams: a begun solve carries a pending mark that the next
-    // advance launch to see it takes up (IS_PENDING), a QP whose rho changed pauses until its refactorisation has run, and
-    // the host tells a finished solve from the slot's previous one by its epoch (IS_EPOCH).
-    hipStream_t ustream = nullptr;
-    bool own_ustream = false;
+    // updates are enqueued on the handle's stream behind the advance launches.  A begun solve carries a pending mark that the
+    // next advance launch to see it takes up (IS_PENDING), a QP whose rho changed pauses until its refactorisation has run,
+    // and the host tells a finished solve from the slot's previous one by its epoch (IS_EPOCH).
     hipEvent_t ev_adv = nullptr;             // behind the last advance launch (the refactorisation kernels wait for it)
     std::vector<int> epoch;                  // per QP: solves begun so far (what IS_EPOCH reads once the begin has run)
-    DevBuf<double> rz_scratch;               // equilibration scratch of that stream (not the check kernels': they may be running)
+    DevBuf<double> rz_scratch;               // equilibration scratch of the per-QP calls (not the check kernels')
     double *keepA = nullptr, *keepl = nullptr, *keepu = nullptr;   // a mi_gomp_scene's QP-major copy of the raw rows: reinit / update keep it current
     DevBuf<unsigned> counter;                // tiles that have left the advance launch in flight
     unsigned *h_done = nullptr; size_t h_done_cap = 0;      // pinned: [0] sequence number of the last advance launch that is over, [1] tiles that iterated in it
-    unsigned last_active = 0;                // tiles that iterated in the last launch polled
-    hipEvent_t ev_u = nullptr;               // end of the second stream's queue (a launch after an idle one waits for it)
   } cont;
   ~mi_osqp_batch() {
     DevGuard guard(device);
     if (stream) (void)hipStreamSynchronize(stream);      // (the buffers go back to their pools right after: DevBuf remembers its device)
     for (int k = 0; k < 2; k++) { hostpool::give(cont.h_is[k], cont.h_is_cap[k]); hostpool::give(cont.h_ds[k], cont.h_ds_cap[k]); if (cont.ev[k]) (void)hipEventDestroy(cont.ev[k]); }
     hostpool::give(cont.xh, cont.xh_cap); hostpool::give(cont.yh, cont.yh_cap); hostpool::give(cont.ring_h, cont.ring_h_cap);
-    if (cont.ustream && cont.own_ustream) { (void)hipStreamSynchronize(cont.ustream); (void)hipStreamDestroy(cont.ustream); }
     if (cont.ev_adv) (void)hipEventDestroy(cont.ev_adv);
-    if (cont.ev_u) (void)hipEventDestroy(cont.ev_u);
     hostpool::give(cont.h_done, cont.h_done_cap);
     hostpool::give(h_iscal, h_iscal_cap); hostpool::give(h_dscal, h_dscal_cap); hostpool::give(pin, pin_cap); hostpool::give(h_npos, h_npos_cap);
     if (stream && ev0 && ev1 && evf0 && evf1 && evf2) streampool::give({device, stream, {ev0, ev1, evf0, evf1, evf2}});
@@ -394,12 +387,6 @@ static Settings to_settings(const mi_osqp_settings *s) {
   return t;
 }
 
-// threads per tile of the refactorisation kernel (experiments: MI_OSQP_FACTOR_THREADS)
-static int factor_threads() {
-  const char *e = getenv("MI_OSQP_FACTOR_THREADS");
-  return e ? std::max(64, std::min(1024, atoi(e) / 64 * 64)) : 1024;
-}
-
 static size_t lds_bytes(int N, int BT, int threads) {
   int nw = threads / 64;
   return ((size_t)N * BT + (size_t)nw * 14 * BT + 14 * BT) * sizeof(double);
@@ -416,7 +403,7 @@ static KernelArgs make_args(mi_osqp_batch *h) {
   a.x = h->x.p; a.z = h->z.p; a.y = h->y.p; a.q = h->q.p; a.l = h->l.p; a.u = h->u.p;
   a.rho_vec = h->rho_vec.p; a.rho_inv = h->rho_inv.p; a.Dsc = h->Dsc.p; a.Dsc_inv = h->Dsc_inv.p;
   a.Esc = h->Esc.p; a.Esc_inv = h->Esc_inv.p; a.dx = h->dx.p; a.dy = h->dy.p; a.out1 = h->out1.p; a.out2 = h->out2.p;
-  a.dscal = h->dscal.p; a.iscal = h->iscal.p; a.qp_of_slot = h->qp_of_slot.p;
+  a.dscal = h->dscal.p; a.iscal = h->iscal.p;
   a.x_out = h->x_out.p; a.y_out = h->y_out.p;
   a.xs_global = h->global_xs ? h->xs_global.p : nullptr; a.xs_len = (*h->anp).xs_total; a.wide = (*h->anp).wide ? 1 : 0;
   a.mw_groups = h->mw_groups; a.mw_bar = h->mw_bar.p; a.mw_scratch = h->mw_scratch.p;
@@ -645,7 +632,7 @@ static int reset_solve_state(mi_osqp_batch *h, bool cold) {
 // by a full comparison) and shared read-only between handles.  MI_OSQP_ANALYSIS_CACHE=0 switches the cache off.
 namespace ancache {
 struct Entry {
-  uint64_t hash; int64_t n, m; int nw, bt, max_extra, dt_max, tri_waves, n_tiles; std::string env;
+  uint64_t hash; int64_t n, m; int nw, bt, max_extra, dt_max, tri_waves, n_tiles; AnalysisTuning tune;
   std::vector<int64_t> Pp, Pi, Ap, Ai;
   std::shared_ptr<const Analysis> an;           // null while a thread is still computing it (mi_osqp_prefetch_analysis): others wait
 };
@@ -660,17 +647,15 @@ static uint64_t fnv(uint64_t h, const void *p, size_t bytes) {
 }
 }  // namespace ancache
 
-static int cached_analysis(int64_t n, int64_t m, const int64_t *Pp, const int64_t *Pi, const int64_t *Ap, const int64_t *Ai, int nw,
-                           int bt, int max_extra, int dt_max, int tri_waves, int n_tiles, std::shared_ptr<const Analysis> &out) {
+static int cached_analysis(int64_t n, int64_t m, const int64_t *Pp, const int64_t *Pi, const int64_t *Ap, const int64_t *Ai, const Tuning &tune,
+                           int nw, int bt, int max_extra, int dt_max, int tri_waves, int n_tiles, std::shared_ptr<const Analysis> &out) {
   n_tiles = n_tiles <= 1 ? 1 : (n_tiles <= 32 ? 32 : (n_tiles <= 128 ? 128 : (n_tiles <= 256 ? 256 : 512)));      // (buckets: the analysis is shared between handles)
-  const char *off = getenv("MI_OSQP_ANALYSIS_CACHE");
-  const bool use = !(off && atoi(off) == 0) && n > 0 && m >= 0 && Pp && Ap && Pp[0] == 0 && Ap[0] == 0 && Pp[n] >= 0 && Ap[n] >= 0 &&
+  const bool use = tune.analysis_cache && n > 0 && m >= 0 && Pp && Ap && Pp[0] == 0 && Ap[0] == 0 && Pp[n] >= 0 && Ap[n] >= 0 &&
                    Pp[n] < ((int64_t)1 << 30) && Ap[n] < ((int64_t)1 << 30);
-  std::string env;                              // the knobs analyze() reads
-  for (const char *k : {"MI_OSQP_DENSE_TAIL", "MI_OSQP_ORDERING", "MI_OSQP_ND_LEAF", "MI_OSQP_RELAX"}) { const char *v = getenv(k); env += v ? v : "-"; env += ';'; }
   uint64_t hsh = 1469598103934665603ull;
   auto same = [&](const ancache::Entry &e) {
-    if (e.hash != hsh || e.n != n || e.m != m || e.nw != nw || e.bt != bt || e.max_extra != max_extra || e.dt_max != dt_max || e.tri_waves != tri_waves || e.n_tiles != n_tiles || e.env != env) return false;
+    if (e.hash != hsh || e.n != n || e.m != m || e.nw != nw || e.bt != bt || e.max_extra != max_extra || e.dt_max != dt_max || e.tri_waves != tri_waves || e.n_tiles != n_tiles ||
+        !(e.tune == tune.analysis)) return false;
     return (int64_t)e.Pi.size() == Pp[n] && (int64_t)e.Ai.size() == Ap[n] && !memcmp(e.Pp.data(), Pp, (size_t)(n + 1) * 8) &&
            !memcmp(e.Pi.data(), Pi, (size_t)Pp[n] * 8) && !memcmp(e.Ap.data(), Ap, (size_t)(n + 1) * 8) && !memcmp(e.Ai.data(), Ai, (size_t)Ap[n] * 8);
   };
@@ -691,11 +676,19 @@ static int cached_analysis(int64_t n, int64_t m, const int64_t *Pp, const int64_
     if (ancache::entries.size() >= ancache::kMaxEntries) {
       for (size_t i = 0; i < ancache::entries.size(); i++) if (ancache::entries[i].an) { ancache::entries.erase(ancache::entries.begin() + i); break; }
     }
-    ancache::entries.push_back(ancache::Entry{hsh, n, m, nw, bt, max_extra, dt_max, tri_waves, n_tiles, env, {Pp, Pp + n + 1}, {Pi, Pi + Pp[n]}, {Ap, Ap + n + 1}, {Ai, Ai + Ap[n]}, nullptr});
+    ancache::entries.push_back(ancache::Entry{hsh, n, m, nw, bt, max_extra, dt_max, tri_waves, n_tiles, tune.analysis, {Pp, Pp + n + 1}, {Pi, Pi + Pp[n]}, {Ap, Ap + n + 1}, {Ai, Ai + Ap[n]}, nullptr});
   }
-  auto an = std::make_shared<Analysis>();
-  const int rc = analyze(n, m, Pp, Pi, Ap, Ai, *an, nw, bt, max_extra, dt_max, tri_waves, n_tiles);
-  if (!rc) out = an;
+  // (an exception - bad_alloc on a huge pattern - is an error like any other: the placeholder must go, or every later setup
+  //  of this pattern waits for it forever)
+  int rc;
+  try {
+    auto an = std::make_shared<Analysis>();
+    rc = analyze(n, m, Pp, Pi, Ap, Ai, tune.analysis, *an, nw, bt, max_extra, dt_max, tri_waves, n_tiles);
+    if (!rc) out = an;
+  } catch (const std::exception &e) {
+    g_last_error = std::string("pattern analysis: ") + e.what();
+    rc = MI_OSQP_ERR_ALLOC;
+  }
   if (use) {
     std::lock_guard<std::mutex> lk(ancache::mu);
     for (size_t i = 0; i < ancache::entries.size(); i++)
@@ -719,7 +712,6 @@ static std::mutex &spin_mutex(int device) {
   return mu[(unsigned)device % 64u];
 }
 static int restore_snapshot(mi_osqp_batch *h);
-static int materialise_working(mi_osqp_batch *h);
 static int cont_leave(mi_osqp_batch *h);      // (a blocking call ends the continuous mode of a handle: section "continuous")
 
 // multi-workgroup mode: a grid barrier that gave up waiting (a workgroup of the grid was not resident) leaves its error
@@ -735,16 +727,12 @@ static int mw_barrier_ok(mi_osqp_batch *h) {
 // The launch shape of a handle (threads per workgroup, QPs per tile, where the solve vector lives, the grid of a large single
 // QP): what the pattern analysis is built for.  Shared by setup and by mi_osqp_prefetch_analysis.
 static void derive_shape(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, int64_t device, int &BT_out, int &max_extra_out) {
-  const char *eth = getenv("MI_OSQP_THREADS");
-  h->threads = eth ? std::max(64, std::min(1024, atoi(eth) / 64 * 64)) : 512;
+  const Tuning &tu = h->tune;
+  h->threads = tu.threads ? tu.threads : 512;
   // ---- tile shape (needed by the schedule layout)
   // 2 QPs per tile: iterate_kernel<2> needs 112 VGPRs, so two 512-thread workgroups share a CU and
   // cover each other's barrier stalls; measured best on the 1024-QP headline batch (4 and 1 are slower)
-  int BT = B >= 384 ? 2 : 1;
-  {
-    const char *et = getenv("MI_OSQP_TILE");
-    if (et && (atoi(et) == 1 || atoi(et) == 2 || atoi(et) == 4)) BT = atoi(et);
-  }
+  int BT = tu.tile ? tu.tile : (B >= 384 ? 2 : 1);
   // vectors of 65 535 entries and more: 32-bit index words (twice the index bytes), the solve vector in global
   // memory, one QP per tile, 512 threads (the only instantiation of the wide kernels)
   const bool wide = n + m >= 65535 || 2 * n + m >= 65535;
@@ -756,7 +744,7 @@ static void derive_shape(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, int6
   // LDS: 1 024 against 512 threads measured -10 % on 256 GOMP QPs (7 DOF x 100 waypoints), -18 % on 1 024 of them (2 per
   // tile, 100 KB), -4..7 % on 128-QP shards of the headline batch; the headline batch itself (512 tiles of 40 KB: two
   // 8-wave workgroups per CU cover each other's barrier stalls) stays at 8 waves
-  if (!eth && !wide && BT <= 2 && !getenv("MI_OSQP_GLOBAL_XS") && lds_bytes((int)(n + m), BT, 1024) <= lds_cap) {     // (16-wave kernels: 1 or 2 QPs per tile)
+  if (!tu.threads && !wide && BT <= 2 && !tu.global_xs && lds_bytes((int)(n + m), BT, 1024) <= lds_cap) {     // (16-wave kernels: 1 or 2 QPs per tile)
     int dev = (int)device, cus = 256;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
@@ -765,7 +753,7 @@ static void derive_shape(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, int6
     if (tiles <= cus || lds_bytes((int)(n + m), BT, 1024) > 80 * 1024) h->threads = 1024;
   }
   // too large for LDS even at one QP per tile: the solve vector goes to a per-tile global buffer
-  h->global_xs = wide || lds_bytes((int)(n + m), BT, h->threads) > lds_cap || getenv("MI_OSQP_GLOBAL_XS") != nullptr;
+  h->global_xs = wide || lds_bytes((int)(n + m), BT, h->threads) > lds_cap || tu.global_xs;
   // rows that may get a second vector position (phase B of the solves): what still fits LDS (analyze() also
   // respects the 16-bit index range of the narrow index words)
   int max_extra = -1;
@@ -780,7 +768,6 @@ static void derive_shape(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, int6
   // level costs more than the level: DESIGN.md 7.4).  MI_OSQP_GROUPS = 0: the barrier form, one workgroup.
   h->mw_groups = 0; h->mw_threads = 0;
   if (h->global_xs && BT == 1 && B == 1 && h->threads <= 512) {
-    const char *eg = getenv("MI_OSQP_GROUPS"), *ew = getenv("MI_OSQP_GROUP_THREADS");
     // measured on the 316 x 316 grid of config 5 (scripts/mw_probe.py, ms per iteration): 16 x 512 threads 1.56, 32 x 512 1.23,
     // 64 x 256 1.06, 128 x 128 1.01, 256 x 128 0.97 (the barrier form in one workgroup: 6.5); 150 x 150 grid: 128 x 128 0.40
     // (round 3, same probe: 316 x 316 grid 128 x 128 threads 0.868, 256 x 128 0.818, 192 x 128 0.823, 128 x 256 0.824, 256 x 64 0.899;
@@ -788,15 +775,15 @@ static void derive_shape(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, int6
     //  and smaller grids for the mid-size ones (`scripts/groups_probe.py`, ms per 25-iteration solve: the 802-waypoint trajectory QP,
     //  N = 43 284: 128 x 128 3.46, 64 x 128 3.25, 256 x 128 4.38; 402 waypoints, N = 21 684: 3.34 / 2.96, 32 x 128 2.93)
     const int64_t Nrows = n + m;
-    h->mw_groups = eg ? std::max(0, std::min(256, atoi(eg))) : (Nrows >= 250000 ? 256 : Nrows >= 60000 ? 128 : Nrows >= 30000 ? 64 : 32);
-    h->mw_threads = ew ? std::max(64, std::min(512, atoi(ew) / 64 * 64)) : 128;
+    h->mw_groups = tu.groups >= 0 ? tu.groups : (Nrows >= 250000 ? 256 : Nrows >= 60000 ? 128 : Nrows >= 30000 ? 64 : 32);
+    h->mw_threads = tu.group_threads ? tu.group_threads : 128;
     if (h->mw_groups * (h->mw_threads / 64) > 2048) h->mw_groups = 2048 / (h->mw_threads / 64);
     // never more workgroups than the device keeps resident at once (their waits are for each other): the schedules are
     // built for the clamped grid; a device that cannot hold two of them gets the barrier form in one workgroup
     int dev = (int)device, cus = 0;
     if ((dev >= 0 || hipGetDevice(&dev) == hipSuccess) && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) {
       DevGuard guard(dev);
-      { const char *ec = getenv("MI_OSQP_ASSUME_CUS"); if (ec && atoi(ec) > 0) cus = std::min(cus, atoi(ec)); }      // (tests: the clamp on a device with fewer CUs)
+      if (tu.assume_cus > 0) cus = std::min(cus, tu.assume_cus);      // (tests: the clamp on a device with fewer CUs)
       const int cap = max_coresident_groups(h->mw_threads, lds_bytes(0, 1, h->threads), cus);
       if (cap > 0 && h->mw_groups > cap) h->mw_groups = cap;
       if (h->mw_groups == 1) h->mw_groups = 0;
@@ -816,16 +803,16 @@ static void derive_shape(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, int6
 static int shape_and_analysis(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, const int64_t *Pp, const int64_t *Pi, const int64_t *Ap,
                               const int64_t *Ai, int64_t device, int &BT, int &max_extra, std::shared_ptr<const Analysis> &out) {
   derive_shape(h, B, n, m, device, BT, max_extra);
-  int rc = cached_analysis(n, m, Pp, Pi, Ap, Ai, h->threads / 64, BT, max_extra, h->global_xs ? 0 : 512, h->mw_groups * (h->mw_threads / 64), (int)((B + BT - 1) / BT), out);
+  int rc = cached_analysis(n, m, Pp, Pi, Ap, Ai, h->tune, h->threads / 64, BT, max_extra, h->global_xs ? 0 : 512, h->mw_groups * (h->mw_threads / 64), (int)((B + BT - 1) / BT), out);
   if (rc) return rc;
   const size_t lds_cap = 160 * 1024 - 1024;
-  if (out->dt.k > 0 && (BT != 1 || h->threads != 1024) && !h->global_xs && !getenv("MI_OSQP_TILE") && !getenv("MI_OSQP_THREADS") &&
-      !getenv("MI_OSQP_NO_DENSE_SHAPE") && lds_bytes((int)(n + m), 1, 1024) + (size_t)2 * 512 * sizeof(double) <= lds_cap) {
+  if (out->dt.k > 0 && (BT != 1 || h->threads != 1024) && !h->global_xs && !h->tune.tile && !h->tune.threads &&
+      lds_bytes((int)(n + m), 1, 1024) + (size_t)2 * 512 * sizeof(double) <= lds_cap) {
     const int BT2 = 1, thr2 = 1024;
     const size_t cap_rows = (lds_cap - lds_bytes(0, BT2, thr2)) / (sizeof(double) * BT2);
     const int max_extra2 = (int)(cap_rows - (size_t)(n + m));
     std::shared_ptr<const Analysis> an2;
-    rc = cached_analysis(n, m, Pp, Pi, Ap, Ai, thr2 / 64, BT2, max_extra2, 512, 0, (int)B, an2);
+    rc = cached_analysis(n, m, Pp, Pi, Ap, Ai, h->tune, thr2 / 64, BT2, max_extra2, 512, 0, (int)B, an2);
     if (!rc && an2->dt.k > 0) { BT = BT2; h->threads = thr2; max_extra = max_extra2; out = an2; }
   }
   return MI_OSQP_OK;
@@ -842,6 +829,7 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
   for (int64_t k = 0; k < B * m; k++) if (l[k] > u[k]) return MI_OSQP_ERR_INVALID_DATA;
   int BT = 1, max_extra = -1;
   const size_t lds_cap = 160 * 1024 - 1024;
+  h->tune = tuning_from_env();
   const double ta0 = now_s();
   int rc = shape_and_analysis(h, B, n, m, Pp, Pi, Ap, Ai, device, BT, max_extra, h->anp);
   const double t_analysis = now_s() - ta0;
@@ -909,7 +897,7 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
     if (h->dt_lds > lds_cap || h->dt_lds_asm > lds_cap) { g_last_error = "internal: LDS budget of tail_kernel exceeded"; return MI_OSQP_ERR_ALLOC; }
   }
 #undef ALLOC
-  if ((rc = h->iscal.alloc((size_t)IS_COUNT * T)) || (rc = h->qp_of_slot.alloc((size_t)h->ntiles * BT)) || (rc = h->flag.alloc(4))) return rc;
+  if ((rc = h->iscal.alloc((size_t)IS_COUNT * T)) || (rc = h->flag.alloc(4))) return rc;
   {
     const BlockFactor &bf = an.bf;
     if ((rc = h->bf_blk.upload(bf.blk)) || (rc = h->bf_lvl.upload(bf.lvl)) || (rc = h->bf_ubig.upload(bf.ubig)) || (rc = h->bf_utask.upload(bf.utask4)) ||
@@ -1093,17 +1081,16 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
 
 // ------------------------------------------------------------------- solve
 
-// Per-QP failure isolation: the slots of `bad` (slot = tile * BT + b; outside a solve slot == QP) become kNonConvex on
-// the device (fail_slots_kernel) and are remembered in h->failed.  qp_of_slot: the slot -> QP table of a solve in flight.
-static int fail_slots(mi_osqp_batch *h, KernelArgs a, const std::vector<int> &bad, const std::vector<int> *qp_of_slot, int iter) {
+// Per-QP failure isolation: the slots of `bad` (slot = tile * BT + b = QP) become kNonConvex on the device
+// (fail_slots_kernel) and are remembered in h->failed.
+static int fail_slots(mi_osqp_batch *h, const KernelArgs &a, const std::vector<int> &bad, int iter) {
   if (bad.empty()) return 0;
   int rc;
   if (h->fail_list.n < bad.size() && (rc = h->fail_list.alloc(std::max<size_t>(bad.size(), (size_t)h->ntiles * h->BT)))) return rc;
-  if (!qp_of_slot) a.qp_of_slot = nullptr;                   // identity layout
   HIPCHK(hipMemcpyAsync(h->fail_list.p, bad.data(), bad.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(launch_fail_slots(a, h->fail_list.p, (int)bad.size(), h->BT, iter, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  for (int s : bad) { const int q = qp_of_slot ? (*qp_of_slot)[s] : s; if (q >= 0 && q < h->B) h->failed[q] = 1; }
+  for (int q : bad) if (q >= 0 && q < h->B) h->failed[q] = 1;
   return 0;
 }
 
@@ -1119,8 +1106,7 @@ static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::v
   // latency-bound: 3.3 ms with one QP, 4.6 ms with two), the solve tiling otherwise (measured: 605 QPs take
   // 10.9 ms whether packed 1, 2 or 4 per workgroup - the memory system, not the tiling, is the limit there)
   const int nq = (int)work.size();
-  int kbt = nq <= h->n_cus ? 1 : BT;
-  { const char *e = getenv("MI_OSQP_FACTOR_BT"); if (e && (atoi(e) == 1 || atoi(e) == 2 || atoi(e) == 4)) kbt = atoi(e); }
+  const int kbt = nq <= h->n_cus ? 1 : BT;
   const int wtiles = (nq + kbt - 1) / kbt;
   work.resize((size_t)wtiles * kbt, -1);
   if (h->work.n < work.size() && (rc = h->work.alloc((size_t)h->ntiles * BT + 4))) return rc;
@@ -1133,11 +1119,10 @@ static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::v
   //  lone QP - 0.88 against 0.43 ms at config 2: a lone QP's levels hold hundreds of block tasks, the kernel is short of
   //  waves, not of memory latency - so short lists keep their groups and the LDS form serves one-workgroup-per-QP launches)
   if (kbt == 1 && h->mw_bar.p && (*h->anp).N >= 1000) {
-    const char *eg = getenv("MI_OSQP_FACTOR_GROUPS");
     const int cap = h->B == 1 ? std::max(4, std::min(64, (*h->anp).N / 600)) : 8;
-    int G = eg ? std::max(1, std::min(256, atoi(eg))) : cap;
+    int G = h->tune.factor_groups ? h->tune.factor_groups : cap;
     G = std::min(G, std::max(1, h->n_cus / wtiles));
-    static const int resident = max_coresident_factor_groups(factor_threads(), 1);      // workgroups of factor_kernel per CU
+    static const int resident = max_coresident_factor_groups(h->tune.factor_threads, 1);      // workgroups of factor_kernel per CU
     if (resident > 0) G = std::min(G, std::max(1, resident * h->n_cus / wtiles));
     fa.mw_groups = G > 1 ? G : 0;
   }
@@ -1145,7 +1130,7 @@ static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::v
   if (fa.mw_groups > 1) spin_lock.lock();
   HIPCHK(hipEventRecord(h->evf0, h->stream));
   if (fa.mw_groups > 1) HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t) * (size_t)wtiles, h->stream));
-  HIPCHK(launch_factor(fa, kbt, wtiles, factor_threads(), h->stream));
+  HIPCHK(launch_factor(fa, kbt, wtiles, h->tune.factor_threads, h->stream));
   HIPCHK(hipEventRecord(h->evf1, h->stream));
   if ((*h->anp).dt.k) {      // the tail blocks now hold the Schur complement: invert it into the stream of the symmetric product
     const DenseTail &dt = (*h->anp).dt;
@@ -1215,108 +1200,14 @@ static int refactor_qps(mi_osqp_batch *h, std::vector<int> qps) {
   int rc = device_refactor_slots(h, std::move(qps), &bad);
   if (rc) return rc;
   for (int q : listed) h->failed[q] = 0;
-  if ((rc = fail_slots(h, make_args(h), bad, nullptr, 0))) return rc;
+  if ((rc = fail_slots(h, make_args(h), bad, 0))) return rc;
   if ((int)bad.size() == h->B) { g_last_error = "the KKT factor lost its inertia"; return MI_OSQP_ERR_NONCONVEX; }
-  return 0;
-}
-
-// exchange the complete device state of slot pairs (slot = tile*BT + b)
-static int apply_swaps(mi_osqp_batch *h, const std::vector<int2> &pairs) {
-  if (pairs.empty()) return 0;
-  const Analysis &an = (*h->anp);
-  int np = (int)pairs.size(), BT = h->BT, n = an.n, m = an.m, rc;
-  if (h->pairs.n < pairs.size() && (rc = h->pairs.alloc(std::max<size_t>(pairs.size(), (size_t)h->ntiles * BT)))) return rc;
-  HIPCHK(hipMemcpyAsync(h->pairs.p, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-  hipStream_t st = h->stream;
-  HIPCHK(launch_swap_sched(h->fwd_val.p, h->pairs.p, np, h->fwd.view(an.fwd), BT, st));
-  HIPCHK(launch_swap_sched(h->bwd_val.p, h->pairs.p, np, h->bwd.view(an.bwd), BT, st));
-  HIPCHK(launch_swap_sched(h->chk_val.p, h->pairs.p, np, h->chk.view(an.chk), BT, st));
-  struct PL { double *p; int len; };
-  const PL plain[] = {{h->dinv.p, an.N}, {h->x.p, n}, {h->z.p, m}, {h->y.p, m}, {h->q.p, n}, {h->l.p, m}, {h->u.p, m},
-                      {h->rho_vec.p, m}, {h->rho_inv.p, m}, {h->Dsc.p, n}, {h->Dsc_inv.p, n}, {h->Esc.p, m}, {h->Esc_inv.p, m},
-                      {h->pa_val.p, an.Pp[n] + an.Ap[n]}, {h->dscal.p, DS_COUNT}};
-  for (const PL &a : plain) HIPCHK(launch_swap_plain(a.p, h->pairs.p, np, a.len, BT, st));
-  HIPCHK(launch_swap_int(h->iscal.p, h->pairs.p, np, IS_COUNT, BT, st));
   return 0;
 }
 
 // The ADMM loop runs in segments that end at every termination-check / rho-update
 // point: iterate_kernel (E6-E10) -> check_kernel (E11-E14) -> host reads the flags,
-// (optionally) compacts the QPs still iterating into the leading tiles (slot swaps on the device),
 // runs the device refactorisation for the QPs whose rho changed, and continues.
-// The swaps are undone at the end - also when the loop ends with an error - so outside a solve
-// every array is in the identity layout.
-static int gcd_i(int a, int b);
-static int segment_length(const Settings &S);
-static int ensure_advance_buffers(mi_osqp_batch *h);
-static int wait_launch_over(mi_osqp_batch *h, unsigned seq);
-
-// The latency regime - no more tiles than CUs, the solve vector in LDS (a lone trajectory QP, a strong-scaling shard, the
-// stragglers' world): the host round trip per segment (two launches, a copy of the flags, a stream synchronisation) is a
-// tenth to a third of such a solve.  Here ONE advance_kernel launch carries every QP to its end or to its next rho update
-// (the QP pauses), the host waits on a word in pinned memory, refactors the paused QPs with the grouped factor_kernel and
-// launches again: host round trips = rho-update rounds + 1.  Same arithmetic, same per-QP iteration counts.
-// Measured (round 3): NOT a win as it stands - advance_kernel's fused bodies iterate ~10 % slower than iterate_kernel
-// (register allocation shared with the check), which eats the saved round trips (config 2: 0.73 against 0.69 ms).  Hence
-// opt-in (MI_OSQP_ADVANCE_SOLVE=1; tests/test_gpu_continuous.py runs it for parity).
-static bool small_batch_path(const mi_osqp_batch *h) {
-  if (!getenv("MI_OSQP_ADVANCE_SOLVE")) return false;
-  if (h->global_xs || h->mw_groups > 0 || h->ntiles > h->n_cus || h->BT != 1) return false;      // (tiles of 2 QPs at 16 waves spill in the fused kernel)
-  if (getenv("MI_OSQP_COMPACT") && !(*h->anp).dt.k) return false;
-  return segment_length(h->st) >= 5;
-}
-static int solve_small(mi_osqp_batch *h, KernelArgs a) {
-  mi_osqp_batch::Cont &c = h->cont;
-  const int BT = h->BT, nslots = h->ntiles * BT, L = segment_length(h->st);
-  int rc;
-  if ((rc = ensure_advance_buffers(h))) return rc;
-  HIPCHK(hipMemsetAsync(c.counter.p, 0, 2 * sizeof(unsigned), h->stream));
-  a.info_at_end = 1;
-  const int max_segments = (int)((h->st.max_iter + L - 1) / L) + 1;
-  std::vector<int> paused;
-  for (int round = 0; round < 100000; round++) {
-    const unsigned seq = ++c.launch_seq ? c.launch_seq : ++c.launch_seq;       // (never 0: the word's idle value)
-    c.h_done[0] = 0;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    HIPCHK(launch_advance(a, BT, h->ntiles, h->threads, h->lds, h->stream, max_segments, L, c.h_is[0], c.h_ds[0], nullptr, seq, c.counter.p, c.h_done));
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    if ((rc = wait_launch_over(h, seq))) return rc;
-    h->last_launches++; h->kernel_launches++;
-    paused.clear();
-    bool any_active = false;
-    for (int sl = 0; sl < nslots && sl < h->B; sl++) {
-      const int *t = c.h_is[0] + (size_t)(sl / BT) * IS_COUNT * BT;
-      const int b = sl % BT;
-      if (t[IS_NEED_REFACTOR * BT + b] == 1) paused.push_back(sl);      // paused - or finished at max_iter on a rho-update iteration
-      else if (!t[IS_DONE * BT + b]) any_active = true;       // (cannot happen: a tile leaves only done or paused)
-    }
-    bool any_paused = false;
-    for (int sl : paused) any_paused = any_paused || c.h_is[0][(size_t)(sl / BT) * IS_COUNT * BT + IS_PENDING * BT + sl % BT] == 2;
-    if (paused.empty()) { if (any_active) continue; break; }
-    // ---- row E13 for the paused QPs: the grouped refactorisation of short lists, then resume (or isolate: kNonConvex)
-    const double tr = now_s();
-    std::vector<int> bad;
-    if ((rc = device_refactor_slots(h, paused, &bad))) return rc;
-    HIPCHK(launch_resume_flagged(a, nslots, BT, h->stream));
-    for (int sl : bad) h->failed[(size_t)sl] = 1;
-    h->host_rho_stale = true;
-    h->last_refactors += (int64_t)paused.size();
-    h->last_refactor_s += now_s() - tr;
-    if (!any_paused && !any_active) break;        // (only finished QPs were refactored: nothing is left to iterate)
-  }
-  {     // device time of the launches of this solve (events around the last launch; earlier ones through the stream order)
-    HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) { h->last_device_s += ms * 1e-3; h->kernel_ms_sum += ms; }
-  }
-  // the final flags are in the pinned image already
-  memcpy(h->h_iscal, c.h_is[0], (size_t)h->ntiles * IS_COUNT * BT * sizeof(int));
-  for (int qi = 0; qi < h->B; qi++)
-    h->last_total_iters += h->h_iscal[(size_t)(qi / BT) * IS_COUNT * BT + IS_ITER * BT + qi % BT];
-  h->solved_once = true;
-  return MI_OSQP_OK;
-}
-
 static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream) {
   hipStream_t keep = h->stream;
   struct Restore { mi_osqp_batch *h; hipStream_t s; ~Restore() { h->stream = s; } } restore{h, keep};
@@ -1326,25 +1217,16 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
   KernelArgs a = make_args(h);
   if (d_x_out) a.x_out = d_x_out;
   h->last_total_iters = h->last_launches = h->last_refactors = 0;
-  h->last_device_s = h->last_refactor_s = h->last_compact_s = 0.0;
-  const int BT = h->BT, nslots = h->ntiles * BT;
+  h->last_device_s = h->last_refactor_s = 0.0;
+  const int BT = h->BT, ntl = h->ntiles, nslots = ntl * BT;
   const Settings &S = h->st;
-  std::vector<int> qp_of_slot(nslots);
-  for (int s = 0; s < nslots; s++) qp_of_slot[s] = s < h->B ? s : -1;
-  HIPCHK(hipMemcpyAsync(h->qp_of_slot.p, qp_of_slot.data(), nslots * sizeof(int), hipMemcpyHostToDevice, h->stream));
   {     // QPs without a valid factor (isolated earlier) are kNonConvex from the start
     std::vector<int> bad;
     for (int q = 0; q < h->B; q++) if (h->failed[q]) bad.push_back(q);
-    if ((rc = fail_slots(h, a, bad, &qp_of_slot, 0))) return rc;
+    if ((rc = fail_slots(h, a, bad, 0))) return rc;
   }
-  if (small_batch_path(h)) return solve_small(h, a);
-  std::vector<std::vector<int2>> rounds;
-  // compaction (re-pairing the QPs still iterating into fewer tiles) is implemented and tested but OFF by default:
-  // since the value streams are per QP, a finished QP costs no bytes anyway, and moving data only breaks even
-  const bool no_compact = getenv("MI_OSQP_COMPACT") == nullptr || (*h->anp).dt.k != 0;      // (and not combined with the dense tail)
-  if (!no_compact) { const int rc_m = materialise_working(h); if (rc_m) return rc_m; }      // (its slot swaps move working streams)
   auto loop = [&]() -> int {
-    int iter = 0, ntl = h->ntiles;     // tiles [0, ntl) hold every QP that is still iterating
+    int iter = 0;
     while (true) {
       int seg_end = (int)S.max_iter;
       if (S.check_termination > 0) seg_end = std::min<int64_t>(seg_end, (iter / S.check_termination + 1) * S.check_termination);
@@ -1361,10 +1243,9 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
         {
           // The check of more 16-wave tiles than the CUs hold at once (two each) runs in 8-wave workgroups - four per CU, one round
           // instead of two; the check schedule is walked stream by stream by however many waves there are, row by row in the
-          // same order (headline batch: 0.19 -> 0.11 ms per check, 31.8 -> 31.5 ms per step).  MI_OSQP_CHECK_THREADS forces.
+          // same order (headline batch: 0.19 -> 0.11 ms per check, 31.8 -> 31.5 ms per step).
           int chk_threads = h->mw_groups > 0 ? h->mw_threads : h->threads;
           if (h->mw_groups <= 0 && h->threads == 1024 && ntl > 2 * h->n_cus) chk_threads = 512;
-          if (getenv("MI_OSQP_CHECK_THREADS") && h->mw_groups <= 0) chk_threads = std::max(64, std::min(h->threads, atoi(getenv("MI_OSQP_CHECK_THREADS")) / 64 * 64));
           HIPCHK(launch_check(a, BT, ntl, chk_threads, h->lds, h->stream));
         }
         HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)ntl * IS_COUNT * BT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -1382,88 +1263,44 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
       HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
       h->last_device_s += ms * 1e-3; h->kernel_ms_sum += ms; h->kernel_launches++; h->last_launches++;
       iter = seg_end;
-      // slots still iterating / asking for a refactorisation.  A QP that runs into max_iter at a rho-update iteration
+      // QPs still iterating / asking for a refactorisation.  A QP that runs into max_iter at a rho-update iteration
       // has finished AND asks for its refactorisation: upstream adapts rho (and refactors) before it leaves the loop,
       // and the next Solve() of a warm-started solver continues from that factor.
       std::vector<int> active, work;
-      for (int s = 0; s < ntl * BT; s++) {
+      for (int s = 0; s < h->B; s++) {
         const int *t = h->h_iscal + (size_t)(s / BT) * IS_COUNT * BT;
-        if (qp_of_slot[s] < 0) continue;
         if (!t[IS_DONE * BT + s % BT]) active.push_back(s);
         if (t[IS_NEED_REFACTOR * BT + s % BT]) work.push_back(s);
       }
       const int n_ref = (int)work.size();
       if (active.empty() && !n_ref) break;
-      // ---- compaction
-      int target = ((int)active.size() + BT - 1) / BT;
-      bool compacted_now = false;
-      const int ntl_before = ntl;
-      std::vector<int> bad;             // slots whose refactorisation lost the inertia: isolated below
-      if (!no_compact && target < ntl && !active.empty()) {
-        compacted_now = true;
-        double tc = now_s();
-        std::vector<char> is_active(ntl * BT, 0);
-        for (int s : active) is_active[s] = 1;
-        std::vector<int2> pairs;
-        int hole = 0;
-        for (int k = (int)active.size() - 1; k >= 0 && active[k] >= target * BT; k--) {
-          while (hole < target * BT && is_active[hole]) hole++;
-          pairs.push_back(int2{hole, active[k]});
-          std::swap(qp_of_slot[hole], qp_of_slot[active[k]]);
-          is_active[hole] = 1;
-        }
-        int rc2 = apply_swaps(h, pairs);
-        rounds.push_back(std::move(pairs));              // (recorded first: the caller undoes whatever part was applied)
-        if (rc2) return rc2;
-        HIPCHK(hipMemcpyAsync(h->qp_of_slot.p, qp_of_slot.data(), nslots * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        ntl = target;
-        h->last_compact_s += now_s() - tc;
-      }
       // ---- row E13 on the device: rho vector, KKT assembly, block LDL', scatter into the schedules
       if (n_ref) {
         double tr = now_s();
+        std::vector<int> bad;             // QPs whose refactorisation lost the inertia
         int rc2;
-        if (!compacted_now) {
-          // work list: the flagged slots of the whole batch (fewer, fuller tiles = fewer rounds over the CUs)
-          if ((rc2 = device_refactor_slots(h, std::move(work), &bad))) return rc2;
-        } else {
-          // after a compaction of this segment the host copy of the flags is stale: flag-driven sweep over the tiles
-          FactorArgs fa = make_factor_args(h, 0);
-          fa.mw_groups = 0;
-          HIPCHK(launch_factor(fa, BT, ntl_before, factor_threads(), h->stream));
-          HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)ntl_before * IS_COUNT * BT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-          HIPCHK(hipStreamSynchronize(h->stream));
-          for (int s = 0; s < ntl_before * BT; s++)
-            if (qp_of_slot[s] >= 0 && h->h_iscal[(size_t)(s / BT) * IS_COUNT * BT + IS_NEED_REFACTOR * BT + s % BT] < 0) bad.push_back(s);
-        }
+        // work list: the flagged QPs of the whole batch (fewer, fuller tiles = fewer rounds over the CUs)
+        if ((rc2 = device_refactor_slots(h, std::move(work), &bad))) return rc2;
         // a rho update that makes the factor lose its inertia ends THAT QP as kNonConvex ([EXT] osqp_solve: adapt_rho
         // fails -> OSQP_NON_CVX, break); every other QP of the batch goes on
-        if ((rc2 = fail_slots(h, a, bad, &qp_of_slot, iter))) return rc2;
+        if ((rc2 = fail_slots(h, a, bad, iter))) return rc2;
         h->host_rho_stale = true;
         h->last_refactors += n_ref;
         h->last_refactor_s += now_s() - tr;
-      }
-      if (!bad.empty()) {
-        // (with a compaction in this segment `active` holds pre-swap slot numbers: rebuild it from the table)
-        std::vector<char> isbad(nslots, 0);
-        for (int s : bad) isbad[s] = 1;
-        if (compacted_now) { active.clear(); for (int s = 0; s < ntl * BT; s++) if (qp_of_slot[s] >= 0 && !isbad[s]) active.push_back(s); }
-        else active.erase(std::remove_if(active.begin(), active.end(), [&](int s) { return isbad[s] != 0; }), active.end());
+        if (!bad.empty()) {
+          std::vector<char> isbad(nslots, 0);
+          for (int q : bad) isbad[q] = 1;
+          active.erase(std::remove_if(active.begin(), active.end(), [&](int q) { return isbad[q] != 0; }), active.end());
+        }
       }
       if (active.empty()) break;
     }
     return MI_OSQP_OK;
   };
   rc = loop();
-  // ---- undo the compaction (reverse order; swaps are involutions) - also after an error, so that the handle stays usable
-  {
-    double tc = now_s();
-    for (int r = (int)rounds.size() - 1; r >= 0; r--) { int rc2 = apply_swaps(h, rounds[r]); if (rc2 && !rc) rc = rc2; }
-    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
-    HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)nslots * IS_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->last_compact_s += now_s() - tc;
-  }
+  if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+  HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)nslots * IS_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
   for (int qi = 0; qi < h->B; qi++)
     h->last_total_iters += h->h_iscal[(size_t)(qi / BT) * IS_COUNT * BT + IS_ITER * BT + qi % BT];
   h->solved_once = true;
@@ -1535,6 +1372,7 @@ int mi_osqp_prefetch_analysis(int64_t B, int64_t n, int64_t m, const int64_t *Pp
   CallTimer timer_("prefetch_analysis");
   if (B <= 0 || n <= 0 || m < 0 || !Pp || !Ap || (Pp[n] > 0 && !Pi) || (Ap[n] > 0 && !Ai)) return MI_OSQP_ERR_INVALID_DATA;
   mi_osqp_batch tmp;
+  tmp.tune = tuning_from_env();
   int BT = 1, max_extra = -1;
   std::shared_ptr<const Analysis> an;
   return shape_and_analysis(&tmp, B, n, m, Pp, Pi, Ap, Ai, device, BT, max_extra, an);
@@ -1622,8 +1460,8 @@ int mi_osqp_batch_get_ordering(mi_osqp_batch *h, int64_t *kkt_perm) {
 
 int mi_osqp_batch_last_solve_stats(mi_osqp_batch *h, int64_t *total_iters, int64_t *kernel_launches, double *device_seconds,
                                    double *refactor_seconds, int64_t *refactor_count, double *compact_seconds) {
-  if (h && compact_seconds) *compact_seconds = h->last_compact_s;
   if (!h) return MI_OSQP_ERR_NULL;
+  if (compact_seconds) *compact_seconds = 0.0;      // (the QPs are not compacted during a solve; the field stays in the ABI)
   if (total_iters) *total_iters = h->last_total_iters;
   if (kernel_launches) *kernel_launches = h->last_launches;
   if (device_seconds) *device_seconds = h->last_device_s;
@@ -1668,17 +1506,6 @@ int mi_osqp_batch_reset(mi_osqp_batch *h) {
 }
 }  // extern "C"
 // the state right after setup / the last update that refactored: factor, rho vectors and scalars of the snapshot, cold iterates
-// every QP's current factor into the working copy (what the slot swaps of the compaction path move around)
-static int materialise_working(mi_osqp_batch *h) {
-  const Analysis &an = (*h->anp);
-  const int nslots = h->ntiles * h->BT;
-  if (!h->fwd_val0.p || !h->use_work.p) return MI_OSQP_OK;
-  HIPCHK(launch_copy_flagged_streams(h->fwd_val.p, h->fwd_val0.p, h->use_work.p, 0, nslots, (size_t)an.fwd.phys_steps() * 64, h->stream));
-  HIPCHK(launch_copy_flagged_streams(h->bwd_val.p, h->bwd_val0.p, h->use_work.p, 0, nslots, (size_t)an.bwd.phys_steps() * 64, h->stream));
-  if (an.dt.k && h->dt_val0.p) HIPCHK(launch_copy_flagged_streams(h->dt_val.p, h->dt_val0.p, h->use_work.p, 0, nslots, (size_t)an.dt.n_steps * 64, h->stream));
-  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->use_work.p, 1, (size_t)nslots, h->stream));
-  return MI_OSQP_OK;
-}
 static int restore_snapshot(mi_osqp_batch *h) {
   h->clear_rho_updates = true;
   auto cp = [&](DevBuf<double> &dst, DevBuf<double> &src) -> int {
@@ -1687,14 +1514,8 @@ static int restore_snapshot(mi_osqp_batch *h) {
   };
   int rc;
   const size_t nflags = (size_t)h->ntiles * h->BT;
-  if (getenv("MI_OSQP_RESET_COPIES")) {
-    // (experiments: everything back into the working copy, as before round 3)
-    if ((rc = cp(h->fwd_val, h->fwd_val0)) || (rc = cp(h->bwd_val, h->bwd_val0)) || (rc = cp(h->dt_val, h->dt_val0))) return rc;
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->use_work.p, 1, nflags, h->stream));
-  } else {
-    // every QP's factor is its snapshot again: one word per QP instead of 1 GB of stream copies at the headline batch
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->use_work.p, 0, nflags, h->stream));
-  }
+  // every QP's factor is its snapshot again: one word per QP instead of 1 GB of stream copies at the headline batch
+  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->use_work.p, 0, nflags, h->stream));
   if ((rc = cp(h->dinv, h->dinv0)) || (rc = cp(h->rho_vec, h->rho_vec0)) || (rc = cp(h->rho_inv, h->rho_inv0)) || (rc = cp(h->dscal, h->dscal0))) return rc;
   if ((rc = reset_solve_state(h, true))) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1901,8 +1722,7 @@ static int device_update(mi_osqp_batch *h, const double *Av, const double *l, co
 // update), wrong for a handful of large QPs (one QP of 48 k entries: 5 ms on a host thread, 14 ms in one workgroup).
 // MI_OSQP_HOST_RUIZ=1 / MI_OSQP_DEVICE_RUIZ=1 force one or the other (same bits either way).
 static bool host_ruiz(const mi_osqp_batch *h) {
-  if (getenv("MI_OSQP_HOST_RUIZ")) return true;
-  if (getenv("MI_OSQP_DEVICE_RUIZ")) return false;
+  if (h->tune.ruiz) return h->tune.ruiz > 0;
   const Analysis &an = (*h->anp);
   const long per_qp = (long)an.Pp[an.n] + an.Ap[an.n] + an.n + an.m;
   return h->B < 16 || per_qp > 65536;
@@ -2029,10 +1849,10 @@ int mi_osqp_batch_spmv(mi_osqp_batch *h, const double *d_x, const double *d_y, d
   DevGuard guard(h->device);
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   KernelArgs a = make_args(h);
-  if (h->sp_ptr.n && !getenv("MI_OSQP_SPMV_STREAM")) {      // one read of P and A for all three products
+  if (h->sp_ptr.n) {      // one read of P and A for all three products
     SpmvFused t{};
     t.ptr = h->sp_ptr.p; t.ent = h->sp_ent.p; t.pa_val = h->pa_val.p; t.pa_len = (*h->anp).Pp[(*h->anp).n] + (*h->anp).Ap[(*h->anp).n];
-    if (h->sp_npass && !getenv("MI_OSQP_SPMV_NO_PREFETCH")) {
+    if (h->sp_npass) {
       t.ell = h->sp_ell.p; t.rowid = h->sp_rowid.p; t.n_pass = h->sp_npass;
       for (int p = 0; p < 4; p++) { t.ell_off[p] = h->sp_ell_off[p]; t.ell_k[p] = h->sp_ell_k[p]; }
     }
@@ -2123,20 +1943,6 @@ static int ensure_advance_buffers(mi_osqp_batch *h) {
   if (!c.h_done) { HIPCHK(hostpool::alloc((void **)&c.h_done, 64, &c.h_done_cap)); c.h_done[0] = c.h_done[1] = 0; }
   return MI_OSQP_OK;
 }
-// wait for the completion word of launch `seq` (no runtime call in the way); fallback: the stream
-static int wait_launch_over(mi_osqp_batch *h, unsigned seq) {
-  mi_osqp_batch::Cont &c = h->cont;
-  auto over = [&]() { return __atomic_load_n(c.h_done, __ATOMIC_ACQUIRE) == seq; };
-  const double t0 = now_s();
-  for (int spin = 0; !over(); spin++) {
-    if (spin < 20000) { __builtin_ia32_pause(); continue; }
-    struct timespec ts{0, 20000};
-    nanosleep(&ts, nullptr);
-    if ((spin & 1023) == 0 && now_s() - t0 > 5.0) { HIPCHK(hipStreamSynchronize(h->stream)); if (!over()) { g_last_error = "advance launch ended without reporting"; return MI_OSQP_ERR_DEVICE; } }
-  }
-  return MI_OSQP_OK;
-}
-
 static int cont_enter(mi_osqp_batch *h) {
   mi_osqp_batch::Cont &c = h->cont;
   if (c.on) return MI_OSQP_OK;
@@ -2160,7 +1966,7 @@ static int cont_enter(mi_osqp_batch *h) {
     const size_t per_qp = ((size_t)an.Ap[n] + (size_t)an.Pp[n] + 2 * (size_t)m + (size_t)n + 16) * sizeof(double);      // (a whole call - ids, rows in, scaled values out - fits one lap)
     size_t want = std::max<size_t>((size_t)4 << 20, std::min<size_t>((size_t)256 << 20, 2 * per_qp * (size_t)B));
     // (tests: MI_OSQP_CONT_RING_KB = a ring barely larger than one whole-batch call, so that every few calls wrap)
-    if (const char *er = getenv("MI_OSQP_CONT_RING_KB")) want = std::max<size_t>((size_t)atol(er) << 10, per_qp * (size_t)B + ((size_t)64 << 10));
+    if (h->tune.cont_ring_kb >= 0) want = std::max<size_t>((size_t)h->tune.cont_ring_kb << 10, per_qp * (size_t)B + ((size_t)64 << 10));
     HIPCHK(hostpool::alloc((void **)&c.ring_h, want, &c.ring_h_cap));
     c.ring_cap = c.ring_h_cap;
     int rc = c.ring_d.alloc(c.ring_cap);
@@ -2169,20 +1975,15 @@ static int cont_enter(mi_osqp_batch *h) {
   }
   int rc;
   if (c.work.n < (size_t)nslots + 4 && (rc = c.work.alloc((size_t)nslots + 4))) return rc;
-  if (!c.ustream) {
-    // By default the preparation and the refactorisations share the handle's stream with the advance launches (in order):
-    // measured on the GOMP obstacle scene (ten handles driven by ten host threads) a second stream per handle LOSES - 20
-    // streams on the runtime's 4-10 hardware queues wait for each other's kernels (900 against 620 trajectories/s,
-    // profiles/r03).  MI_OSQP_CONT_STREAMS=2 gives every handle its second stream; the protocol is the same either way.
-    { const char *e = getenv("MI_OSQP_CONT_STREAMS"); c.own_ustream = e && atoi(e) == 2; }
-    if (c.own_ustream) HIPCHK(hipStreamCreateWithFlags(&c.ustream, hipStreamNonBlocking));
-    else c.ustream = h->stream;
+  if (!c.ev_adv) {
+    // The preparation and the refactorisations share the handle's stream with the advance launches (in order): measured on
+    // the GOMP obstacle scene (ten handles driven by ten host threads) a second stream per handle LOSES - 20 streams on the
+    // runtime's 4-10 hardware queues wait for each other's kernels (900 against 620 trajectories/s, profiles/r03).
     HIPCHK(hipEventCreateWithFlags(&c.ev_adv, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c.ev_u, hipEventDisableTiming));
     if ((rc = c.rz_scratch.alloc((size_t)B * (n + m) + 1))) return rc;
   }
   if ((rc = c.counter.zero(h->stream))) return rc;
-  c.h_done[0] = c.h_done[1] = 0; c.last_active = 0;
+  c.h_done[0] = c.h_done[1] = 0;
   // the state of the last blocking solve, if any, stays valid; every slot is idle until its solve is begun
   HIPCHK(hipMemcpy(h->h_iscal, h->iscal.p, icnt * sizeof(int), hipMemcpyDeviceToHost));
   for (int t = 0; t < h->ntiles; t++)
@@ -2197,9 +1998,6 @@ static int cont_enter(mi_osqp_batch *h) {
   memcpy(c.h_is[0], h->h_iscal, icnt * sizeof(int)); memcpy(c.h_is[1], h->h_iscal, icnt * sizeof(int));      // the host images advance_kernel writes
   if (!c.stop.p && (rc = c.stop.alloc(4))) return rc;
   if ((rc = c.stop.zero(h->stream))) return rc;
-  std::vector<int> ident((size_t)nslots);
-  for (int sl = 0; sl < nslots; sl++) ident[sl] = sl < B ? sl : -1;
-  HIPCHK(hipMemcpyAsync(h->qp_of_slot.p, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   c.on = true;
   return MI_OSQP_OK;
@@ -2209,7 +2007,6 @@ static int cont_enter(mi_osqp_batch *h) {
 static int cont_leave(mi_osqp_batch *h) {
   mi_osqp_batch::Cont &c = h->cont;
   if (!c.on) return MI_OSQP_OK;
-  if (c.ustream) HIPCHK(hipStreamSynchronize(c.ustream));
   HIPCHK(hipStreamSynchronize(h->stream));
   const size_t icnt = (size_t)h->ntiles * IS_COUNT * h->BT;
   HIPCHK(hipMemcpy(h->h_iscal, h->iscal.p, icnt * sizeof(int), hipMemcpyDeviceToHost));
@@ -2231,7 +2028,7 @@ static int ring_take(mi_osqp_batch *h, size_t bytes, RingSpan &out) {
   mi_osqp_batch::Cont &c = h->cont;
   bytes = (bytes + 255) & ~(size_t)255;
   if (bytes > c.ring_cap) { g_last_error = "per-QP call larger than the staging ring"; return MI_OSQP_ERR_ALLOC; }
-  if (c.ring_head + bytes > c.ring_cap) { HIPCHK(hipStreamSynchronize(c.ustream)); HIPCHK(hipStreamSynchronize(h->stream)); c.ring_head = 0; }      // everything handed out so far has been consumed
+  if (c.ring_head + bytes > c.ring_cap) { HIPCHK(hipStreamSynchronize(h->stream)); c.ring_head = 0; }      // everything handed out so far has been consumed
   out.host = c.ring_h + c.ring_head; out.dev = c.ring_d.p + c.ring_head;
   c.ring_head += bytes;
   return MI_OSQP_OK;
@@ -2245,11 +2042,11 @@ static int ring_reserve(mi_osqp_batch *h, size_t bytes, int spans) {
   mi_osqp_batch::Cont &c = h->cont;
   bytes += (size_t)256 * (size_t)spans;
   if (bytes > c.ring_cap) { g_last_error = "per-QP call larger than the staging ring"; return MI_OSQP_ERR_ALLOC; }
-  if (c.ring_head + bytes > c.ring_cap) { HIPCHK(hipStreamSynchronize(c.ustream)); HIPCHK(hipStreamSynchronize(h->stream)); c.ring_head = 0; }
+  if (c.ring_head + bytes > c.ring_cap) { HIPCHK(hipStreamSynchronize(h->stream)); c.ring_head = 0; }
   return MI_OSQP_OK;
 }
 static int ring_upload(mi_osqp_batch *h, const RingSpan &sp, size_t bytes) {
-  if (bytes) HIPCHK(hipMemcpyAsync(sp.dev, sp.host, bytes, hipMemcpyHostToDevice, h->cont.ustream));
+  if (bytes) HIPCHK(hipMemcpyAsync(sp.dev, sp.host, bytes, hipMemcpyHostToDevice, h->stream));
   return MI_OSQP_OK;
 }
 
@@ -2299,10 +2096,10 @@ static int snapshot_some(mi_osqp_batch *h, const int *d_ids, int nq, hipStream_t
 static int enqueue_refactor_list(mi_osqp_batch *h, const int *d_work, int count) {
   if (count <= 0) return MI_OSQP_OK;
   const Analysis &an = (*h->anp);
-  hipStream_t st = h->cont.ustream;         // (every refactorisation of the continuous mode: one stream, one scratch)
+  hipStream_t st = h->stream;
   FactorArgs fa = make_factor_args(h, 0);
   fa.work = d_work; fa.mw_groups = 0;
-  HIPCHK(launch_factor(fa, 1, count, factor_threads(), st));
+  HIPCHK(launch_factor(fa, 1, count, h->tune.factor_threads, st));
   if (an.dt.k) {
     const DenseTail &dt = an.dt;
     TailArgs da{};
@@ -2340,7 +2137,7 @@ static int cont_new_data(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, co
     memcpy(hin, Av, cA * sizeof(double)); memcpy(hin + cA, l, cb * sizeof(double)); memcpy(hin + cA + cb, u, cb * sizeof(double));
     if ((rc = ring_upload(h, in, (cA + 2 * cb) * sizeof(double)))) return rc;
   }
-  hipStream_t us = h->cont.ustream;
+  hipStream_t us = h->stream;
   if (!dA && h->cont.keepA) {
     HIPCHK(launch_keep_rows(h->cont.keepA, din, d_ids, nq, nnzA, us));
     HIPCHK(launch_keep_rows(h->cont.keepl, din + cA, d_ids, nq, m, us));
@@ -2406,7 +2203,7 @@ int mi_osqp_batch_warm_start_x_some(mi_osqp_batch *h, int64_t n_ids, const int64
   if ((rc = ring_upload(h, sp, cnt * sizeof(double)))) return rc;
   KernelArgs a = make_args(h);
   a.sel = d_sel;
-  HIPCHK(launch_warm_start(a, h->BT, h->ntiles, h->threads, h->lds, h->cont.ustream, (const double *)sp.dev));
+  HIPCHK(launch_warm_start(a, h->BT, h->ntiles, h->threads, h->lds, h->stream, (const double *)sp.dev));
   return MI_OSQP_OK;
 }
 
@@ -2430,7 +2227,7 @@ int mi_osqp_batch_solve_begin_some(mi_osqp_batch *h, int64_t n_ids, const int64_
   KernelArgs a = make_args(h);
   a.x_out = c.xh; a.y_out = c.yh;
   // (a QP whose last refactorisation lost the inertia carries flag -1 on the device: start_slots_kernel ends it as kNonConvex)
-  HIPCHK(launch_start_slots(a, (const int *)sp.dev, (const int *)sp.dev + n_ids, (int)n_ids, h->BT, h->st.warm_start ? 0 : 1, c.ustream));
+  HIPCHK(launch_start_slots(a, (const int *)sp.dev, (const int *)sp.dev + n_ids, (int)n_ids, h->BT, h->st.warm_start ? 0 : 1, h->stream));
   for (int64_t j = 0; j < n_ids; j++) {
     const size_t q = (size_t)ids[j];
     if (!c.running[q]) { c.running[q] = 1; c.n_running++; }
@@ -2455,13 +2252,6 @@ int mi_osqp_batch_advance(mi_osqp_batch *h, int64_t n_segments) {
   // solutions of finished QPs in pinned host memory; with several segments the launch ends early for everybody once a QP
   // has finished (the caller wants to react to it), and for a tile whose QP asks for a refactorisation
   a.info_at_end = 1;
-  // Nothing orders the two streams - unless the last launch found nothing to iterate: then whatever is running waits for
-  // its preparation / refactorisation on the second stream, and launching again at once would only spin.  Such a launch
-  // waits for the second stream's queue.
-  if (c.last_active == 0) {
-    HIPCHK(hipEventRecord(c.ev_u, c.ustream));
-    HIPCHK(hipStreamWaitEvent(h->stream, c.ev_u, 0));
-  }
   c.launch_seq++;
   const int par = (int)(c.adv_seq & 1);
   HIPCHK(launch_advance(a, BT, h->ntiles, h->threads, h->lds, h->stream, (int)std::min<int64_t>(n_segments, 1 << 20), c.L, c.h_is[par], c.h_ds[par],
@@ -2470,10 +2260,9 @@ int mi_osqp_batch_advance(mi_osqp_batch *h, int64_t n_segments) {
   if (h->st.adaptive_rho) {
     // row E13 without the host, next to the following launches: the QPs this launch paused (their rho changed) are listed on
     // the device, refactored and marked to resume - or ended as kNonConvex when the new factor lost its inertia
-    HIPCHK(hipStreamWaitEvent(c.ustream, c.ev[par], 0));
-    HIPCHK(launch_worklist(h->iscal.p, c.work.p, nslots, BT, c.ustream));
+    HIPCHK(launch_worklist(h->iscal.p, c.work.p, nslots, BT, h->stream));
     if ((rc = enqueue_refactor_list(h, c.work.p, nslots))) return rc;
-    HIPCHK(launch_resume_flagged(a, nslots, BT, c.ustream));
+    HIPCHK(launch_resume_flagged(a, nslots, BT, h->stream));
   }
   c.adv_seq++;
   c.seq_of[par] = c.adv_seq;
@@ -2503,7 +2292,6 @@ int mi_osqp_batch_poll(mi_osqp_batch *h, int64_t wait, int64_t *n_finished, int6
       if ((spin & 1023) == 0 && now_s() - t0 > 5.0) { HIPCHK(hipEventSynchronize(c.ev[par])); if (!over()) { g_last_error = "advance launch ended without reporting"; return MI_OSQP_ERR_DEVICE; } }
     }
   }
-  c.last_active = c.h_done[1];
   const int BT = h->BT;
   int64_t nf = 0;
   auto finished = [&](int q) {
@@ -2598,7 +2386,7 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
   if ((rc = cont_stage_ids(h, n_ids, ids, &d_ids, nullptr)) || (rc = ring_take(h, (size_t)nq * n * sizeof(double), sp))) return rc;
   memcpy(sp.host, x, (size_t)nq * n * sizeof(double));
   if ((rc = ring_upload(h, sp, (size_t)nq * n * sizeof(double)))) return rc;
-  hipStream_t st = h->cont.ustream;
+  hipStream_t st = h->stream;
   GompArgs g{};
   g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
   g.row0 = sc->row0; g.write_rows = write_rows;
@@ -2678,7 +2466,6 @@ void mi_gomp_scene_free(mi_gomp_scene *sc) {
   if (!sc) return;
   DevGuard guard(sc->h->device);
   (void)hipStreamSynchronize(sc->h->stream);
-  if (sc->h->cont.ustream) (void)hipStreamSynchronize(sc->h->cont.ustream);
   if (sc->h->cont.keepA == sc->A.p) sc->h->cont.keepA = sc->h->cont.keepl = sc->h->cont.keepu = nullptr;
   delete sc;
 }
@@ -2690,7 +2477,7 @@ int mi_gomp_scene_set_rows(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids,
   DevGuard guard(h->device);
   const Analysis &an = (*h->anp);
   const size_t nnzA = (size_t)an.Ap[an.n], m = (size_t)an.m;
-  hipStream_t st = h->cont.on && h->cont.ustream ? h->cont.ustream : h->stream;
+  hipStream_t st = h->stream;
   for (int64_t j = 0; j < n_ids; j++) {
     if (ids[j] < 0 || ids[j] >= h->B) return MI_OSQP_ERR_INVALID_DATA;
     HIPCHK(hipMemcpyAsync(sc->A.p + (size_t)ids[j] * nnzA, Av + (size_t)j * nnzA, nnzA * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2979,7 +2766,8 @@ int mi_osqp_debug_host_kkt_solve(int64_t n, int64_t m, const int64_t *Pp, const 
   if (validate_settings(s)) return MI_OSQP_ERR_INVALID_SETTINGS;
   Analysis an;
   // tile > 1: the dataflow form for tile - 1 workgroups per QP (global solve vector, no dense tail)
-  int rc = tile > 1 ? analyze(n, m, Pp, Pi, Ap, Ai, an, 8, 1, -1, 0, (int)tile - 1) : analyze(n, m, Pp, Pi, Ap, Ai, an);
+  const AnalysisTuning tune = tuning_from_env().analysis;
+  int rc = tile > 1 ? analyze(n, m, Pp, Pi, Ap, Ai, tune, an, 8, 1, -1, 0, (int)tile - 1) : analyze(n, m, Pp, Pi, Ap, Ai, tune, an);
   if (rc) return rc;
   QPNumeric Q;
   load_qp(an, s, Pv, nullptr, Av, l, u, Q);
@@ -3011,7 +2799,7 @@ int mi_osqp_debug_host_block_factor(int64_t n, int64_t m, const int64_t *Pp, con
   Settings s = to_settings(settings);
   if (validate_settings(s)) return MI_OSQP_ERR_INVALID_SETTINGS;
   Analysis an;
-  int rc = analyze(n, m, Pp, Pi, Ap, Ai, an);
+  int rc = analyze(n, m, Pp, Pi, Ap, Ai, tuning_from_env().analysis, an);
   if (rc) return rc;
   QPNumeric Q, R;
   load_qp(an, s, Pv, nullptr, Av, l, u, Q);

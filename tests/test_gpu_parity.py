@@ -349,10 +349,9 @@ def test_device_refactor_matches_host_factor(tile, monkeypatch):
         _compare(info, s.primal(), _oracle_batch(pr, range(B)), range(B))
 
 
-def test_compaction_path_gives_identical_results(monkeypatch):
-    """MI_OSQP_COMPACT=1 packs the QPs still iterating into the leading tiles between
-    segments (slot swaps on the device, undone afterwards): results must be bitwise
-    identical to the plain path, and a following solve must still work."""
+def test_four_qps_per_tile_give_the_results_of_the_default_tiling(monkeypatch):
+    """MI_OSQP_TILE=4 packs four QPs into every tile: the same iteration counts and the same solution up to round-off as
+    the default tiling, and a tile-4 solver - its solve, a bounds update and the solve after it - is reproducible."""
     pr = PR.random_box_qp(24, n=96, mg=64, nnz_per_row=6)
     def run():
         s = M.BatchSolver(pr["P"], pr["Px"], pr["q"], pr["A"], pr["Ax"], pr["l"], pr["u"])
@@ -361,17 +360,13 @@ def test_compaction_path_gives_identical_results(monkeypatch):
         i2 = s.solve(); x2 = s.primal().copy()
         return [i.iter for i in i1], x1, y1, [i.iter for i in i2], x2, s.last_solve_stats()
     a = run()
-    monkeypatch.setenv("MI_OSQP_COMPACT", "1")
     monkeypatch.setenv("MI_OSQP_TILE", "4")
     b = run()
-    monkeypatch.delenv("MI_OSQP_COMPACT")
     c = run()
     assert b[0] == c[0] and b[3] == c[3]
-    # round-off only: the two paths may refactor with different numbers of QPs per workgroup (the packed work list
-    # vs. the flag-driven sweep over the compacted tiles), which changes the order of the partial sums
     for k in (1, 2, 4):
         assert np.max(np.abs(b[k] - c[k])) <= 1e-12
-    assert a[0] == b[0] and np.max(np.abs(a[1] - b[1])) <= 1e-9      # tile 2 vs tile 4: same algorithm, round-off only
+    assert a[0] == b[0] and np.max(np.abs(a[1] - b[1])) <= 1e-9      # default tiling vs tile 4: same algorithm, round-off only
 
 
 def test_config4_full_size_gomp_batch():
