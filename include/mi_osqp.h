@@ -75,6 +75,12 @@ typedef struct {
   int64_t check_termination;      /* 25   */
   int64_t warm_start;             /* 1    */
   int64_t verbose;                /* 0 here; the reference passes 1 (log only) */
+  /* solution polishing (OSQP polish.c, README "Polishing"): after every blocking solve, each QP that ended kOptimal solves
+   * the reduced KKT system of the active set guessed from its final iterate and keeps the result when its residuals are
+   * smaller.  Not available in the continuous mode: mi_osqp_batch_solve_begin_some refuses a handle with polish = 1. */
+  int64_t polish;                 /* 0    */
+  int64_t polish_refine_iter;     /* 3    (>= 0) */
+  double  delta;                  /* 1e-6 (> 0): regularisation of the reduced KKT matrix */
 } mi_osqp_settings;
 
 typedef struct {
@@ -87,6 +93,8 @@ typedef struct {
   int64_t rho_updates;
   double  rho_estimate;
   double  rho;
+  int64_t status_polish;  /* 1 polished solution accepted, -1 polishing failed / not better, 0 not polished (polish off, or
+                           * the QP did not end kOptimal) */
 } mi_osqp_info;
 
 /* analysis / schedule statistics (DESIGN.md quotes these) */
@@ -208,6 +216,12 @@ int mi_osqp_batch_reset(mi_osqp_batch *h);
 int mi_osqp_batch_last_solve_stats(mi_osqp_batch *h, int64_t *total_iters, int64_t *kernel_launches,
                                    double *device_seconds, double *refactor_seconds, int64_t *refactor_count,
                                    double *compact_seconds);
+/* Polishing of the last solve: QPs polished (those that ended kOptimal), QPs whose polished solution was accepted, and the
+ * seconds the polish took on the device (HIP events: active set, polish factor, polish kernel).  Zeros without polish. */
+int mi_osqp_batch_last_polish_stats(mi_osqp_batch *h, int64_t *polished, int64_t *accepted, double *seconds);
+/* (tests) the active set of the last polish, act[B][m]: -1 lower-active, +1 upper-active, 0 inactive (all 0 for QPs that
+ * were not polished, and before the first polish). */
+int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act);
 
 /* ------------------------------------------------------ continuous batching
  * The reference's SQP loop is per trajectory: solve -> check -> re-linearise -> update -> solve again
@@ -244,7 +258,7 @@ int mi_osqp_batch_reinit_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *id
 int mi_osqp_batch_update_A_bounds_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids,
                                        const double *A_val, const double *l, const double *u);
 int mi_osqp_batch_warm_start_x_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *x /*[n_ids][n]*/);
-int mi_osqp_batch_solve_begin_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids);
+int mi_osqp_batch_solve_begin_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids);   /* polish = 1: MI_OSQP_ERR_INVALID_SETTINGS */
 int mi_osqp_batch_advance(mi_osqp_batch *h, int64_t n_segments);
 /* wait != 0: block until the oldest unpolled advance has run; wait == 0: *n_finished = -1 when it has not.  ids_out receives
  * the QPs that finished in it (capacity >= B is always enough; too small: error, *n_finished = the number, nothing consumed). */

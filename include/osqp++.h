@@ -14,11 +14,12 @@
 //   absl::Status::ok / ToString                                                                               [REF] :30,34-48
 //   osqp::OsqpExitCode, osqp::ToString                                                                        [REF] utils.h:11; gomp-solver.h:40,46-49,68,72,79
 // plus dual_solution / iterations / objective_value / IsInitialized.  Entry points of osqp-cpp that the C-ABI has no
-// counterpart for (SetObjectiveVector, UpdateObjectiveMatrix, SetDualWarmStart, polishing) return kUnimplemented.
+// counterpart for (SetObjectiveVector, UpdateObjectiveMatrix, SetDualWarmStart) return kUnimplemented.
 //
-// Settings that the MI355X core does not implement are validated like upstream and otherwise ignored: polish (the
-// reference leaves it off), time_limit, delta, adaptive_rho_fraction (the wall-clock rule; the deterministic interval
-// 4 * check_termination stands in for "auto").
+// polish, polish_refine_iter and delta map onto the core's solution polishing (mi_osqp_settings, README "Polishing").
+// Settings that the MI355X core does not implement are validated like upstream and otherwise ignored: time_limit,
+// adaptive_rho_fraction (the wall-clock rule; the deterministic interval 4 * check_termination stands in for "auto",
+// DESIGN.md section 2).
 #ifndef MI_OSQP_OSQPPP_SHIM_H_
 #define MI_OSQP_OSQPPP_SHIM_H_
 
@@ -133,7 +134,6 @@ class OsqpSolver {
     if (instance.objective_matrix.rows() != n || instance.objective_matrix.cols() != n ||
         instance.constraint_matrix.rows() != m || instance.constraint_matrix.cols() != n || instance.upper_bounds.size() != m)
       return MI_OSQP_SHIM_STATUS(kInvalidArgument, "The dimensions of the objective / constraint data do not agree");
-    if (settings.polish) return MI_OSQP_SHIM_STATUS(kUnimplemented, "polish is not available in the MI355X core");
     Eigen::SparseMatrix<double, Eigen::ColMajor, c_int> P = instance.objective_matrix, A = instance.constraint_matrix;
     P.makeCompressed(); A.makeCompressed();
     mi_osqp_settings s;
@@ -144,6 +144,7 @@ class OsqpSolver {
     s.eps_prim_inf = settings.eps_prim_inf; s.eps_dual_inf = settings.eps_dual_inf; s.alpha = settings.alpha;
     s.scaled_termination = settings.scaled_termination; s.check_termination = settings.check_termination;
     s.warm_start = settings.warm_start; s.verbose = settings.verbose;
+    s.polish = settings.polish ? 1 : 0; s.polish_refine_iter = settings.polish_refine_iter; s.delta = settings.delta;
     static_assert(sizeof(c_int) == sizeof(int64_t), "CSC index width");
     const int rc = mi_osqp_setup(&h_, n, m, reinterpret_cast<const int64_t *>(P.outerIndexPtr()),
                                  reinterpret_cast<const int64_t *>(P.innerIndexPtr()), P.valuePtr(), instance.objective_vector.data(),

@@ -37,13 +37,18 @@ class Settings(C.Structure):
                 ("adaptive_rho_tolerance", C.c_double), ("max_iter", C.c_int64),
                 ("eps_abs", C.c_double), ("eps_rel", C.c_double), ("eps_prim_inf", C.c_double),
                 ("eps_dual_inf", C.c_double), ("alpha", C.c_double), ("scaled_termination", C.c_int64),
-                ("check_termination", C.c_int64), ("warm_start", C.c_int64), ("verbose", C.c_int64)]
+                ("check_termination", C.c_int64), ("warm_start", C.c_int64), ("verbose", C.c_int64),
+                ("polish", C.c_int64), ("polish_refine_iter", C.c_int64), ("delta", C.c_double)]
 
 
 class Info(C.Structure):
     _fields_ = [("iter", C.c_int64), ("status_val", C.c_int64), ("exit_code", C.c_int64),
                 ("obj_val", C.c_double), ("pri_res", C.c_double), ("dua_res", C.c_double),
-                ("rho_updates", C.c_int64), ("rho_estimate", C.c_double), ("rho", C.c_double)]
+                ("rho_updates", C.c_int64), ("rho_estimate", C.c_double), ("rho", C.c_double),
+                ("status_polish", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -105,6 +110,8 @@ def lib():
         L.mi_osqp_batch_reset.argtypes = [vp]
         L.mi_osqp_batch_refactor_device.argtypes = [vp]
         L.mi_osqp_batch_last_solve_stats.argtypes = [vp, ip, ip, dp, dp, ip, dp]
+        L.mi_osqp_batch_last_polish_stats.argtypes = [vp, ip, ip, dp]
+        L.mi_osqp_batch_get_polish_active.argtypes = [vp, C.POINTER(C.c_int8)]
         L.mi_osqp_batch_spmv.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.mi_osqp_batch_kkt_solve.argtypes = [vp, vp, vp, vp]
         L.mi_osqp_batch_kernel_time.argtypes = [vp, dp, ip]
@@ -315,6 +322,18 @@ class BatchSolver:
                                                   C.byref(cs)), "stats")
         return dict(total_iters=it.value, launches=ln.value, device_s=ds.value, refactor_s=rs.value, refactors=rc.value,
                     compact_s=cs.value)
+
+    def last_polish_stats(self):
+        """Polishing of the last solve: QPs polished, QPs whose polished solution was accepted, device seconds."""
+        pol, acc, sec = C.c_int64(), C.c_int64(), C.c_double()
+        _chk(lib().mi_osqp_batch_last_polish_stats(self._h, C.byref(pol), C.byref(acc), C.byref(sec)), "last_polish_stats")
+        return dict(polished=pol.value, accepted=acc.value, seconds=sec.value)
+
+    def polish_active(self):
+        """Active set of the last polish, int8 [B, m]: -1 lower-active, +1 upper-active, 0 inactive / not polished."""
+        act = np.zeros((self.B, self.m), dtype=np.int8)
+        _chk(lib().mi_osqp_batch_get_polish_active(self._h, act.ctypes.data_as(C.POINTER(C.c_int8))), "get_polish_active")
+        return act
 
     def kernel_time(self):
         ms, cnt = C.c_double(), C.c_int64()

@@ -99,6 +99,13 @@ struct FactorArgs {
   // the ONE QP of a handle shared by mw_groups workgroups (single large QPs; grid barriers between the phases of a level)
   int mw_groups;
   unsigned *mw_bar;
+  // polish mode (pmask non-null): the reduced KKT matrix [[P + sigma I, A~'], [A~, -pdelta I]] (sigma = the polish delta;
+  // A~ = A with the entries of the rows pmask marks inactive set to zero) into the polish streams; the rho vectors and
+  // iscal stay untouched, a factor with the wrong inertia sets pstat[slot] = -1
+  const signed char *pmask;  // [slot][m]: -1 / +1 active, 0 inactive
+  const int32_t *arow;       // row of every entry of A (CSC order)
+  int *pstat;
+  double pdelta;
 };
 
 // dense tail: assembly of the Schur complement + its inversion (tail_kernel; one workgroup per refactored QP, after
@@ -120,8 +127,22 @@ struct TailArgs {
   double *Sd, *dt_val, *dinv;
   int *npos, *iscal;
   unsigned long long *trace;    // null, or 8 clock sums per workgroup (MI_OSQP_TAIL_TRACE)
+  int *pstat;                   // polish factor (FactorArgs::pmask): the wrong inertia sets pstat[slot] = -1 instead of the iscal flag
 };
 hipError_t launch_tail(const TailArgs &a, int nwork, size_t lds_asm, size_t lds, hipStream_t st);
+
+// solution polishing (OSQP polish.c on the scaled data; solver.hip "polish")
+struct PolishArgs {
+  int *stat;                    // [slot]: 1 = polish this QP (kOptimal; a polish factor with the wrong inertia has set -1), 0 = not;
+                                // polish_kernel leaves 1 = accepted, -1 = rejected
+  signed char *act;             // [slot][m]: -1 lower-active, +1 upper-active, 0 inactive (polish_active_kernel)
+  double *sol;                  // [tile][N][BT]: the refinement iterate [x; y_red] in natural order
+  int refine_iter;
+};
+// active set of every kOptimal QP from its final iterate, stat = 1 for those QPs, 0 for the others
+hipError_t launch_polish_active(const KernelArgs &a, const PolishArgs &p, int BT, hipStream_t st);
+// a = the handle's arguments with the polish factor's streams / dinv / dense-tail stream (use_work null)
+hipError_t launch_polish(const KernelArgs &a, const PolishArgs &p, int BT, int tiles, int threads, size_t lds, int n_cus, hipStream_t st);
 hipError_t launch_factor(const FactorArgs &a, int BT, int tiles, int threads, hipStream_t st);
 size_t factor_lds_bytes(int BT, int threads);
 bool factor_fits_lds(const FactorArgs &a, int threads);      // the LDS-resident form of factor_kernel<1> applies (one QP per workgroup, no group sharing)

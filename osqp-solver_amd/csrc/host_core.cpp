@@ -26,6 +26,7 @@ int validate_settings(const Settings &s) {
   if (!(s.eps_prim_inf > 0.0) || !(s.eps_dual_inf > 0.0)) return 1;
   if (!(s.alpha > 0.0) || !(s.alpha < 2.0)) return 1;
   if ((s.scaled_termination | 1) != 1 || (s.warm_start | 1) != 1) return 1;
+  if ((s.polish | 1) != 1 || s.polish_refine_iter < 0 || !(s.delta > 0.0)) return 1;
   return 0;
 }
 

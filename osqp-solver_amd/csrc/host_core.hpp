@@ -28,6 +28,8 @@ struct Settings {
   int64_t max_iter = 4000;
   double eps_abs = 1e-3, eps_rel = 1e-3, eps_prim_inf = 1e-4, eps_dual_inf = 1e-4, alpha = 1.6;
   int64_t scaled_termination = 0, check_termination = 25, warm_start = 1, verbose = 0;
+  int64_t polish = 0, polish_refine_iter = 3;
+  double delta = 1e-6;
 };
 int validate_settings(const Settings &s);   // 0 ok
 

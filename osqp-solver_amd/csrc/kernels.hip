@@ -1511,6 +1511,174 @@ __global__ __launch_bounds__(NT) void kkt_solve_kernel(KernelArgs a, const doubl
   }
 }
 
+// ---- solution polishing (OSQP polish.c on the scaled data; solver.hip "polish") ----------------------------------------
+// Before the polish factor: the active set of every kOptimal QP from its final iterate (z, y):
+//   lower-active  z_j - l_j < -y_j,   upper-active  u_j - z_j < y_j   (l <= u: never both)
+// one thread per (QP, row); the thread of row m marks the QP as one to polish.
+__global__ void polish_active_kernel(KernelArgs a, PolishArgs pa, int BT) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x, per = (size_t)a.m + 1;
+  if (g >= (size_t)a.B * per) return;
+  const int slot = (int)(g / per), j = (int)(g % per), m = a.m;
+  const size_t t = (size_t)slot / BT, b = (size_t)slot % BT;
+  const bool cand = a.iscal[(t * IS_COUNT + IS_STATUS) * BT + b] == 1;
+  if (j == m) { pa.stat[slot] = cand ? 1 : 0; return; }
+  signed char s = 0;
+  if (cand) {
+    const size_t k = (t * m + j) * BT + b;
+    const double z = a.z[k], y = a.y[k];
+    if (z - a.l[k] < -y) s = -1;
+    else if (a.u[k] - z < y) s = 1;
+  }
+  pa.act[(size_t)slot * m + j] = s;
+}
+
+// After the polish factor (a's streams / dinv / dense-tail stream are the polish factor's): for the QPs marked 1
+//   s = K_d^-1 b, then refine_iter rounds of  s += K_d^-1 (b - K s)      K_d = [[P + d I, A~'], [A~, -d I]], K: d = 0
+//   b = [-q; l_j (lower-active) | u_j (upper-active) | 0 (inactive)],  A~ = A without its inactive rows
+// then x = s_x, z = A x, y = s_y (0 on inactive rows), the projection t = z + y, z = clip(t, l, u), y = t - z, the
+// residuals and the objective exactly as check_kernel computes them, and the acceptance test against the residuals of the
+// termination check.  Accepted: the polished point becomes the iterate, the solution and the info of the QP.
+// K s runs through the check schedule (P x / A'y / A x): A~'s_y = A's_y (s_y is 0 on inactive rows), A~ s_x = A s_x
+// masked.  Thread / barrier structure as check_body (one QP shared by the grid in the dataflow form).
+template <int BT, int NT, bool GX, bool WIDE = false>
+__global__ __launch_bounds__(NT) void polish_kernel(KernelArgs a, PolishArgs pa) {
+  extern __shared__ double smem[];
+  bool df = false, dfm = false;
+  if constexpr (GX && BT == 1 && WIDE) { df = a.df != 0; dfm = df && a.mw_groups > 1; }
+  const Mw mw{a.mw_bar, dfm ? (unsigned)a.mw_groups : 1u};
+  const int tile = dfm ? 0 : blockIdx.x;
+  const int ltid = threadIdx.x, lwave = __builtin_amdgcn_readfirstlane(ltid >> 6), lnw = blockDim.x >> 6;
+  const int tid = dfm ? blockIdx.x * blockDim.x + threadIdx.x : threadIdx.x, nthr = dfm ? blockDim.x * mw.G : blockDim.x;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nthr >> 6;
+  const int b = tid % BT;
+  auto sync = [&]() { if constexpr (GX && BT == 1 && WIDE) wg_or_grid_barrier(mw); else __syncthreads(); };
+  auto gscratch = [&](int slot) { return a.mw_scratch + (size_t)slot * 256 * 16; };
+  const int n = a.n, m = a.m, N = a.N;
+  const uint32_t sh = a.df_shadow;
+  double *red;
+  double *xs = solve_vector<BT, GX>(a, smem, tile, red);
+  TilePtrs<BT> p = tile_ptrs<BT>(a, tile);
+  p.act = 0;
+#pragma unroll
+  for (int bb = 0; bb < BT; bb++) {       // QPs not polished stream nothing (same for every thread: wave-uniform)
+    const int sl = tile * BT + bb;
+    if (sl < a.B && pa.stat[sl] == 1) { p.act |= 1 << bb; continue; }
+    p.vfwd.vals[bb] = make_rsrc(nullptr, 0u); p.vbwd.vals[bb] = make_rsrc(nullptr, 0u);
+    p.vchk.vals[bb] = make_rsrc(nullptr, 0u); p.vdt[bb] = make_rsrc(nullptr, 0u);
+  }
+  if (!p.act) return;
+  const int slot = tile * BT + b;
+  const bool on = (p.act >> b) & 1;
+  const signed char *act = pa.act + (size_t)(on ? slot : 0) * m;
+  double *s = pa.sol + (size_t)tile * N * BT;
+  auto put_rhs = [&](int e, double v) {        // natural entry e / BT of the right-hand side -> the solve vector
+    const uint32_t pe = a.pinv[e / BT];
+    if (df) { st_sc1(xs + pe, v); df_arm_fwd(xs, pe, a.rflag[pe], a.xloc[pe], sh); }
+    else xs[(size_t)pe * BT + b] = v;
+  };
+  auto get_sol = [&](int e) -> double {
+    const uint32_t pe = a.pinv[e / BT];
+    return df ? ld_sc1(xs + df_bloc(pe, a.rflag[pe], sh)) : xs[(size_t)pe * BT + b];
+  };
+  const size_t nB = (size_t)n * BT, mB = (size_t)m * BT;
+  auto spmv = [&]() {                           // natural [x; y] in xs -> P x, A'y, A x in out1
+    sync();
+    run_spmv<BT, MI_PFV, WIDE>(a.chk, p.vchk, xs, p.out1, wave, lane, 0, 3, nw);
+    sync();
+  };
+  for (int r = 0; r <= pa.refine_iter; r++) {
+    if (r > 0) {
+      for (int e = tid; e < N * BT; e += nthr) xs[e] = s[e];
+      spmv();
+    }
+    for (int e = tid; e < N * BT; e += nthr) {
+      double v = 0.0;
+      if (on) {
+        const int i = e / BT;
+        if (i < n) {
+          v = -p.q[e];
+          if (r > 0) v -= p.out1[e] + p.out1[nB + e];
+        } else {
+          const int ez = e - (int)nB;
+          const signed char c = act[i - n];
+          if (c) {
+            v = c < 0 ? p.l[ez] : p.u[ez];
+            if (r > 0) v -= p.out1[2 * nB + ez];
+          }
+        }
+      }
+      put_rhs(e, v);
+    }
+    if (df && tid == 0) st_sc1(xs + 2 * (size_t)sh, 0.0);
+    sync();
+    kkt_solve_lds<BT, MI_PFV_NT(NT, GX), GX, WIDE>(a, p, xs, tid, nthr, wave, nw, lane, mw);
+    for (int e = tid; e < N * BT; e += nthr) {
+      const int i = e / BT;
+      double d = get_sol(e);
+      if (i >= n && !act[i - n]) d = 0.0;
+      s[e] = r ? s[e] + d : d;
+    }
+    sync();
+  }
+  // z = A x
+  for (int e = tid; e < N * BT; e += nthr) xs[e] = e < (int)nB ? s[e] : 0.0;
+  spmv();
+  // y from y_red, normal-cone projection: t = z + y, z = clip(t, l, u), y = t - z   (z -> out2)
+  for (int e = tid; e < (int)mB; e += nthr) {
+    const double t = p.out1[2 * nB + e] + s[nB + e];
+    const double zn = fmin(fmax(t, p.l[e]), p.u[e]);
+    p.out2[e] = zn; s[nB + e] = t - zn;
+  }
+  sync();
+  // residuals and objective at the polished point (check_kernel's arithmetic)
+  for (int e = tid; e < N * BT; e += nthr) xs[e] = s[e];
+  spmv();
+  const double cinv = p.dscal[DS_CINV * BT + b];
+  const bool unscale = a.scaling && !a.scaled_termination;
+  double mx[4] = {0.0, 0.0, 0.0, 0.0};
+  double sm[1] = {0.0};
+  for (int e = tid; e < (int)nB; e += nthr) {
+    const double px = p.out1[e], aty = p.out1[nB + e], qv = p.q[e], xv = s[e];
+    double dres = qv + px;
+    dres += aty;
+    mx[0] = fmax(mx[0], fabs(dres)); mx[1] = fmax(mx[1], fabs(p.Dsc_inv[e] * dres));
+    sm[0] += 0.5 * xv * px + qv * xv;
+  }
+  for (int e = tid; e < (int)mB; e += nthr) {
+    const double pres = p.out1[2 * nB + e] - p.out2[e];
+    mx[2] = fmax(mx[2], fabs(pres)); mx[3] = fmax(mx[3], fabs(p.Esc_inv[e] * pres));
+  }
+  block_reduce<BT, 4, true>(mx, red, ltid, lwave, lnw, lane);
+  block_reduce<BT, 1, false>(sm, red, ltid, lwave, lnw, lane);
+  if constexpr (GX && BT == 1 && WIDE) {
+    grid_reduce<4, true>(mx, red, mw, gscratch(0), ltid, lwave, lnw, lane);
+    grid_reduce<1, false>(sm, red, mw, gscratch(1), ltid, lwave, lnw, lane);
+  }
+  const double pri = (m == 0) ? 0.0 : (unscale ? mx[3] : mx[2]);
+  const double dua = unscale ? cinv * mx[1] : mx[0];
+  double obj = sm[0];
+  if (a.scaling) obj *= cinv;
+  const double pri0 = p.dscal[DS_PRI_RES * BT + b], dua0 = p.dscal[DS_DUA_RES * BT + b];
+  const bool acc = on && ((pri < pri0 && dua < dua0) || (pri < pri0 && dua0 < 1e-10) || (dua < dua0 && pri0 < 1e-10));
+  sync();
+  if (acc) {
+    for (int e = tid; e < (int)nB; e += nthr) {
+      const double xv = s[e];
+      p.x[e] = xv;
+      a.x_out[(size_t)slot * n + e / BT] = a.scaling ? p.Dsc[e] * xv : xv;
+    }
+    for (int e = tid; e < (int)mB; e += nthr) {
+      const double yv = s[nB + e];
+      p.z[e] = p.out2[e]; p.y[e] = yv;
+      a.y_out[(size_t)slot * m + e / BT] = a.scaling ? p.Esc[e] * yv * cinv : yv;
+    }
+  }
+  if (tid < BT && on) {
+    pa.stat[slot] = acc ? 1 : -1;
+    if (acc) { p.dscal[DS_PRI_RES * BT + b] = pri; p.dscal[DS_DUA_RES * BT + b] = dua; p.dscal[DS_OBJ * BT + b] = obj; }
+  }
+}
+
 // Debug twin of kkt_solve_kernel<2, 512, false> (MI_OSQP trace entry point, scripts/trace_phases.py): same
 // solve, plus per-phase / per-wave shader-clock stamps of tiles {0, gridDim/2} copied to trace[2][words].
 // Layout of one tile's words: [0..3] = memtime / memrealtime at start and end (low words), [4..5] = memtime before / after
@@ -1946,8 +2114,8 @@ __global__ __launch_bounds__(1024) void factor_kernel(FactorArgs a) {
   if constexpr (LBL) { Lb = lds_rest; Dl = lds_rest + (size_t)a.storage * BT; }
   else { Lb = a.Lblk + (size_t)tile * a.storage * BT; Dl = a.Dl + (size_t)tile * N * BT; }
   const double rho = a.dscal[H(DS_COUNT, DS_RHO)];
-  // ---- rho vector of the QPs being refactored ([EXT] osqp_update_rho)
-  if (flag && !a.force_all) {
+  // ---- rho vector of the QPs being refactored ([EXT] osqp_update_rho); not for a polish factor
+  if (flag && !a.force_all && !a.pmask) {
     for (int e = tid; e < m * BT; e += nthr) {
       const size_t k = H(m, e / BT);
       const double l = a.l[k], u = a.u[k];
@@ -1986,8 +2154,12 @@ __global__ __launch_bounds__(1024) void factor_kernel(FactorArgs a) {
         if (kind == 0) v[u] = a.pa_val[H(a.pa_len, idx)];
         else if (kind == 1) v[u] = a.pa_val[H(a.pa_len, idx)] + a.sigma;
         else if (kind == 2) v[u] = a.sigma;
-        else if (kind == 3) v[u] = a.pa_val[H(a.pa_len, (size_t)a.nnzP + idx)];
-        else v[u] = -a.rho_inv[H(m, idx)];
+        else if (kind == 3) {
+          // polish factor: the entries of inactive rows are zero (the row decouples; its solution entry is 0)
+          const bool off = a.pmask && (slot < 0 || a.pmask[(size_t)slot * m + a.arow[idx]] == 0);
+          v[u] = off ? 0.0 : a.pa_val[H(a.pa_len, (size_t)a.nnzP + idx)];
+        }
+        else v[u] = a.pmask ? -a.pdelta : -a.rho_inv[H(m, idx)];
       }
 #pragma unroll
       for (int u = 0; u < UA; u++) if (e0 + u * nthr < tot) Lb[(size_t)dst[u] * BT + b] = v[u];
@@ -2118,7 +2290,8 @@ __global__ __launch_bounds__(1024) void factor_kernel(FactorArgs a) {
   if (tid < BT && slot >= 0 && flag && a.use_work) a.use_work[slot] = 1;      // this QP's factor now lives in the working copy
   sync();
   __threadfence();          // (continuous batching: an advance launch on another stream may read the flag)
-  if (tid < BT && slot >= 0) a.iscal[H(IS_COUNT, IS_NEED_REFACTOR)] = bad_inertia ? -1 : 0;   // -1: the new factor has the wrong inertia
+  if (a.pmask) { if (tid < BT && slot >= 0 && bad_inertia) a.pstat[slot] = -1; }        // polish factor: that QP is not polished
+  else if (tid < BT && slot >= 0) a.iscal[H(IS_COUNT, IS_NEED_REFACTOR)] = bad_inertia ? -1 : 0;   // -1: the new factor has the wrong inertia
 }
 
 template <int BT, bool LBL = false>
@@ -2570,7 +2743,7 @@ __global__ __launch_bounds__(512) void tail_kernel(TailArgs a) {
   if (tid == 0) {
     const int total = a.npos[slot] + npos;
     a.npos[slot] = total;
-    if (total != a.n) a.iscal[H(IS_COUNT, IS_NEED_REFACTOR)] = -1;
+    if (total != a.n) { if (a.pstat) a.pstat[slot] = -1; else a.iscal[H(IS_COUNT, IS_NEED_REFACTOR)] = -1; }
   }
   if (a.trace) {
     __syncthreads();
@@ -3365,6 +3538,23 @@ hipError_t launch_kkt_solve(const KernelArgs &a, int BT, int tiles, int threads,
   if (a.df && debug_drop_group("kkt") && tiles > 1) tiles--;
 #endif
   MI_DISPATCH(kkt_solve_kernel, a, rhs, sol);
+}
+hipError_t launch_polish_active(const KernelArgs &a, const PolishArgs &p, int BT, hipStream_t st) {
+  const size_t total = (size_t)a.B * ((size_t)a.m + 1);
+  hipLaunchKernelGGL(polish_active_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, p, BT);
+  return hipGetLastError();
+}
+hipError_t launch_polish(const KernelArgs &a, const PolishArgs &p, int BT, int tiles, int threads, size_t lds, int n_cus, hipStream_t st) {
+  if (a.df && a.mw_groups > 1) {
+    // the grid spins on its barriers: every workgroup must be resident at once
+    if (tiles != 1 || BT != 1 || !a.xs_global || !a.wide || !a.mw_bar || !a.mw_scratch) return hipErrorInvalidValue;
+    int nb = 0;
+    const void *k = reinterpret_cast<const void *>(&polish_kernel<1, 512, true, true>);
+    if (ensure_dynamic_lds(k, lds) != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds) != hipSuccess ||
+        nb * n_cus < a.mw_groups) return hipErrorInvalidValue;
+    tiles = a.mw_groups;
+  }
+  MI_DISPATCH(polish_kernel, a, p);
 }
 hipError_t launch_kkt_trace(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st,
                             const double *rhs, double *sol, uint32_t *trace, uint32_t words) {

@@ -325,6 +325,15 @@ struct mi_osqp_batch {
   DevBuf<int> fail_list;
   // raw triu(P) and q as setup received them ([QP][nnzP], [QP][n]): what mi_osqp_batch_reinit_some equilibrates from
   DevBuf<double> rawP, rawq;
+  // solution polishing (section "polish"): the polish factor's streams / dinv / dense-tail stream, the refinement iterate,
+  // the active set and the per-QP state - allocated at the first polish of the handle; the ADMM factor never reads them
+  DevBuf<double> pol_fwd, pol_bwd, pol_dinv, pol_dt, pol_sol;
+  DevBuf<signed char> pol_act;
+  DevBuf<int> pol_stat;
+  std::vector<int> pol_status;          // per QP: status_polish of the last solve (empty: nothing polished yet)
+  int64_t pol_count = 0, pol_accepted = 0;
+  double pol_seconds = 0.0;
+  hipEvent_t evp0 = nullptr, evp1 = nullptr;
   // ---- continuous batching (the per-QP entry points + advance / poll; section "continuous" below)
   struct Cont {
     bool on = false;
@@ -362,6 +371,8 @@ struct mi_osqp_batch {
     for (int k = 0; k < 2; k++) { hostpool::give(cont.h_is[k], cont.h_is_cap[k]); hostpool::give(cont.h_ds[k], cont.h_ds_cap[k]); if (cont.ev[k]) (void)hipEventDestroy(cont.ev[k]); }
     hostpool::give(cont.xh, cont.xh_cap); hostpool::give(cont.yh, cont.yh_cap); hostpool::give(cont.ring_h, cont.ring_h_cap);
     if (cont.ev_adv) (void)hipEventDestroy(cont.ev_adv);
+    if (evp0) (void)hipEventDestroy(evp0);
+    if (evp1) (void)hipEventDestroy(evp1);
     hostpool::give(cont.h_done, cont.h_done_cap);
     hostpool::give(h_iscal, h_iscal_cap); hostpool::give(h_dscal, h_dscal_cap); hostpool::give(pin, pin_cap); hostpool::give(h_npos, h_npos_cap);
     if (stream && ev0 && ev1 && evf0 && evf1 && evf2) streampool::give({device, stream, {ev0, ev1, evf0, evf1, evf2}});
@@ -384,6 +395,7 @@ static Settings to_settings(const mi_osqp_settings *s) {
   t.max_iter = s->max_iter; t.eps_abs = s->eps_abs; t.eps_rel = s->eps_rel; t.eps_prim_inf = s->eps_prim_inf;
   t.eps_dual_inf = s->eps_dual_inf; t.alpha = s->alpha; t.scaled_termination = s->scaled_termination;
   t.check_termination = s->check_termination; t.warm_start = s->warm_start; t.verbose = s->verbose;
+  t.polish = s->polish; t.polish_refine_iter = s->polish_refine_iter; t.delta = s->delta;
   return t;
 }
 
@@ -1097,11 +1109,18 @@ static int fail_slots(mi_osqp_batch *h, const KernelArgs &a, const std::vector<i
 // Row E13 on the device for a list of slots (tile * BT + b): rho vector from the current bounds and rho, KKT
 // assembly, block LDL', scatter into the solve streams.  The work list packs the slots kbt per workgroup.
 // Slots whose new factor has the wrong inertia are appended to *bad (the caller isolates them).
-static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::vector<int> *bad) {
+// pol != null: the polish factor of the listed slots instead (FactorArgs::pmask; section "polish"): it goes to the polish
+// buffers, leaves the ADMM factor, the rho vectors, the flags and the refactorisation statistics alone, and a wrong inertia
+// only marks the slot's polish as failed.
+static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::vector<int> *bad, const PolishArgs *pol = nullptr) {
   if (work.empty()) return 0;
   const int BT = h->BT;
   int rc;
   FactorArgs fa = make_factor_args(h, 0);
+  if (pol) {
+    fa.pmask = pol->act; fa.arow = h->rz_arow.p; fa.pstat = pol->stat; fa.pdelta = h->st.delta; fa.sigma = h->st.delta;
+    fa.fwd_val = h->pol_fwd.p; fa.bwd_val = h->pol_bwd.p; fa.dinv = h->pol_dinv.p; fa.use_work = nullptr;
+  }
   // QPs per workgroup of this refactorisation: one while every QP can have a CU of its own (a lone tile is
   // latency-bound: 3.3 ms with one QP, 4.6 ms with two), the solve tiling otherwise (measured: 605 QPs take
   // 10.9 ms whether packed 1, 2 or 4 per workgroup - the memory system, not the tiling, is the limit there)
@@ -1142,6 +1161,7 @@ static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::v
     da.dt_task = h->dt_task.p; da.dt_task_step = h->dt_task_step.p; da.n_tasks = (uint32_t)(dt.task.size() / 4);
     da.asm_q64 = h->dt_asm_q64.p; da.diag_tile = h->dt_diag_tile.p; da.src_tile = h->dt_src_tile.p;
     da.Lblk = h->Lblk.p; da.Dl = h->Dl.p; da.Sd = h->dt_Sd.p; da.dt_val = h->dt_val.p; da.dinv = h->dinv.p; da.npos = h->npos.p; da.iscal = h->iscal.p;
+    if (pol) { da.dt_val = h->pol_dt.p; da.dinv = h->pol_dinv.p; da.pstat = pol->stat; }
     unsigned long long *d_trace = nullptr;
     const bool tracing = getenv("MI_OSQP_TAIL_TRACE") != nullptr;          // timing stamps only; results are unaffected
     if (tracing) { HIPCHK(hipMalloc((void **)&d_trace, (size_t)wtiles * kbt * 8 * sizeof(unsigned long long))); HIPCHK(hipMemsetAsync(d_trace, 0, (size_t)wtiles * kbt * 64, h->stream)); }
@@ -1169,10 +1189,11 @@ static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::v
       if (w[4 * (size_t)t + 2]) {
         // a workgroup of a group never showed up: the streams of the listed QPs hold a half-written factor.  Every listed
         // QP is without a valid factor (kNonConvex on every solve) until a later refactorisation of it succeeds.
-        for (int sl : work) if (sl >= 0 && sl < h->B) h->failed[(size_t)sl] = 1;
+        if (!pol) for (int sl : work) if (sl >= 0 && sl < h->B) h->failed[(size_t)sl] = 1;
         g_last_error = "refactorisation on several workgroups: a barrier of the group timed out"; return MI_OSQP_ERR_DEVICE;
       }
   }
+  if (pol) return 0;
   {
     float f = 0.f, d = 0.f;
     HIPCHK(hipEventElapsedTime(&f, h->evf0, h->evf1)); HIPCHK(hipEventElapsedTime(&d, h->evf1, h->evf2));
@@ -1203,6 +1224,59 @@ static int refactor_qps(mi_osqp_batch *h, std::vector<int> qps) {
   if ((rc = fail_slots(h, make_args(h), bad, 0))) return rc;
   if ((int)bad.size() == h->B) { g_last_error = "the KKT factor lost its inertia"; return MI_OSQP_ERR_NONCONVEX; }
   return 0;
+}
+
+// ------------------------------------------------------------------- polish
+// Solution polishing after a blocking solve (OSQP polish.c on the scaled data): the active set of
+// every kOptimal QP (polish_active_kernel), the reduced KKT matrix of those QPs factored in the handle's own pattern into
+// the polish buffers (device_refactor_slots in polish mode: same work list / grouped workgroups / dense tail as a
+// refactorisation), then polish_kernel: solve + refinement, projection, residuals, acceptance and write-back.  `a` = the
+// solve's arguments (its x_out receives the polished solutions).  No per-QP host work beyond the work list.
+static int polish_impl(mi_osqp_batch *h, const KernelArgs &a) {
+  const Analysis &an = (*h->anp);
+  const int BT = h->BT, ntl = h->ntiles;
+  const size_t T = (size_t)ntl * BT;
+  int rc;
+  h->pol_count = h->pol_accepted = 0; h->pol_seconds = 0.0;
+  h->pol_status.assign((size_t)h->B, 0);
+  if (!h->pol_stat.p) {
+    if ((rc = h->pol_fwd.alloc(h->fwd_val.n)) || (rc = h->pol_fwd.zero(h->stream)) || (rc = h->pol_bwd.alloc(h->bwd_val.n)) ||
+        (rc = h->pol_bwd.zero(h->stream)) || (rc = h->pol_dinv.alloc(h->dinv.n)) || (rc = h->pol_dinv.zero(h->stream)) ||
+        (rc = h->pol_sol.alloc(T * an.N)) || (rc = h->pol_act.alloc(std::max<size_t>(1, T * an.m))) || (rc = h->pol_act.zero(h->stream)) ||
+        (rc = h->pol_stat.alloc(T)) || (rc = h->pol_stat.zero(h->stream))) return rc;
+    if (an.dt.k && ((rc = h->pol_dt.alloc(h->dt_val.n)) || (rc = h->pol_dt.zero(h->stream)))) return rc;
+    if (!h->evp0) HIPCHK(hipEventCreate(&h->evp0));
+    if (!h->evp1) HIPCHK(hipEventCreate(&h->evp1));
+  }
+  std::vector<int> work;                // the QPs that ended kOptimal (h_iscal: copied at the end of the solve)
+  for (int q = 0; q < h->B; q++)
+    if (h->h_iscal[(size_t)(q / BT) * IS_COUNT * BT + IS_STATUS * BT + q % BT] == 1) work.push_back(q);
+  PolishArgs pa{h->pol_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter};
+  HIPCHK(hipEventRecord(h->evp0, h->stream));
+  HIPCHK(launch_polish_active(a, pa, BT, h->stream));
+  const int n_pol = (int)work.size();
+  if (n_pol) {
+    if ((rc = device_refactor_slots(h, std::move(work), nullptr, &pa))) return rc;
+    KernelArgs ap = a;
+    ap.fwd_val = h->pol_fwd.p; ap.bwd_val = h->pol_bwd.p; ap.dinv = h->pol_dinv.p; ap.dt_val = h->pol_dt.p; ap.use_work = nullptr;
+    std::unique_lock<std::mutex> spin_lock(spin_mutex(h->device), std::defer_lock);
+    if (h->mw_groups > 0) { spin_lock.lock(); HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), h->stream)); }
+    HIPCHK(launch_polish(ap, pa, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds, h->n_cus, h->stream));
+    HIPCHK(hipEventRecord(h->evp1, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (spin_lock.owns_lock()) spin_lock.unlock();
+    if ((rc = mw_barrier_ok(h))) return rc;
+  } else {
+    HIPCHK(hipEventRecord(h->evp1, h->stream));
+  }
+  HIPCHK(hipMemcpyAsync(h->pol_status.data(), h->pol_stat.p, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, h->evp0, h->evp1));
+  h->pol_seconds = ms * 1e-3;
+  h->pol_count = n_pol;
+  for (int v : h->pol_status) h->pol_accepted += v == 1;
+  return MI_OSQP_OK;
 }
 
 // The ADMM loop runs in segments that end at every termination-check / rho-update
@@ -1304,6 +1378,7 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
   for (int qi = 0; qi < h->B; qi++)
     h->last_total_iters += h->h_iscal[(size_t)(qi / BT) * IS_COUNT * BT + IS_ITER * BT + qi % BT];
   h->solved_once = true;
+  if (h->st.polish && (rc = polish_impl(h, a))) return rc;
   return MI_OSQP_OK;
 }
 
@@ -1317,6 +1392,7 @@ void mi_osqp_default_settings(mi_osqp_settings *s) {
   s->adaptive_rho_tolerance = 5.0; s->max_iter = 4000; s->eps_abs = 1e-3; s->eps_rel = 1e-3;
   s->eps_prim_inf = 1e-4; s->eps_dual_inf = 1e-4; s->alpha = 1.6; s->scaled_termination = 0;
   s->check_termination = 25; s->warm_start = 1; s->verbose = 0;
+  s->polish = 0; s->polish_refine_iter = 3; s->delta = 1e-6;
 }
 
 const char *mi_osqp_exit_code_name(int64_t c) {
@@ -1330,7 +1406,7 @@ const char *mi_osqp_error_name(int64_t e) {
                                 "non-convex problem / KKT inertia", "device error", "null argument", "allocation / size"};
   return (e >= 0 && e <= 7) ? names[e] : "unknown";
 }
-const char *mi_osqp_version(void) { return "mi-osqp 0.1 (gfx950)"; }
+const char *mi_osqp_version(void) { return "mi-osqp 0.2 (gfx950)"; }
 const char *mi_osqp_last_error(void) { return g_last_error.c_str(); }
 
 static int64_t exit_code_of(int status) {
@@ -1441,7 +1517,25 @@ int mi_osqp_batch_get_info(mi_osqp_batch *h, mi_osqp_info *info) {
     I.iter = ti[IS_ITER * BT + b]; I.status_val = ti[IS_STATUS * BT + b]; I.exit_code = exit_code_of((int)I.status_val);
     I.obj_val = td[DS_OBJ * BT + b]; I.pri_res = td[DS_PRI_RES * BT + b]; I.dua_res = td[DS_DUA_RES * BT + b];
     I.rho_updates = ti[IS_RHO_UPDATES * BT + b]; I.rho_estimate = td[DS_RHO_EST * BT + b]; I.rho = td[DS_RHO * BT + b];
+    I.status_polish = h->pol_status.empty() ? 0 : h->pol_status[(size_t)q];
   }
+  return MI_OSQP_OK;
+}
+
+int mi_osqp_batch_last_polish_stats(mi_osqp_batch *h, int64_t *polished, int64_t *accepted, double *seconds) {
+  if (!h) return MI_OSQP_ERR_NULL;
+  if (polished) *polished = h->pol_count;
+  if (accepted) *accepted = h->pol_accepted;
+  if (seconds) *seconds = h->pol_seconds;
+  return MI_OSQP_OK;
+}
+
+int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act) {
+  if (!h || !act) return MI_OSQP_ERR_NULL;
+  const size_t cnt = (size_t)h->B * (*h->anp).m;
+  if (!h->pol_act.p) { memset(act, 0, cnt); return MI_OSQP_OK; }
+  DevGuard guard(h->device);
+  if (cnt) HIPCHK(hipMemcpy(act, h->pol_act.p, cnt, hipMemcpyDeviceToHost));
   return MI_OSQP_OK;
 }
 
@@ -2210,6 +2304,7 @@ int mi_osqp_batch_warm_start_x_some(mi_osqp_batch *h, int64_t n_ids, const int64
 int mi_osqp_batch_solve_begin_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids) {
   CallTimer timer_("batch_solve_begin_some");
   if (!h) return MI_OSQP_ERR_NULL;
+  if (h->st.polish) { g_last_error = "the continuous mode does not polish: set up the handle with polish = 0"; return MI_OSQP_ERR_INVALID_SETTINGS; }
   DevGuard guard(h->device);
   int rc;
   if ((rc = cont_enter(h)) || (rc = cont_check_ids(h, n_ids, ids, true))) return rc;
