@@ -143,6 +143,21 @@ int mi_osqp_update_A_bounds(mi_osqp_solver *h, const int64_t *A_colptr, const in
                             const double *l, const double *u);
 /* QPSolver::setWarmStart = SetPrimalWarmStart ([REF] src/osqp-wrapper.h:45-49). */
 int mi_osqp_warm_start_x(mi_osqp_solver *h, const double *x);
+/* Objective updates (README "Objective updates"; OSQP 0.6.x semantics, no value validation, like OSQP):
+ * osqp_update_lin_cost = osqp-cpp SetObjectiveVector: q_s = c * (D .* q) with the D and c in force; no refactorisation,
+ * iterates and rho kept, the count of rho updates restarts. */
+int mi_osqp_update_q(mi_osqp_solver *h, const double *q);
+/* osqp_update_P = osqp-cpp UpdateObjectiveMatrix: P in the form mi_osqp_setup accepts (both triangles or the upper one);
+ * its upper triangle must have the pattern of setup's (else MI_OSQP_ERR_PATTERN_CHANGED, nothing changed).  P, A and q are
+ * unscaled, triu(P) replaced, the problem equilibrated again (new D, E, c; bounds rescaled) and refactored with the current
+ * rho vectors. */
+int mi_osqp_update_P(mi_osqp_solver *h, const int64_t *P_colptr, const int64_t *P_rowidx, const double *P_val);
+/* osqp_update_P_A = osqp-cpp UpdateObjectiveAndConstraintMatrices: both, with one equilibration and one refactorisation. */
+int mi_osqp_update_P_A(mi_osqp_solver *h, const int64_t *P_colptr, const int64_t *P_rowidx, const double *P_val,
+                       const int64_t *A_colptr, const int64_t *A_rowidx, const double *A_val);
+/* osqp_warm_start_y = osqp-cpp SetDualWarmStart: y_s = c * (Einv .* y), warm_start = 1; x and z untouched.  osqp-cpp
+ * SetWarmStart(x, y) = mi_osqp_warm_start_x followed by mi_osqp_warm_start_y. */
+int mi_osqp_warm_start_y(mi_osqp_solver *h, const double *y);
 /* QPSolver::solve = Solve ([REF] src/osqp-wrapper.h:52); returns error code,
  * exit code and residuals in *info (may be NULL). */
 int mi_osqp_solve(mi_osqp_solver *h, mi_osqp_info *info);
@@ -171,6 +186,15 @@ int mi_osqp_batch_update_bounds(mi_osqp_batch *h, const double *l, const double 
 int mi_osqp_batch_update_A_bounds(mi_osqp_batch *h, const int64_t *A_colptr, const int64_t *A_rowidx, const double *A_val,
                                   const double *l, const double *u);      /* see mi_osqp_update_A_bounds */
 int mi_osqp_batch_warm_start_x(mi_osqp_batch *h, const double *x);
+/* Objective updates of every QP (see mi_osqp_update_q / _update_P / _update_P_A / _warm_start_y): q[B][n]; P values
+ * [B][nnz of the P array as passed], in the caller's CSC order as at setup; y[B][m].  After them the raw P and q the handle
+ * keeps (mi_osqp_batch_reinit_some) are the ones in force.  A QP whose new KKT matrix is not quasi-definite ends its next
+ * solve as kNonConvex; the other QPs are not affected. */
+int mi_osqp_batch_update_q(mi_osqp_batch *h, const double *q);                                     /* osqp_update_lin_cost */
+int mi_osqp_batch_update_P(mi_osqp_batch *h, const int64_t *P_colptr, const int64_t *P_rowidx, const double *P_val);   /* osqp_update_P */
+int mi_osqp_batch_update_P_A(mi_osqp_batch *h, const int64_t *P_colptr, const int64_t *P_rowidx, const double *P_val,
+                             const int64_t *A_colptr, const int64_t *A_rowidx, const double *A_val);  /* osqp_update_P_A */
+int mi_osqp_batch_warm_start_y(mi_osqp_batch *h, const double *y);                                 /* osqp_warm_start_y */
 /* Blocking solve of all B QPs (the ADMM iterate runs on the GPU). */
 int mi_osqp_batch_solve(mi_osqp_batch *h);
 int mi_osqp_batch_get_primal(mi_osqp_batch *h, double *x_out /*[B][n]*/);
@@ -202,10 +226,13 @@ int mi_osqp_batch_update_bounds_device(mi_osqp_batch *h, const double *d_l, cons
 /* QPSolver::update ([REF] src/osqp-wrapper.h:33-43) with the new A values ([B][nnzA], CSC order of setup's pattern) and bounds
  * ([B][m]) in HBM; `stream`: the stream that wrote them (NULL: none pending) */
 int mi_osqp_batch_update_A_bounds_device(mi_osqp_batch *h, const double *d_Av, const double *d_l, const double *d_u, void *stream);
+/* osqp_update_lin_cost with q ([B][n], unscaled) in HBM: nothing crosses PCIe; `stream`: the stream that wrote it */
+int mi_osqp_batch_update_q_device(mi_osqp_batch *h, const double *d_q, void *stream);
 /* Solve and leave x[B][n] (and optionally status[B]/iters[B], int32) in HBM. */
 int mi_osqp_batch_solve_device(mi_osqp_batch *h, double *d_x_out, int32_t *d_status, int32_t *d_iters, void *stream);
 /* Back to the state right after setup (or after the last update that refactored): cold-start every QP, restore rho,
- * the rho vectors and the factor of that moment, forget the count of rho updates.  A planner that builds the same
+ * the rho vectors and the factor of that moment, forget the count of rho updates.  q is not part of that state: the q in
+ * force (the last mi_osqp_batch_update_q, if any) is kept.  A planner that builds the same
  * solver again and again (one per horizon segment and run, [REF] src/gomp-solver.h:61) may keep the handle instead:
  * reset + update_bounds + warm_start gives bitwise the results of a fresh setup with the same P and A.  The bench uses it
  * so that repeated steps do identical work. */
@@ -231,6 +258,7 @@ int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act);
  * advance whatever is iterating without blocking:
  *
  *     reinit_some / update_A_bounds_some / warm_start_x_some   new data for QPs that are not iterating
+ *     update_q_some / warm_start_y_some
  *     solve_begin_some                                         Solve() entry of those QPs (own iteration count from 0)
  *     advance(n_segments)                                      enqueue ONE launch in which every iterating QP runs up to
  *                                                              n_segments segments of L iterations + check, L =
@@ -249,8 +277,8 @@ int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act);
  * advances may be waiting for their poll().  A blocking mi_osqp_batch_* call ends the continuous mode of the handle (solves
  * in flight are forgotten).  Not available for handles whose solve vector does not fit LDS (large single QPs).
  *
- * reinit_some = QPSolver::QPSolver for those QPs ([REF] src/osqp-wrapper.h:16-31) with the P and q given at setup and new
- * A values / bounds: equilibration from the raw data, rho = settings.rho, zero iterates, no rho updates - the state
+ * reinit_some = QPSolver::QPSolver for those QPs ([REF] src/osqp-wrapper.h:16-31) with the P and q in force (those given
+ * at setup, or by the last mi_osqp_batch_update_P / _update_P_A / _update_q / update_q_some of the QP) and new A values / bounds: equilibration from the raw data, rho = settings.rho, zero iterates, no rho updates - the state
  * mi_osqp_batch_setup leaves for that QP, bit for bit, without analysis or allocation.
  * update_A_bounds_some = QPSolver::update ([REF] src/osqp-wrapper.h:33-43) for those QPs. */
 int mi_osqp_batch_reinit_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids,
@@ -258,6 +286,9 @@ int mi_osqp_batch_reinit_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *id
 int mi_osqp_batch_update_A_bounds_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids,
                                        const double *A_val, const double *l, const double *u);
 int mi_osqp_batch_warm_start_x_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *x /*[n_ids][n]*/);
+/* osqp_update_lin_cost / osqp_warm_start_y for those QPs (see mi_osqp_update_q / mi_osqp_warm_start_y) */
+int mi_osqp_batch_update_q_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *q /*[n_ids][n]*/);
+int mi_osqp_batch_warm_start_y_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *y /*[n_ids][m]*/);
 int mi_osqp_batch_solve_begin_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids);   /* polish = 1: MI_OSQP_ERR_INVALID_SETTINGS */
 int mi_osqp_batch_advance(mi_osqp_batch *h, int64_t n_segments);
 /* wait != 0: block until the oldest unpolled advance has run; wait == 0: *n_finished = -1 when it has not.  ids_out receives
@@ -322,6 +353,11 @@ int mi_osqp_multi_batch_update_bounds(mi_osqp_multi *h, const double *l, const d
 int mi_osqp_multi_batch_update_A_bounds(mi_osqp_multi *h, const int64_t *A_colptr, const int64_t *A_rowidx, const double *A_val,
                                         const double *l, const double *u);
 int mi_osqp_multi_batch_warm_start_x(mi_osqp_multi *h, const double *x);
+int mi_osqp_multi_batch_update_q(mi_osqp_multi *h, const double *q);                               /* osqp_update_lin_cost */
+int mi_osqp_multi_batch_update_P(mi_osqp_multi *h, const int64_t *P_colptr, const int64_t *P_rowidx, const double *P_val);  /* osqp_update_P */
+int mi_osqp_multi_batch_update_P_A(mi_osqp_multi *h, const int64_t *P_colptr, const int64_t *P_rowidx, const double *P_val,
+                                   const int64_t *A_colptr, const int64_t *A_rowidx, const double *A_val);    /* osqp_update_P_A */
+int mi_osqp_multi_batch_warm_start_y(mi_osqp_multi *h, const double *y);                           /* osqp_warm_start_y */
 int mi_osqp_multi_batch_solve(mi_osqp_multi *h);
 /* The same without waiting (every shard has one long-lived worker thread; all calls of this section run on them): solve_async
  * returns once the shards have their job, wait() joins them and returns the first shard error.  Any other multi-batch call

@@ -13,8 +13,11 @@
 //   osqp::OsqpSolver::Init / UpdateConstraintMatrix / SetBounds / SetPrimalWarmStart / Solve / primal_solution [REF] :28,36,40,46,52,53
 //   absl::Status::ok / ToString                                                                               [REF] :30,34-48
 //   osqp::OsqpExitCode, osqp::ToString                                                                        [REF] utils.h:11; gomp-solver.h:40,46-49,68,72,79
-// plus dual_solution / iterations / objective_value / IsInitialized.  Entry points of osqp-cpp that the C-ABI has no
-// counterpart for (SetObjectiveVector, UpdateObjectiveMatrix, SetDualWarmStart) return kUnimplemented.
+// plus dual_solution / iterations / objective_value / IsInitialized, and the objective updates and warm starts the reference
+// does not call: SetObjectiveVector, UpdateObjectiveMatrix, UpdateObjectiveAndConstraintMatrices, SetDualWarmStart and
+// SetWarmStart(x, y) (C-ABI mi_osqp_update_q / _update_P / _update_P_A / _warm_start_y; README "Objective updates").
+// Statuses as upstream: kFailedPrecondition before a successful Init, kInvalidArgument for a wrong length or shape or a
+// changed sparsity pattern (the core extracts the upper triangle of an objective matrix given with both).
 //
 // polish, polish_refine_iter and delta map onto the core's solution polishing (mi_osqp_settings, README "Polishing").
 // Settings that the MI355X core does not implement are validated like upstream and otherwise ignored: time_limit,
@@ -198,15 +201,53 @@ class OsqpSolver {
     return from_error(mi_osqp_update_A(h_, reinterpret_cast<const int64_t *>(A.outerIndexPtr()),
                                        reinterpret_cast<const int64_t *>(A.innerIndexPtr()), A.valuePtr()), "osqp_update_A");
   }
-  // entry points of osqp-cpp without a counterpart in the C-ABI (the reference uses none of them)
-  absl::Status SetDualWarmStart(const Eigen::Ref<const Eigen::VectorXd> &) { return unimplemented("SetDualWarmStart"); }
-  absl::Status SetObjectiveVector(const Eigen::Ref<const Eigen::VectorXd> &) { return unimplemented("SetObjectiveVector"); }
-  absl::Status UpdateObjectiveMatrix(const Eigen::SparseMatrix<double, Eigen::ColMajor, c_int> &) { return unimplemented("UpdateObjectiveMatrix"); }
+  // objective updates and dual warm starts (the reference uses none of them)
+  absl::Status SetDualWarmStart(const Eigen::Ref<const Eigen::VectorXd> &dual_vector) {
+    if (!h_) return not_initialized();
+    if (dual_vector.size() != m_) return MI_OSQP_SHIM_STATUS(kInvalidArgument, "The dual warm start has the wrong length");
+    const Eigen::VectorXd y = dual_vector;
+    return from_error(mi_osqp_warm_start_y(h_, y.data()), "osqp_warm_start_y");
+  }
+  absl::Status SetWarmStart(const Eigen::Ref<const Eigen::VectorXd> &primal_vector, const Eigen::Ref<const Eigen::VectorXd> &dual_vector) {
+    if (!h_) return not_initialized();
+    if (primal_vector.size() != n_ || dual_vector.size() != m_) return MI_OSQP_SHIM_STATUS(kInvalidArgument, "The warm start has the wrong length");
+    const absl::Status sx = SetPrimalWarmStart(primal_vector);
+    if (!sx.ok()) return sx;
+    return SetDualWarmStart(dual_vector);
+  }
+  absl::Status SetObjectiveVector(const Eigen::Ref<const Eigen::VectorXd> &objective_vector) {
+    if (!h_) return not_initialized();
+    if (objective_vector.size() != n_) return MI_OSQP_SHIM_STATUS(kInvalidArgument, "The objective vector has the wrong length");
+    const Eigen::VectorXd q = objective_vector;
+    return from_error(mi_osqp_update_q(h_, q.data()), "osqp_update_lin_cost");
+  }
+  absl::Status UpdateObjectiveMatrix(const Eigen::SparseMatrix<double, Eigen::ColMajor, c_int> &objective_matrix) {
+    if (!h_) return not_initialized();
+    if (objective_matrix.rows() != n_ || objective_matrix.cols() != n_)
+      return MI_OSQP_SHIM_STATUS(kInvalidArgument, "The objective matrix has the wrong shape");
+    Eigen::SparseMatrix<double, Eigen::ColMajor, c_int> P = objective_matrix;
+    P.makeCompressed();
+    return from_error(mi_osqp_update_P(h_, reinterpret_cast<const int64_t *>(P.outerIndexPtr()),
+                                       reinterpret_cast<const int64_t *>(P.innerIndexPtr()), P.valuePtr()), "osqp_update_P");
+  }
+  absl::Status UpdateObjectiveAndConstraintMatrices(const Eigen::SparseMatrix<double, Eigen::ColMajor, c_int> &objective_matrix,
+                                                    const Eigen::SparseMatrix<double, Eigen::ColMajor, c_int> &constraint_matrix) {
+    if (!h_) return not_initialized();
+    if (objective_matrix.rows() != n_ || objective_matrix.cols() != n_)
+      return MI_OSQP_SHIM_STATUS(kInvalidArgument, "The objective matrix has the wrong shape");
+    if (constraint_matrix.rows() != m_ || constraint_matrix.cols() != n_)
+      return MI_OSQP_SHIM_STATUS(kInvalidArgument, "The constraint matrix has the wrong shape");
+    Eigen::SparseMatrix<double, Eigen::ColMajor, c_int> P = objective_matrix, A = constraint_matrix;
+    P.makeCompressed(); A.makeCompressed();
+    return from_error(mi_osqp_update_P_A(h_, reinterpret_cast<const int64_t *>(P.outerIndexPtr()),
+                                         reinterpret_cast<const int64_t *>(P.innerIndexPtr()), P.valuePtr(),
+                                         reinterpret_cast<const int64_t *>(A.outerIndexPtr()),
+                                         reinterpret_cast<const int64_t *>(A.innerIndexPtr()), A.valuePtr()), "osqp_update_P_A");
+  }
 
  private:
   void reset() { if (h_) mi_osqp_free(h_); h_ = nullptr; n_ = m_ = 0; }
   static absl::Status not_initialized() { return MI_OSQP_SHIM_STATUS(kFailedPrecondition, "OsqpSolver is not initialized."); }
-  static absl::Status unimplemented(const char *what) { return MI_OSQP_SHIM_STATUS(kUnimplemented, std::string(what) + " is not available in the MI355X core"); }
   static absl::Status from_error(int rc, const char *where) {
     if (rc == MI_OSQP_OK) return MI_OSQP_SHIM_OK();
     std::string msg = std::string(where) + ": " + mi_osqp_error_name(rc);

@@ -97,6 +97,13 @@ def lib():
         L.mi_osqp_batch_update_A_bounds.argtypes = [vp, ip, ip, dp, dp, dp]
         L.mi_osqp_batch_update_bounds.argtypes = [vp, dp, dp]
         L.mi_osqp_batch_warm_start_x.argtypes = [vp, dp]
+        L.mi_osqp_batch_update_q.argtypes = [vp, dp]
+        L.mi_osqp_batch_update_q_device.argtypes = [vp, vp, vp]
+        L.mi_osqp_batch_update_P.argtypes = [vp, ip, ip, dp]
+        L.mi_osqp_batch_update_P_A.argtypes = [vp, ip, ip, dp, ip, ip, dp]
+        L.mi_osqp_batch_warm_start_y.argtypes = [vp, dp]
+        L.mi_osqp_batch_update_q_some.argtypes = [vp, C.c_int64, ip, dp]
+        L.mi_osqp_batch_warm_start_y_some.argtypes = [vp, C.c_int64, ip, dp]
         L.mi_osqp_batch_solve.argtypes = [vp]
         L.mi_osqp_batch_get_primal.argtypes = [vp, dp]
         L.mi_osqp_batch_get_dual.argtypes = [vp, dp]
@@ -131,6 +138,10 @@ def lib():
         L.mi_osqp_update_A.argtypes = [vp, ip, ip, dp]
         L.mi_osqp_update_bounds.argtypes = [vp, dp, dp]
         L.mi_osqp_warm_start_x.argtypes = [vp, dp]
+        L.mi_osqp_update_q.argtypes = [vp, dp]
+        L.mi_osqp_update_P.argtypes = [vp, ip, ip, dp]
+        L.mi_osqp_update_P_A.argtypes = [vp, ip, ip, dp, ip, ip, dp]
+        L.mi_osqp_warm_start_y.argtypes = [vp, dp]
         L.mi_osqp_solve.argtypes = [vp, C.POINTER(Info)]
         L.mi_osqp_get_primal.argtypes = [vp, dp]
         L.mi_osqp_get_dual.argtypes = [vp, dp]
@@ -142,6 +153,10 @@ def lib():
         L.mi_osqp_multi_batch_update_bounds.argtypes = [vp, dp, dp]
         L.mi_osqp_multi_batch_update_A_bounds.argtypes = [vp, ip, ip, dp, dp, dp]
         L.mi_osqp_multi_batch_warm_start_x.argtypes = [vp, dp]
+        L.mi_osqp_multi_batch_update_q.argtypes = [vp, dp]
+        L.mi_osqp_multi_batch_update_P.argtypes = [vp, ip, ip, dp]
+        L.mi_osqp_multi_batch_update_P_A.argtypes = [vp, ip, ip, dp, ip, ip, dp]
+        L.mi_osqp_multi_batch_warm_start_y.argtypes = [vp, dp]
         L.mi_osqp_multi_batch_solve.argtypes = [vp]
         L.mi_osqp_multi_batch_solve_async.argtypes = [vp]
         L.mi_osqp_multi_batch_wait.argtypes = [vp]
@@ -309,6 +324,38 @@ class BatchSolver:
         x = _f64(x).reshape(self.B, -1)
         _chk(lib().mi_osqp_batch_warm_start_x(self._h, _dp(x)), "warm_start_x")
 
+    # ---- objective updates (OSQP osqp_update_lin_cost / osqp_update_P / osqp_update_P_A / osqp_warm_start_y)
+    def update_q(self, q):
+        q = _f64(q).reshape(self.B, -1)
+        _chk(lib().mi_osqp_batch_update_q(self._h, _dp(q)), "update_q")
+
+    def update_q_device(self, q, stream=None):
+        """update_q from a torch CUDA tensor ([B, n], float64, contiguous)."""
+        _chk(lib().mi_osqp_batch_update_q_device(self._h, C.c_void_p(q.data_ptr()), None if stream is None else C.c_void_p(stream)),
+             "update_q_device")
+
+    def _P_arrays(self, Px, P_pattern):
+        Pp, Pi = self._Pp, self._Pi
+        if P_pattern is not None:
+            P = _csc(P_pattern)
+            Pp, Pi = _i64(P.indptr), _i64(P.indices)
+        return Pp, Pi, _f64(Px).reshape(self.B, -1)
+
+    def update_P(self, Px, P_pattern=None):
+        """New P values [B, nnz] in the CSC order of P_pattern (default: setup's pattern); both triangles or the upper one."""
+        Pp, Pi, Px = self._P_arrays(Px, P_pattern)
+        _chk(lib().mi_osqp_batch_update_P(self._h, _ip(Pp), _ip(Pi), _dp(Px)), "update_P")
+
+    def update_P_A(self, Px, Ax, P_pattern=None):
+        Pp, Pi, Px = self._P_arrays(Px, P_pattern)
+        Ax = _f64(Ax).reshape(self.B, -1)
+        _chk(lib().mi_osqp_batch_update_P_A(self._h, _ip(Pp), _ip(Pi), _dp(Px), _ip(self._Ap), _ip(self._Ai), _dp(Ax)),
+             "update_P_A")
+
+    def warm_start_y(self, y):
+        y = _f64(y).reshape(self.B, -1)
+        _chk(lib().mi_osqp_batch_warm_start_y(self._h, _dp(y)), "warm_start_y")
+
     def reset(self):
         _chk(lib().mi_osqp_batch_reset(self._h), "reset")
 
@@ -366,6 +413,14 @@ class BatchSolver:
     def warm_start_x_some(self, ids, x):
         ids = _i64(ids); x = _f64(x).reshape(len(ids), -1)
         _chk(lib().mi_osqp_batch_warm_start_x_some(self._h, len(ids), _ip(ids), _dp(x)), "warm_start_x_some")
+
+    def update_q_some(self, ids, q):
+        ids = _i64(ids); q = _f64(q).reshape(len(ids), -1)
+        _chk(lib().mi_osqp_batch_update_q_some(self._h, len(ids), _ip(ids), _dp(q)), "update_q_some")
+
+    def warm_start_y_some(self, ids, y):
+        ids = _i64(ids); y = _f64(y).reshape(len(ids), -1)
+        _chk(lib().mi_osqp_batch_warm_start_y_some(self._h, len(ids), _ip(ids), _dp(y)), "warm_start_y_some")
 
     def solve_begin_some(self, ids):
         ids = _i64(ids)
@@ -523,6 +578,23 @@ class MultiBatchSolver:
     def warm_start_x(self, x):
         x = _f64(x).reshape(self.B, -1)
         _chk(lib().mi_osqp_multi_batch_warm_start_x(self._h, _dp(x)), "multi warm_start_x")
+
+    def update_q(self, q):
+        q = _f64(q).reshape(self.B, -1)
+        _chk(lib().mi_osqp_multi_batch_update_q(self._h, _dp(q)), "multi update_q")
+
+    def update_P(self, Px):
+        Px = _f64(Px).reshape(self.B, -1)
+        _chk(lib().mi_osqp_multi_batch_update_P(self._h, _ip(self._Pp), _ip(self._Pi), _dp(Px)), "multi update_P")
+
+    def update_P_A(self, Px, Ax):
+        Px, Ax = _f64(Px).reshape(self.B, -1), _f64(Ax).reshape(self.B, -1)
+        _chk(lib().mi_osqp_multi_batch_update_P_A(self._h, _ip(self._Pp), _ip(self._Pi), _dp(Px), _ip(self._Ap), _ip(self._Ai),
+                                                  _dp(Ax)), "multi update_P_A")
+
+    def warm_start_y(self, y):
+        y = _f64(y).reshape(self.B, -1)
+        _chk(lib().mi_osqp_multi_batch_warm_start_y(self._h, _dp(y)), "multi warm_start_y")
 
 
 class QPSolver:

@@ -184,7 +184,7 @@ hipError_t launch_interleave(const double *src, double *dst, const int *ids, int
 hipError_t launch_scatter(const double *src, double *dst, const int *map, const int *ids, int nq, int srclen,
                           const SchedDev &sd, int BT, hipStream_t st);
 hipError_t launch_deinterleave(const double *src, double *dst, int nq, int len, int BT, hipStream_t st);
-// Row E2 on the device (ruiz_kernel): new raw A values (and bounds) of every QP of the batch -> unscale, Ruiz rescale,
+// Row E2 on the device (ruiz_kernel): new raw A and / or P values (and bounds) of every QP of the batch -> unscale, Ruiz rescale,
 // scaled bounds; one workgroup per QP, the arithmetic and its order are those of host_core.cpp scale_qp / unscale_qp.
 struct RuizArgs {
   int n, m, nnzP, nnzA, B, BT, iters;
@@ -193,13 +193,21 @@ struct RuizArgs {
   int fresh;                                 // 1: equilibrate from the raw P and q kept since setup (rawP / rawq, [QP][nnzP], [QP][n]) instead of
   const double *rawP, *rawq;                 //    unscaling the values in force: bit for bit what setup computes for (P, q, rawA, rawl, rawu)
   const int32_t *Prow, *Pcol, *Arow, *Acol;   // per entry of triu(P) / A: row, column
-  const double *rawA;                        // [B][nnzA] new values of A (natural CSC order)
+  const double *rawPnew;                     // non-null (fresh = 0): [B][nnzP] new values of triu(P) (analysis order) replace the unscaled P
+  const double *rawA;                        // [B][nnzA] new values of A (natural CSC order), or null: unscale A with the E, D in force
   const double *rawl, *rawu;                 // [B][m] new bounds, or null: keep the bounds (unscale, rescale)
   double *pa_val, *q, *Dsc, *Dsc_inv, *Esc, *Esc_inv, *l, *u, *dscal;      // tile-interleaved state of the handle
   double *dn, *en;                           // scratch [B][n], [B][m]
   double *pa_out;                            // [B][nnzP + nnzA]: the scaled values once more, QP-major (for the check-stream scatter)
 };
 hipError_t launch_ruiz(const RuizArgs &a, hipStream_t st);
+// objective vector (osqp_update_lin_cost, lin_cost_kernel): raw q QP-major [nq][n] (row j = QP ids[j], or j when ids is null)
+// -> q = c * (D .* q) in the tile-interleaved layout (scaling != 0; else q itself) and the raw q into rawq[QP][n]
+hipError_t launch_lin_cost(const double *gq, const int *ids, double *q, double *rawq, const double *Dsc, const double *dscal,
+                           int nq, int n, int BT, int scaling, hipStream_t st);
+// dual warm start (osqp_warm_start_y, warm_start_y_kernel): y = c * (Einv .* y0) of the QPs a.sel addresses (null: every QP,
+// y0 [B][m]); x and z are left alone
+hipError_t launch_warm_start_y(const KernelArgs &a, int nslots, int BT, hipStream_t st, const double *y0);
 // ---- per-QP entry points (continuous batching; solver.hip "continuous")
 // begin a solve of the listed slots: status unsolved, own iteration count 0, next epoch, pending until an advance launch
 // activates it; slots whose factor is invalid (IS_NEED_REFACTOR < 0) end at once as kNonConvex.

@@ -3017,6 +3017,40 @@ __global__ void bounds_kernel(const double *__restrict__ gl, const double *__res
   if (want != rho_vec[e]) atomicOr(changed, 1);
 }
 
+// objective vector update on device (osqp_update_lin_cost): q <- c * (D .* q_raw), the raw q kept QP-major in rawq.
+// Reads QP-major (coalesced), writes the tile-interleaved q BT doubles apart, like interleave_kernel.
+__global__ void lin_cost_kernel(const double *__restrict__ gq, const int *__restrict__ ids, double *q, double *rawq,
+                                const double *__restrict__ Dsc, const double *__restrict__ dscal, int nq, int n, int BT,
+                                int scaling) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (size_t)nq * n) return;
+  const int j = (int)(g / n), i = (int)(g % n);
+  const int qp = ids ? ids[j] : j;
+  const size_t tile = (size_t)(qp / BT), b = (size_t)(qp % BT);
+  const size_t e = (tile * n + i) * BT + b;
+  const double raw = gq[g];
+  double v = raw;
+  if (scaling) { v *= Dsc[e]; v *= dscal[(tile * DS_COUNT + DS_C) * BT + b]; }      // (D first, then c: OSQP's order)
+  q[e] = v;
+  rawq[(size_t)qp * n + i] = raw;
+}
+
+// dual warm start (osqp_warm_start_y): y <- c * (Einv .* y0) for the QPs of the launch (KernelArgs::sel: the addressed slots,
+// input row = position in the caller's list; null: every QP, row = QP id).  x and z are left alone.
+__global__ void warm_start_y_kernel(KernelArgs a, const double *__restrict__ y0, int nslots, int BT) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int m = a.m;
+  if (g >= (size_t)nslots * m) return;
+  const int slot = (int)(g / m), i = (int)(g % m);
+  const int row = a.sel ? a.sel[slot] - 1 : (slot < a.B ? slot : -1);
+  if (row < 0) return;
+  const size_t tile = (size_t)(slot / BT), b = (size_t)(slot % BT);
+  const size_t e = (tile * m + i) * BT + b;
+  double v = y0[(size_t)row * m + i];
+  if (a.scaling) { v *= a.Esc_inv[e]; v *= a.dscal[(tile * DS_COUNT + DS_C) * BT + b]; }
+  a.y[e] = v;
+}
+
 // ---- row E2 on the device: Ruiz equilibration of [[P, A'],[A, 0]] + cost normalisation after new A values ------------
 // One workgroup per QP.  Same operations in the same order as host_core.cpp unscale_qp / scale_qp (and the oracle):
 // infinity norms are maxima (exact in any order: atomic max on the bit patterns of non-negative doubles), every product is a
@@ -3036,25 +3070,38 @@ __global__ __launch_bounds__(512) void ruiz_kernel(RuizArgs a) {
   auto H = [&](size_t len, size_t i) { return (tile * len + i) * BT + b; };
   double *dn = a.dn + (size_t)qp * n, *en = a.en + (size_t)qp * m;
   const int jr = a.raw_by_qp ? qp : jq;          // row of the raw A / bounds arguments
-  const double *rawA = a.rawA + (size_t)jr * nnzA;
+  const double *rawA = a.rawA ? a.rawA + (size_t)jr * nnzA : nullptr;
   // (dn / en are updated by atomics, which execute in L2: they are read and reset past the CU's L1 as well)
   auto ld = [](const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
   auto st0 = [](double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
   double c = a.dscal[H(DS_COUNT, DS_C)];
   const double cinv0 = a.dscal[H(DS_COUNT, DS_CINV)];
-  // ---- unscale P and q with the scaling in force; A is replaced; the bounds are replaced or unscaled
+  // ---- unscale P and q with the scaling in force (or take new P values); A is replaced or unscaled; the bounds are
+  // replaced or unscaled
   if (a.fresh) {       // the QP as setup sees it: P and q as given then
     for (int k = tid; k < nnzP; k += nthr) a.pa_val[H(pa_len, k)] = a.rawP[(size_t)qp * nnzP + k];
     for (int j = tid; j < n; j += nthr) a.q[H(n, j)] = a.rawq[(size_t)qp * n + j];
   } else {
-    for (int k = tid; k < nnzP; k += nthr) {
-      double v = a.pa_val[H(pa_len, k)];
-      v *= cinv0; v *= a.Dsc_inv[H(n, a.Prow[k])]; v *= a.Dsc_inv[H(n, a.Pcol[k])];
-      a.pa_val[H(pa_len, k)] = v;
+    if (a.rawPnew) {
+      for (int k = tid; k < nnzP; k += nthr) a.pa_val[H(pa_len, k)] = a.rawPnew[(size_t)jr * nnzP + k];
+    } else {
+      for (int k = tid; k < nnzP; k += nthr) {
+        double v = a.pa_val[H(pa_len, k)];
+        v *= cinv0; v *= a.Dsc_inv[H(n, a.Prow[k])]; v *= a.Dsc_inv[H(n, a.Pcol[k])];
+        a.pa_val[H(pa_len, k)] = v;
+      }
     }
     for (int j = tid; j < n; j += nthr) a.q[H(n, j)] *= cinv0 * a.Dsc_inv[H(n, j)];
   }
-  for (int k = tid; k < nnzA; k += nthr) a.pa_val[H(pa_len, nnzP + k)] = rawA[k];
+  if (rawA) {
+    for (int k = tid; k < nnzA; k += nthr) a.pa_val[H(pa_len, nnzP + k)] = rawA[k];
+  } else {
+    for (int k = tid; k < nnzA; k += nthr) {
+      double v = a.pa_val[H(pa_len, nnzP + k)];
+      v *= a.Esc_inv[H(m, a.Arow[k])]; v *= a.Dsc_inv[H(n, a.Acol[k])];
+      a.pa_val[H(pa_len, nnzP + k)] = v;
+    }
+  }
   for (int i = tid; i < m; i += nthr) {
     double lo, up;
     if (a.rawl) { lo = fmax(a.rawl[(size_t)jr * m + i], -MI_INFTY); up = fmin(a.rawu[(size_t)jr * m + i], MI_INFTY); }
@@ -3151,7 +3198,7 @@ __global__ __launch_bounds__(512) void ruiz_reg_kernel(RuizArgs a) {
   auto H = [&](size_t len, size_t i) { return (tile * len + i) * BT + b; };
   double *nv = rz_lds;
   const int jr = a.raw_by_qp ? qp : jq;
-  const double *rawA = a.rawA + (size_t)jr * nnzA;
+  const double *rawA = a.rawA ? a.rawA + (size_t)jr * nnzA : nullptr;
   auto amax = [](double *p, double v) { atomicMax(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v)); };
   double c = a.dscal[H(DS_COUNT, DS_C)];
   const double cinv0 = a.dscal[H(DS_COUNT, DS_CINV)];
@@ -3166,10 +3213,13 @@ __global__ __launch_bounds__(512) void ruiz_reg_kernel(RuizArgs a) {
       const int r = a.Prow[k], cc = a.Pcol[k];
       sl = ((unsigned)r << 16) | (unsigned)cc;
       if (a.fresh) x = a.rawP[(size_t)qp * nnzP + k];
+      else if (a.rawPnew) x = a.rawPnew[(size_t)jr * nnzP + k];
       else { x = a.pa_val[H(pa_len, k)]; x *= cinv0; x *= a.Dsc_inv[H(n, r)]; x *= a.Dsc_inv[H(n, cc)]; }
     } else if (k < pa_len) {
-      sl = ((unsigned)(n + a.Arow[k - nnzP]) << 16) | (unsigned)a.Acol[k - nnzP];
-      x = rawA[k - nnzP];
+      const int r = a.Arow[k - nnzP], cc = a.Acol[k - nnzP];
+      sl = ((unsigned)(n + r) << 16) | (unsigned)cc;
+      if (rawA) x = rawA[k - nnzP];
+      else { x = a.pa_val[H(pa_len, k)]; x *= a.Esc_inv[H(m, r)]; x *= a.Dsc_inv[H(n, cc)]; }
     }
     v[i] = x; slot[i] = sl;
   }
@@ -3604,6 +3654,17 @@ hipError_t launch_bounds(const double *gl, const double *gu, double *l, double *
                          int scaling, hipStream_t st) {
   if (!m) return hipSuccess;
   hipLaunchKernelGGL(bounds_kernel, dim3(nblk((size_t)B * m, 256)), dim3(256), 0, st, gl, gu, l, u, Esc, rho_vec, dscal, changed, B, m, BT, scaling);
+  return hipGetLastError();
+}
+hipError_t launch_lin_cost(const double *gq, const int *ids, double *q, double *rawq, const double *Dsc, const double *dscal,
+                           int nq, int n, int BT, int scaling, hipStream_t st) {
+  if (!nq || !n) return hipSuccess;
+  hipLaunchKernelGGL(lin_cost_kernel, dim3(nblk((size_t)nq * n, 256)), dim3(256), 0, st, gq, ids, q, rawq, Dsc, dscal, nq, n, BT, scaling);
+  return hipGetLastError();
+}
+hipError_t launch_warm_start_y(const KernelArgs &a, int nslots, int BT, hipStream_t st, const double *y0) {
+  if (!nslots || !a.m) return hipSuccess;
+  hipLaunchKernelGGL(warm_start_y_kernel, dim3(nblk((size_t)nslots * a.m, 256)), dim3(256), 0, st, a, y0, nslots, BT);
   return hipGetLastError();
 }
 

@@ -1937,6 +1937,181 @@ int mi_osqp_batch_refactor_device(mi_osqp_batch *h) {
   return refactor_qps(h, std::move(all));
 }
 
+// ------------------------------------------------------------------ objective updates
+// osqp_update_lin_cost / osqp_update_P / osqp_update_P_A / osqp_warm_start_y (OSQP 0.6.x semantics, README "Objective updates").
+
+// triu(P) of a P given in the form setup accepts (both triangles or the upper one), extracted as analyze() does: src[t] =
+// position in the caller's value array of the t-th entry of the analysis's triu(P).  false: the pattern differs.
+static bool triu_sources(const Analysis &an, const int64_t *Pp, const int64_t *Pi, std::vector<int64_t> &src) {
+  const int n = an.n;
+  src.clear();
+  src.reserve((size_t)an.Pp[n]);
+  if (Pp[0] != 0) return false;
+  for (int j = 0; j < n; j++) {
+    for (int64_t k = Pp[j]; k < Pp[j + 1]; k++)
+      if (Pi[k] <= j) {
+        const size_t t = src.size();
+        if ((int64_t)t >= an.Pp[j + 1] || Pi[k] != an.Pi[t]) return false;
+        src.push_back(k);
+      }
+    if ((int64_t)src.size() != an.Pp[j + 1]) return false;
+  }
+  return true;
+}
+static bool same_A_pattern(const Analysis &an, const int64_t *Ap, const int64_t *Ai) {
+  for (int j = 0; j <= an.n; j++) if (Ap[j] != an.Ap[j]) return false;
+  for (int k = 0; k < an.Ap[an.n]; k++) if (Ai[k] != an.Ai[k]) return false;
+  return true;
+}
+
+// q -> h->q (scaled with the D and c in force) and rawq, on `s`; the host mirrors follow (q_host) or are marked stale
+static int update_q_impl(mi_osqp_batch *h, const double *q_host, const double *d_q, hipStream_t s) {
+  const Analysis &an = (*h->anp);
+  const int n = an.n, B = h->B;
+  const size_t cnt = (size_t)B * n;
+  h->clear_rho_updates = true;
+  int rc;
+  if (q_host) {
+    if ((rc = ensure_stage(h, cnt, 0)) || (rc = ensure_pin(h, cnt))) return rc;
+    const size_t slice = (size_t)1 << 19;          // 4 MB slices, as mi_osqp_batch_update_bounds
+    for (size_t o = 0; o < cnt; o += slice) {
+      const size_t len = std::min(slice, cnt - o);
+      par_copy(h->pin + o, q_host + o, len);
+      HIPCHK(hipMemcpyAsync(h->stage.p + o, h->pin + o, len * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    d_q = h->stage.p;
+  }
+  HIPCHK(launch_lin_cost(d_q, nullptr, h->q.p, h->rawq.p, h->Dsc.p, h->dscal.p, B, n, h->BT, h->st.scaling ? 1 : 0, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (h->host_scaling_stale) return MI_OSQP_OK;       // (the mirrors are fetched whole when a host path needs them)
+  if (!q_host) { h->host_scaling_stale = true; return MI_OSQP_OK; }
+  parallel_for(B, [&](int qi, int) {
+    QPNumeric &Q = h->qp[qi];
+    for (int j = 0; j < n; j++) {
+      double v = q_host[(size_t)qi * n + j];
+      if (h->st.scaling) { v *= Q.D[j]; v *= Q.c; }
+      Q.q[j] = v;
+    }
+  });
+  return MI_OSQP_OK;
+}
+
+// New values of triu(P) (and of A when Av != null): unscale with the scaling in force, replace, equilibrate again from
+// P, q and A, rescale the bounds, refactor every QP with its current rho vectors, snapshot - as mi_osqp_batch_update_A
+// does for A.  src: triu_sources() of the caller's P.
+static int update_P_impl(mi_osqp_batch *h, const std::vector<int64_t> &src, int64_t nnzPin, const double *Pv, const double *Av) {
+  const Analysis &an = (*h->anp);
+  const int n = an.n, B = h->B, nnzP = an.Pp[n], nnzA = an.Ap[n], pa_len = nnzP + nnzA;
+  h->clear_rho_updates = true;
+  int rc;
+  const size_t cP = (size_t)B * nnzP, cA = Av ? (size_t)B * nnzA : 0, cpa = (size_t)B * pa_len;
+  if ((rc = ensure_pin(h, cP + cA + 1)) || (rc = ensure_stage(h, cP + cA + cpa + 1, (size_t)B))) return rc;
+  // the new triu(P) of every QP, QP-major in the analysis's order (what rawP keeps)
+  parallel_for(B, [&](int qi, int) {
+    double *dst = h->pin + (size_t)qi * nnzP;
+    const double *sv = Pv + (size_t)qi * nnzPin;
+    for (int t = 0; t < nnzP; t++) dst[t] = sv[src[t]];
+  });
+  if (Av) par_copy(h->pin + cP, Av, cA);
+  if (cP + cA) HIPCHK(hipMemcpyAsync(h->stage.p, h->pin, (cP + cA) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (cP) HIPCHK(hipMemcpyAsync(h->rawP.p, h->stage.p, cP * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  std::vector<int> all(B);
+  for (int i = 0; i < B; i++) all[i] = i;
+  if (!host_ruiz(h)) {
+    RuizArgs r{};
+    r.n = n; r.m = an.m; r.nnzP = nnzP; r.nnzA = nnzA; r.B = B; r.BT = h->BT; r.iters = (int)h->st.scaling;
+    r.Prow = h->rz_prow.p; r.Pcol = h->rz_pcol.p; r.Arow = h->rz_arow.p; r.Acol = h->rz_acol.p;
+    r.rawPnew = h->stage.p; r.rawA = Av ? h->stage.p + cP : nullptr; r.rawl = r.rawu = nullptr;
+    r.pa_val = h->pa_val.p; r.q = h->q.p; r.Dsc = h->Dsc.p; r.Dsc_inv = h->Dsc_inv.p; r.Esc = h->Esc.p; r.Esc_inv = h->Esc_inv.p;
+    r.l = h->l.p; r.u = h->u.p; r.dscal = h->dscal.p;
+    r.dn = h->out1.p; r.en = h->out1.p + (size_t)B * n;              // (scratch of check_kernel: (2n + m) doubles per QP)
+    r.pa_out = h->stage.p + cP + cA;
+    HIPCHK(launch_ruiz(r, h->stream));
+    HIPCHK(hipMemcpyAsync(h->ids.p, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(launch_scatter(r.pa_out, h->chk_val.p, h->chk.src.p, h->ids.p, B, pa_len, h->chk.view(an.chk), h->BT, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->host_scaling_stale = true; h->host_bounds_stale = true; h->host_rho_stale = true;
+  } else {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = ensure_mirrors(h)) || (rc = sync_bounds_to_host(h)) || (rc = sync_rho_to_host(h))) return rc;
+    const int CH = 128;
+    for (int c0 = 0; c0 < B; c0 += CH) {
+      const int c1 = std::min(B, c0 + CH);
+      parallel_for(c1 - c0, [&](int k, int) {
+        const int qi = c0 + k;
+        QPNumeric &Q = h->qp[qi];
+        if (h->st.scaling) unscale_qp(an, Q);
+        const double *sv = Pv + (size_t)qi * nnzPin;
+        for (int t = 0; t < nnzP; t++) Q.Pv[t] = sv[src[t]];
+        if (Av) std::copy(Av + (size_t)qi * nnzA, Av + (size_t)(qi + 1) * nnzA, Q.Av.begin());
+        if (h->st.scaling) scale_qp(an, h->st, Q);
+      });
+      std::vector<int> ids(all.begin() + c0, all.begin() + c1);
+      if ((rc = upload_problem(h, ids, true)) || (rc = sync_scalars_to_device(h, ids, true))) return rc;
+    }
+  }
+  if ((rc = refactor_qps(h, std::move(all)))) return rc;          // (the rho vectors in force; factor_kernel re-derives them from the bounds)
+  return snapshot(h);
+}
+
+static int update_P_checked(mi_osqp_batch *h, const int64_t *Pp, const int64_t *Pi, const double *Pv,
+                            const int64_t *Ap, const int64_t *Ai, const double *Av) {
+  DevGuard guard(h->device);
+  { const int rc_ = cont_leave(h); if (rc_) return rc_; }
+  const Analysis &an = (*h->anp);
+  std::vector<int64_t> src;
+  if (!triu_sources(an, Pp, Pi, src)) return MI_OSQP_ERR_PATTERN_CHANGED;
+  if (Av && !same_A_pattern(an, Ap, Ai)) return MI_OSQP_ERR_PATTERN_CHANGED;
+  return update_P_impl(h, src, Pp[an.n], Pv, Av);
+}
+
+int mi_osqp_batch_update_q(mi_osqp_batch *h, const double *q) {
+  CallTimer timer_("batch_update_q");
+  if (!h || !q) return MI_OSQP_ERR_NULL;
+  DevGuard guard(h->device);
+  { const int rc_ = cont_leave(h); if (rc_) return rc_; }
+  return update_q_impl(h, q, nullptr, h->stream);
+}
+
+int mi_osqp_batch_update_q_device(mi_osqp_batch *h, const double *d_q, void *stream) {
+  CallTimer timer_("batch_update_q_device");
+  if (!h || !d_q) return MI_OSQP_ERR_NULL;
+  DevGuard guard(h->device);
+  { const int rc_ = cont_leave(h); if (rc_) return rc_; }
+  return update_q_impl(h, nullptr, d_q, stream ? (hipStream_t)stream : h->stream);
+}
+
+int mi_osqp_batch_update_P(mi_osqp_batch *h, const int64_t *Pp, const int64_t *Pi, const double *Pv) {
+  CallTimer timer_("batch_update_P");
+  if (!h || !Pp || !Pi || !Pv) return MI_OSQP_ERR_NULL;
+  return update_P_checked(h, Pp, Pi, Pv, nullptr, nullptr, nullptr);
+}
+
+int mi_osqp_batch_update_P_A(mi_osqp_batch *h, const int64_t *Pp, const int64_t *Pi, const double *Pv,
+                             const int64_t *Ap, const int64_t *Ai, const double *Av) {
+  CallTimer timer_("batch_update_P_A");
+  if (!h || !Pp || !Pi || !Pv || !Ap || !Ai || !Av) return MI_OSQP_ERR_NULL;
+  return update_P_checked(h, Pp, Pi, Pv, Ap, Ai, Av);
+}
+
+int mi_osqp_batch_warm_start_y(mi_osqp_batch *h, const double *y) {
+  CallTimer timer_("batch_warm_start_y");
+  if (!h || !y) return MI_OSQP_ERR_NULL;
+  DevGuard guard(h->device);
+  { const int rc_ = cont_leave(h); if (rc_) return rc_; }
+  h->st.warm_start = 1;
+  const size_t cnt = (size_t)h->B * (*h->anp).m;
+  if (!cnt) return MI_OSQP_OK;
+  int rc;
+  if ((rc = ensure_stage(h, cnt, 0)) || (rc = ensure_pin(h, cnt))) return rc;
+  par_copy(h->pin, y, cnt);
+  HIPCHK(hipMemcpyAsync(h->stage.p, h->pin, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  KernelArgs a = make_args(h);
+  HIPCHK(launch_warm_start_y(a, h->ntiles * h->BT, h->BT, h->stream, h->stage.p));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return MI_OSQP_OK;
+}
+
 int mi_osqp_batch_spmv(mi_osqp_batch *h, const double *d_x, const double *d_y, double *d_Px, double *d_Aty, double *d_Ax,
                        void *stream) {
   if (!h) return MI_OSQP_ERR_NULL;
@@ -2301,6 +2476,51 @@ int mi_osqp_batch_warm_start_x_some(mi_osqp_batch *h, int64_t n_ids, const int64
   return MI_OSQP_OK;
 }
 
+// osqp_update_lin_cost for the listed (idle) QPs: ring upload, lin_cost_kernel, nothing waits
+int mi_osqp_batch_update_q_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *q) {
+  CallTimer timer_("batch_update_q_some");
+  if (!h || (n_ids > 0 && !q)) return MI_OSQP_ERR_NULL;
+  DevGuard guard(h->device);
+  int rc;
+  if ((rc = cont_enter(h)) || (rc = cont_check_ids(h, n_ids, ids, true))) return rc;
+  if (!n_ids) return MI_OSQP_OK;
+  const int n = (*h->anp).n;
+  const size_t cnt = (size_t)n_ids * n;
+  int *d_ids = nullptr;
+  RingSpan sp;
+  if ((rc = ring_reserve(h, (size_t)n_ids * sizeof(int) + cnt * sizeof(double), 2))) return rc;
+  if ((rc = cont_stage_ids(h, n_ids, ids, &d_ids, nullptr)) || (rc = ring_take(h, cnt * sizeof(double), sp))) return rc;
+  memcpy(sp.host, q, cnt * sizeof(double));
+  if ((rc = ring_upload(h, sp, cnt * sizeof(double)))) return rc;
+  HIPCHK(launch_lin_cost((const double *)sp.dev, d_ids, h->q.p, h->rawq.p, h->Dsc.p, h->dscal.p, (int)n_ids, n, h->BT,
+                         h->st.scaling ? 1 : 0, h->stream));
+  for (int64_t j = 0; j < n_ids; j++) h->cont.clear_rho[(size_t)ids[j]] = 1;
+  h->host_scaling_stale = true;
+  return MI_OSQP_OK;
+}
+
+// osqp_warm_start_y for the listed (idle) QPs
+int mi_osqp_batch_warm_start_y_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *y) {
+  CallTimer timer_("batch_warm_start_y_some");
+  if (!h || (n_ids > 0 && !y)) return MI_OSQP_ERR_NULL;
+  DevGuard guard(h->device);
+  int rc;
+  if ((rc = cont_enter(h)) || (rc = cont_check_ids(h, n_ids, ids, true))) return rc;
+  if (!n_ids) return MI_OSQP_OK;
+  h->st.warm_start = 1;
+  const size_t cnt = (size_t)n_ids * (*h->anp).m;
+  int *d_ids = nullptr, *d_sel = nullptr;
+  RingSpan sp;
+  if ((rc = ring_reserve(h, ((size_t)n_ids + (size_t)h->ntiles * h->BT) * sizeof(int) + cnt * sizeof(double), 2))) return rc;
+  if ((rc = cont_stage_ids(h, n_ids, ids, &d_ids, &d_sel)) || (rc = ring_take(h, std::max<size_t>(cnt, 1) * sizeof(double), sp))) return rc;
+  memcpy(sp.host, y, cnt * sizeof(double));
+  if ((rc = ring_upload(h, sp, cnt * sizeof(double)))) return rc;
+  KernelArgs a = make_args(h);
+  a.sel = d_sel;
+  HIPCHK(launch_warm_start_y(a, h->ntiles * h->BT, h->BT, h->stream, (const double *)sp.dev));
+  return MI_OSQP_OK;
+}
+
 int mi_osqp_batch_solve_begin_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids) {
   CallTimer timer_("batch_solve_begin_some");
   if (!h) return MI_OSQP_ERR_NULL;
@@ -2656,6 +2876,15 @@ int mi_osqp_update_bounds(mi_osqp_solver *h, const double *l, const double *u) {
   return h ? mi_osqp_batch_update_bounds(h->b, l, u) : MI_OSQP_ERR_NULL;
 }
 int mi_osqp_warm_start_x(mi_osqp_solver *h, const double *x) { return h ? mi_osqp_batch_warm_start_x(h->b, x) : MI_OSQP_ERR_NULL; }
+int mi_osqp_update_q(mi_osqp_solver *h, const double *q) { return h ? mi_osqp_batch_update_q(h->b, q) : MI_OSQP_ERR_NULL; }
+int mi_osqp_update_P(mi_osqp_solver *h, const int64_t *Pp, const int64_t *Pi, const double *Pv) {
+  return h ? mi_osqp_batch_update_P(h->b, Pp, Pi, Pv) : MI_OSQP_ERR_NULL;
+}
+int mi_osqp_update_P_A(mi_osqp_solver *h, const int64_t *Pp, const int64_t *Pi, const double *Pv, const int64_t *Ap, const int64_t *Ai,
+                       const double *Av) {
+  return h ? mi_osqp_batch_update_P_A(h->b, Pp, Pi, Pv, Ap, Ai, Av) : MI_OSQP_ERR_NULL;
+}
+int mi_osqp_warm_start_y(mi_osqp_solver *h, const double *y) { return h ? mi_osqp_batch_warm_start_y(h->b, y) : MI_OSQP_ERR_NULL; }
 int mi_osqp_solve(mi_osqp_solver *h, mi_osqp_info *info) {
   if (!h) return MI_OSQP_ERR_NULL;
   int rc = mi_osqp_batch_solve(h->b);
@@ -2815,6 +3044,27 @@ int mi_osqp_multi_batch_update_A_bounds(mi_osqp_multi *h, const int64_t *Ap, con
 int mi_osqp_multi_batch_warm_start_x(mi_osqp_multi *h, const double *x) {
   if (!h || !x) return MI_OSQP_ERR_NULL;
   return multi_fan_out(h, [&](size_t k) { return mi_osqp_batch_warm_start_x(h->shard[k], x + h->begin[k] * h->n); });
+}
+int mi_osqp_multi_batch_update_q(mi_osqp_multi *h, const double *q) {
+  if (!h || !q) return MI_OSQP_ERR_NULL;
+  return multi_fan_out(h, [&](size_t k) { return mi_osqp_batch_update_q(h->shard[k], q + h->begin[k] * h->n); });
+}
+int mi_osqp_multi_batch_update_P(mi_osqp_multi *h, const int64_t *Pp, const int64_t *Pi, const double *Pv) {
+  if (!h || !Pp || !Pi || !Pv) return MI_OSQP_ERR_NULL;
+  const int64_t nnzP = Pp[h->n];
+  return multi_fan_out(h, [&](size_t k) { return mi_osqp_batch_update_P(h->shard[k], Pp, Pi, Pv + h->begin[k] * nnzP); });
+}
+int mi_osqp_multi_batch_update_P_A(mi_osqp_multi *h, const int64_t *Pp, const int64_t *Pi, const double *Pv, const int64_t *Ap,
+                                   const int64_t *Ai, const double *Av) {
+  if (!h || !Pp || !Pi || !Pv || !Ap || !Ai || !Av) return MI_OSQP_ERR_NULL;
+  const int64_t nnzP = Pp[h->n], nnzA = Ap[h->n];
+  return multi_fan_out(h, [&](size_t k) {
+    return mi_osqp_batch_update_P_A(h->shard[k], Pp, Pi, Pv + h->begin[k] * nnzP, Ap, Ai, Av + h->begin[k] * nnzA);
+  });
+}
+int mi_osqp_multi_batch_warm_start_y(mi_osqp_multi *h, const double *y) {
+  if (!h || !y) return MI_OSQP_ERR_NULL;
+  return multi_fan_out(h, [&](size_t k) { return mi_osqp_batch_warm_start_y(h->shard[k], y + h->begin[k] * h->m); });
 }
 int mi_osqp_multi_batch_solve(mi_osqp_multi *h) {
   if (!h) return MI_OSQP_ERR_NULL;
