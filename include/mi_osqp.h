@@ -395,6 +395,10 @@ int mi_osqp_batch_refactor_time(mi_osqp_batch *h, double *factor_ms, double *tai
  * durations of factor_kernel and of the dense-tail kernels (tail_assemble_kernel + tail_kernel). Reset by refactor_time. */
 int mi_osqp_batch_refactor_peak(mi_osqp_batch *h, int64_t *qps, double *factor_ms, double *tail_ms);
 
+/* The Ruiz scaling in force (all ones with scaling = 0), read from the device copies the kernels use: the scaled problem is
+ * c D P D, c D q, E A D, E l, E u.  Ends the continuous mode like mi_osqp_batch_get_primal. */
+int mi_osqp_batch_get_scaling(mi_osqp_batch *h, double *D /*[B][n]*/, double *E /*[B][m]*/, double *c /*[B]*/);
+
 /* --------------------------------------------------- host-only diagnostics
  * No GPU needed: analyse a pattern + one value set and replay the DEVICE
  * schedules on the host (a sequential interpreter of the same task tables) so

@@ -74,6 +74,7 @@ def _bind(lib):
     lib.oq_solve.argtypes = [C.c_void_p]
     lib.oq_get_solution.argtypes = [C.c_void_p, dp, dp]
     lib.oq_get_info.argtypes = [C.c_void_p, C.POINTER(Info)]
+    lib.oq_get_scaling.argtypes = [C.c_void_p, dp, dp, dp]
     lib.oq_update_A.restype = C.c_longlong
     lib.oq_update_A.argtypes = [C.c_void_p, ip, ip, dp]
     lib.oq_update_bounds.restype = C.c_longlong
@@ -179,6 +180,11 @@ class OracleQPSolver:
 
     def info(self):
         i = Info(); self._L.oq_get_info(self._h, C.byref(i)); return i
+
+    def scaling(self):
+        """Ruiz scaling in force: (D [n], E [m], c)."""
+        D, E, c = np.empty(self.n), np.empty(self.m), C.c_double()
+        self._L.oq_get_scaling(self._h, _dp(D), _dp(E), C.byref(c)); return D, E, c.value
 
     def update(self, l, A, u):
         import scipy.sparse as sp

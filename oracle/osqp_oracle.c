@@ -935,6 +935,11 @@ void oq_get_solution(const oq_work *w, oq_float *x, oq_float *y) {
   if (y) memcpy(y, w->sol_y, (size_t)w->m * sizeof(oq_float));
 }
 void oq_get_info(const oq_work *w, oq_info *info) { *info = w->info; info->rho = w->settings.rho; }
+void oq_get_scaling(const oq_work *w, oq_float *D, oq_float *E, oq_float *c) {
+  memcpy(D, w->D, (size_t)w->n * sizeof(oq_float));
+  if (w->m) memcpy(E, w->E, (size_t)w->m * sizeof(oq_float));
+  *c = w->c;
+}
 
 /* --------------------------------------------------------- updates R3, R4 */
 

@@ -111,6 +111,8 @@ oq_int oq_solve(oq_work *w);
  * when the status carries no solution. */
 void oq_get_solution(const oq_work *w, oq_float *x, oq_float *y);
 void oq_get_info(const oq_work *w, oq_info *info);
+/* the Ruiz scaling in force: D[n], E[m], c (all ones with scaling = 0) */
+void oq_get_scaling(const oq_work *w, oq_float *D, oq_float *E, oq_float *c);
 
 /* UpdateConstraintMatrix ([REF] src/osqp-wrapper.h:36): same pattern, new
  * values.  Ap/Ai are compared with the stored pattern; mismatch -> 1. */

@@ -119,6 +119,7 @@ def lib():
         L.mi_osqp_batch_last_solve_stats.argtypes = [vp, ip, ip, dp, dp, ip, dp]
         L.mi_osqp_batch_last_polish_stats.argtypes = [vp, ip, ip, dp]
         L.mi_osqp_batch_get_polish_active.argtypes = [vp, C.POINTER(C.c_int8)]
+        L.mi_osqp_batch_get_scaling.argtypes = [vp, dp, dp, dp]
         L.mi_osqp_batch_spmv.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.mi_osqp_batch_kkt_solve.argtypes = [vp, vp, vp, vp]
         L.mi_osqp_batch_kernel_time.argtypes = [vp, dp, ip]
@@ -381,6 +382,12 @@ class BatchSolver:
         act = np.zeros((self.B, self.m), dtype=np.int8)
         _chk(lib().mi_osqp_batch_get_polish_active(self._h, act.ctypes.data_as(C.POINTER(C.c_int8))), "get_polish_active")
         return act
+
+    def scaling(self):
+        """Ruiz scaling in force, read from the device: (D [B, n], E [B, m], c [B]); all ones with scaling = 0."""
+        D, E, c = np.empty((self.B, self.n)), np.empty((self.B, self.m)), np.empty(self.B)
+        _chk(lib().mi_osqp_batch_get_scaling(self._h, _dp(D), _dp(E), _dp(c)), "get_scaling")
+        return D, E, c
 
     def kernel_time(self):
         ms, cnt = C.c_double(), C.c_int64()

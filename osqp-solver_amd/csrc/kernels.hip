@@ -1367,7 +1367,8 @@ __global__ __launch_bounds__(512) void spmv_fused_kernel(KernelArgs a, SpmvFused
 #pragma unroll
       for (int k = 0; k < KMAX; k++) w[p][k] = (p < t.n_pass && (uint32_t)k < t.ell_k[p]) ? t.ell[t.ell_off[p] + (uint32_t)k * 512u + (uint32_t)tid] : 0u;
     }
-    vals[(size_t)len * BT + (tid % BT)] = 0.0;        // the zero the padding entries point at
+    vals[(size_t)len * BT + (tid % BT)] = 0.0;        // the zeros the padding entries point at (value and vector slot)
+    xs[((size_t)n + m) * BT + (tid % BT)] = 0.0;
     __syncthreads();
 #pragma unroll
     for (int p = 0; p < PMAX; p++) {
@@ -1428,7 +1429,7 @@ __global__ __launch_bounds__(512) void spmv_fused_qp_kernel(KernelArgs a, SpmvFu
 #pragma unroll
     for (int k = 0; k < KMAX; k++) w[p][k] = (p < t.n_pass && (uint32_t)k < t.ell_k[p]) ? t.ell[t.ell_off[p] + (uint32_t)k * 512u + (uint32_t)tid] : 0u;
   }
-  if (tid == 0) vals[len] = 0.0;
+  if (tid == 0) { vals[len] = 0.0; xs[n + m] = 0.0; }
   __syncthreads();
 #pragma unroll
   for (int p = 0; p < PMAX; p++) {
@@ -1446,7 +1447,8 @@ __global__ __launch_bounds__(512) void spmv_fused_qp_kernel(KernelArgs a, SpmvFu
     else if (gAx) gAx[(size_t)q * m + (r - 2 * n)] = acc;
   }
 }
-size_t spmv_fused_lds_bytes(int n, int m, int pa_len, int BT) { return ((size_t)pa_len + 1 + n + m) * BT * sizeof(double); }
+// values + their zero, [x ; y] + its zero slot (the target of the ELL padding), per QP of the tile
+size_t spmv_fused_lds_bytes(int n, int m, int pa_len, int BT) { return ((size_t)pa_len + 1 + n + m + 1) * BT * sizeof(double); }
 hipError_t launch_spmv_fused(const KernelArgs &a, const SpmvFused &t, int BT, int tiles, int n_cus, hipStream_t st,
                              const double *x, const double *y, double *Px, double *Aty, double *Ax) {
   (void)n_cus;

@@ -953,7 +953,8 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
       std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return rows[x].size() > rows[y].size(); });
       const int npass = (int)((nrows + 511) / 512);
       std::vector<uint32_t> ell, rowid((size_t)npass * 512, 0xFFFFFFFFu);
-      const uint32_t pad = (uint32_t)(an.Pp[n] + an.Ap[n]);          // value position of the zero, vector index 0
+      // value position of the zero, vector index of the zero slot past [x ; y] (a padding entry must not read x[0]: 0 * inf)
+      const uint32_t pad = (uint32_t)(an.Pp[n] + an.Ap[n]) | ((uint32_t)(n + m) << 16);
       for (int p = 0; p < npass; p++) {
         const size_t r0 = (size_t)p * 512, r1 = std::min(nrows, r0 + 512);
         const uint32_t K = (uint32_t)rows[order[r0]].size();
@@ -1536,6 +1537,29 @@ int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act) {
   if (!h->pol_act.p) { memset(act, 0, cnt); return MI_OSQP_OK; }
   DevGuard guard(h->device);
   if (cnt) HIPCHK(hipMemcpy(act, h->pol_act.p, cnt, hipMemcpyDeviceToHost));
+  return MI_OSQP_OK;
+}
+
+// The scaling the kernels use: the device copies Dsc, Esc and DS_C of dscal, out of the tile layout (the host mirrors
+// h->qp[q] lag behind after a device equilibration).
+int mi_osqp_batch_get_scaling(mi_osqp_batch *h, double *D, double *E, double *c) {
+  if (!h || !D || !E || !c) return MI_OSQP_ERR_NULL;
+  DevGuard guard(h->device);
+  { const int rc_ = cont_leave(h); if (rc_) return rc_; }
+  const int n = (*h->anp).n, m = (*h->anp).m, B = h->B, BT = h->BT;
+  int rc;
+  if ((rc = ensure_stage(h, (size_t)B * std::max({n, m, 1}) + 1, 0))) return rc;
+  auto down = [&](const double *src, int len, double *dst) -> int {
+    if (!len) return 0;
+    HIPCHK(launch_deinterleave(src, h->stage.p, B, len, BT, h->stream));
+    HIPCHK(hipMemcpyAsync(dst, h->stage.p, (size_t)B * len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  };
+  if ((rc = down(h->Dsc.p, n, D)) || (rc = down(h->Esc.p, m, E))) return rc;
+  const size_t dcnt = (size_t)h->ntiles * DS_COUNT * BT;
+  HIPCHK(hipMemcpy(h->h_dscal, h->dscal.p, dcnt * sizeof(double), hipMemcpyDeviceToHost));
+  for (int q = 0; q < B; q++) c[q] = h->h_dscal[(size_t)(q / BT) * DS_COUNT * BT + DS_C * BT + q % BT];
   return MI_OSQP_OK;
 }
 
