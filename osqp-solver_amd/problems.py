@@ -111,6 +111,21 @@ def grid_qp(g, seed=7):
     return dict(n=n, m=m, P=P, A=A, Px=P.data[None].copy(), Ax=A.data[None].copy(), q=q[None], l=l[None], u=u[None])
 
 
+def make_dual_infeasible(prob, b, push=1.0):
+    """QP b of a batch dict becomes dual infeasible (unbounded below) along d = -e_0, in place and on the SAME pattern:
+    every stored entry of row 0 and of column 0 of P is set to 0.0 and stays an entry of Px (P d = 0; the rest of P is a
+    principal submatrix of a positive definite matrix: still positive semidefinite), q[0] = push > 0 (q'd < 0), and every
+    row of A that holds column 0 becomes free (l = -INF, u = INF), so A d vanishes wherever a bound is finite."""
+    assert push > 0
+    P, A = prob["P"], prob["A"]
+    pcols = np.repeat(np.arange(P.shape[1]), np.diff(P.indptr))
+    prob["Px"][b, (P.indices == 0) | (pcols == 0)] = 0.0
+    prob["q"][b, 0] = push
+    rows = A.indices[A.indptr[0]:A.indptr[1]]
+    prob["l"][b, rows] = -INF
+    prob["u"][b, rows] = INF
+
+
 def qp_matrices(prob, b):
     """scipy matrices (P upper triangle, A) of QP b of a batch dict."""
     P = prob["P"].copy(); P.data = prob["Px"][b].copy()

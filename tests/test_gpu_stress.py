@@ -2,7 +2,12 @@
 scripts/stress_random.py (shapes, tilings, thread counts, LDS / global solve vector) and
 scripts/stress_settings.py (solver settings and call sequences) exit non-zero on any mismatch in exit code,
 iteration count, number of rho updates or x; scripts/stress_dense_tail.py does the same for the dense tail under bad
-conditioning (nearly-LP objectives, equality and free rows, tight tolerances; chosen and forced tails)."""
+conditioning (nearly-LP objectives, equality and free rows, tight tolerances; chosen and forced tails).
+
+Exit codes: the "infeasible" and "unbounded" kinds of stress_settings.py put primal and dual infeasible QPs (the
+families of tests/exit_cases.py) next to feasible ones under random settings, and its low max_iter draws reach the
+inaccurate codes by chance; the sweep prints the QPs per exit code.  The tests that expect each code 0-6 by construction,
+on every launch form, are in tests/test_gpu_exit_codes.py."""
 import os
 import subprocess
 import sys
