@@ -108,6 +108,7 @@ typedef struct {
   double  setup_seconds_host, setup_seconds_factor, setup_seconds_upload;
   int64_t nnz_L_before_tail;   /* entries of L in the columns before the dense tail (= nnz_L without one): what the two sweeps stream */
   int64_t solve_groups, solve_group_threads;   /* large single QP: workgroups x threads that share its sweeps (0 = one workgroup); never more than the device keeps resident */
+  int64_t resident_state, lds_bytes_iterate;   /* 1: the iterate keeps the ADMM state and D^-1 of a tile in LDS across a segment; dynamic LDS of its launches (= lds_bytes when 0) */
 } mi_osqp_stats;
 
 typedef struct mi_osqp_solver mi_osqp_solver; /* one QP  */

@@ -56,6 +56,7 @@ struct KernelArgs {
   double *x_out, *y_out;                // QP-major [B][n], [B][m]
   double *xs_global;                    // non-null: the solve vector lives here ([tile][xs_len][BT]) instead of LDS
   int xs_len;                           // length of the solve vector: Analysis::Next >= n + m
+  int rs_off;                           // iterate / advance launches: LDS offset (in doubles) of the resident state (iterate_body RS), 0 = streamed
   int wide;                             // 32-bit gather / row indices (Schedule::idxw64): vectors of 65 535 entries and more; needs xs_global, BT = 1
   // settings (row S)
   double sigma, alpha, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, rho_tolerance;

@@ -1026,6 +1026,7 @@ Tuning tuning_from_env() {
   t.ruiz = getenv("MI_OSQP_HOST_RUIZ") ? 1 : getenv("MI_OSQP_DEVICE_RUIZ") ? -1 : 0;
   if (const char *e = getenv("MI_OSQP_CONT_RING_KB")) t.cont_ring_kb = std::max(0L, atol(e));
   if (const char *e = getenv("MI_OSQP_ANALYSIS_CACHE")) t.analysis_cache = atoi(e) != 0;
+  t.stream_state = getenv("MI_OSQP_STREAM_STATE") != nullptr;
   AnalysisTuning &a = t.analysis;
   if (const char *e = getenv("MI_OSQP_DENSE_TAIL")) a.dense_tail = atoi(e);
   if (const char *e = getenv("MI_OSQP_ORDERING")) a.ordering = e[0];

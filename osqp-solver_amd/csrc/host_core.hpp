@@ -57,6 +57,7 @@ struct Tuning {
   int ruiz = 0;                    // MI_OSQP_HOST_RUIZ: 1 host equilibration, MI_OSQP_DEVICE_RUIZ: -1 device
   long cont_ring_kb = -1;          // MI_OSQP_CONT_RING_KB: staging ring of the per-QP calls
   bool analysis_cache = true;      // MI_OSQP_ANALYSIS_CACHE=0 switches the cache off
+  bool stream_state = false;       // MI_OSQP_STREAM_STATE: the iterate streams the ADMM state from global memory even where it fits LDS
   AnalysisTuning analysis;
 };
 Tuning tuning_from_env();

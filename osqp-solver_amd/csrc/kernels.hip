@@ -877,8 +877,14 @@ __device__ __forceinline__ void kkt_solve_lds(const KernelArgs &a, const TilePtr
 // residual / termination / rho logic lives in check_kernel, so this kernel needs
 // little beyond the register ring of the step streams.
 // (n_iter iterations; a device function so that advance_kernel can run it segment after segment)
-template <int BT, int NT, bool GX, bool WIDE = false>
+// RS (resident state, LDS vector only): what the vector step reads and writes - x, q, z, y, rho_inv, rho_vec, l, u - and the
+// D^-1 of kkt_middle live in LDS behind the solve vector and its scratch (KernelArgs::rs_off) for the whole call: loaded by
+// the pass that builds the first right-hand side, x / z / y stored by the last iteration.  Only this workgroup touches
+// them in between and nobody reads them before check_kernel.  Same expressions in the same order: the results are
+// bitwise those of the streaming form.  A compile-time flag for the reason given at solve_vector.
+template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false>
 __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, int n_iter) {
+  static_assert(!RS || (!GX && !WIDE), "the resident state goes with the LDS solve vector");
   // multi-workgroup mode (global vector, one QP): the grid is ONE tile; thread / wave numbers run over the grid and the
   // barriers between phases are grid barriers
   const Mw mw{a.mw_bar, GX && BT == 1 && a.mw_groups > 1 ? (unsigned)a.mw_groups : 1u};
@@ -897,12 +903,32 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
   bool df = false;
   if constexpr (GX && BT == 1 && WIDE) df = a.df != 0;
   const uint32_t sh = a.df_shadow;
+  // the per-QP vectors of the vector step and D^-1: the tile's global arrays, or their LDS copies ([i][BT] as well)
+  double *rs = nullptr;
+  if constexpr (RS) rs = smem + a.rs_off;
+  double *const X = RS ? rs : p.x, *const Z = RS ? rs + (size_t)2 * n * BT : p.z, *const Y = RS ? Z + (size_t)m * BT : p.y;
+  const double *const Q = RS ? X + (size_t)n * BT : p.q, *const RI = RS ? Y + (size_t)m * BT : p.rho_inv;
+  const double *const RV = RS ? RI + (size_t)m * BT : p.rho_vec, *const LO = RS ? RV + (size_t)m * BT : p.l;
+  const double *const UP = RS ? LO + (size_t)m * BT : p.u, *const DI = RS ? UP + (size_t)m * BT : p.dinv;
   // ---- E6 of the first iteration: rhs into the permuted solve vector
   for (int e = tid; e < N * BT; e += nthr) {
     const int i = e / BT;
     double v;
-    if (i < n) v = sigma * p.x[e] - p.q[e];
-    else { const int ez = e - n * BT; v = p.z[ez] - p.rho_inv[ez] * p.y[ez]; }
+    if constexpr (RS) {
+      rs[(size_t)(2 * n + 6 * m) * BT + e] = p.dinv[e];
+      if (i < n) { const double xv = p.x[e], qv = p.q[e]; rs[e] = xv; rs[(size_t)n * BT + e] = qv; v = sigma * xv - qv; }
+      else {
+        const int ez = e - n * BT;
+        const double zv = p.z[ez], ri = p.rho_inv[ez], yv = p.y[ez];
+        double *sz = rs + (size_t)2 * n * BT + ez;
+        sz[0] = zv; sz[(size_t)m * BT] = yv; sz[(size_t)2 * m * BT] = ri;
+        sz[(size_t)3 * m * BT] = p.rho_vec[ez]; sz[(size_t)4 * m * BT] = p.l[ez]; sz[(size_t)5 * m * BT] = p.u[ez];
+        v = zv - ri * yv;
+      }
+    } else {
+      if (i < n) v = sigma * p.x[e] - p.q[e];
+      else { const int ez = e - n * BT; v = p.z[ez] - p.rho_inv[ez] * p.y[ez]; }
+    }
     const uint32_t pe = a.pinv[i];
     if (df) { st_sc1(xs + pe, v); df_arm_fwd(xs, pe, a.rflag[pe], a.xloc[pe], sh); }
     else xs[(size_t)pe * BT + b] = v;
@@ -911,8 +937,15 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
   if constexpr (GX) wg_or_grid_barrier(mw); else __syncthreads();
   for (int iter = 1; iter <= n_iter; iter++) {
     const bool do_info = a.info_at_end && iter == n_iter;     // delta_x / delta_y are only needed by check_kernel
+    const bool last = iter == n_iter;                         // (resident state: x, z, y go back to global memory)
     // ---- E7
-    kkt_solve_lds<BT, MI_PFV_NT(NT, GX), GX, WIDE>(a, p, xs, tid, nthr, wave, nw, lane, mw);
+    if constexpr (RS) {                                       // kkt_solve_lds with D^-1 from LDS
+      run_tri<BT, MI_PFV_NT(NT, GX), GX, 0, WIDE>(a.fwd, p.vfwd, xs, wave, lane);
+      kkt_middle<BT, GX>(a, DI, p.vdt, p.act, xs, tid, nthr, wave, lane);
+      run_tri<BT, MI_PFV_NT(NT, GX), GX, 0, WIDE>(a.bwd, p.vbwd, xs, wave, lane);
+    } else {
+      kkt_solve_lds<BT, MI_PFV_NT(NT, GX), GX, WIDE>(a, p, xs, tid, nthr, wave, nw, lane, mw);
+    }
     // ---- E8-E10 fused with E6 of the next iteration (run_tri ends with a barrier): every thread replaces the
     // solution entry it has just consumed by the next right-hand side entry - same position, no other reader
     // (global-vector mode: one workgroup walks 4 x 10^5 entries, each a dependent pinv -> xs gather: U entries per thread
@@ -933,14 +966,18 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int e = e0 + u * nthr < n * BT ? e0 + u * nthr : e0;
-        xt[u] = df ? ld_sc1(xs + df_bloc((uint32_t)pos[u], fl[u], sh)) : xs[pos[u]]; xp[u] = p.x[e]; qv[u] = p.q[e];
+        xt[u] = df ? ld_sc1(xs + df_bloc((uint32_t)pos[u], fl[u], sh)) : xs[pos[u]]; xp[u] = X[e]; qv[u] = Q[e];
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int e = e0 + u * nthr;
         if (e < n * BT) {
           double xn = alpha * xt[u] + (1.0 - alpha) * xp[u];
-          if (!done) { p.x[e] = xn; if (do_info) p.dx[e] = xn - xp[u]; } else xn = xp[u];
+          if (!done) {
+            X[e] = xn;
+            if constexpr (RS) { if (last) p.x[e] = xn; }
+            if (do_info) p.dx[e] = xn - xp[u];
+          } else xn = xp[u];
           if (df) { st_sc1(xs + pos[u], sigma * xn - qv[u]); df_arm_fwd(xs, (uint32_t)pos[u], fl[u], xl[u], sh); }
           else xs[pos[u]] = sigma * xn - qv[u];
         }
@@ -957,7 +994,7 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int e = e0 + u * nthr < m * BT ? e0 + u * nthr : e0;
-        nu[u] = df ? ld_sc1(xs + df_bloc((uint32_t)pos[u], fl[u], sh)) : xs[pos[u]]; zp[u] = p.z[e]; yv[u] = p.y[e]; ri[u] = p.rho_inv[e]; rv[u] = p.rho_vec[e]; lo[u] = p.l[e]; up[u] = p.u[e];
+        nu[u] = df ? ld_sc1(xs + df_bloc((uint32_t)pos[u], fl[u], sh)) : xs[pos[u]]; zp[u] = Z[e]; yv[u] = Y[e]; ri[u] = RI[e]; rv[u] = RV[e]; lo[u] = LO[e]; up[u] = UP[e];
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
@@ -969,7 +1006,11 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
           double zn = fmin(fmax(zr + ri[u] * yv[u], lo[u]), up[u]);
           const double dyv = rv[u] * (zr - zn);
           double yn = yv[u] + dyv;
-          if (!done) { p.z[e] = zn; p.y[e] = yn; if (do_info) p.dy[e] = dyv; } else { zn = zp[u]; yn = yv[u]; }
+          if (!done) {
+            Z[e] = zn; Y[e] = yn;
+            if constexpr (RS) { if (last) { p.z[e] = zn; p.y[e] = yn; } }
+            if (do_info) p.dy[e] = dyv;
+          } else { zn = zp[u]; yn = yv[u]; }
           if (df) { st_sc1(xs + pos[u], zn - ri[u] * yn); df_arm_fwd(xs, (uint32_t)pos[u], fl[u], xl[u], sh); }
           else xs[pos[u]] = zn - ri[u] * yn;
         }
@@ -978,10 +1019,10 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
     if constexpr (GX) wg_or_grid_barrier(mw); else __syncthreads();
   }
 }
-template <int BT, int NT, bool GX, bool WIDE = false>
+template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false>
 __global__ __launch_bounds__(NT) void iterate_kernel(KernelArgs a) {
   extern __shared__ double smem[];
-  iterate_body<BT, NT, GX, WIDE>(a, smem, a.iter_end - a.iter_begin);
+  iterate_body<BT, NT, GX, WIDE, RS>(a, smem, a.iter_end - a.iter_begin);
 }
 
 // E11-E14 after a segment of n_iter iterations: residuals, termination and infeasibility tests, rho estimate / update
@@ -1230,7 +1271,7 @@ struct AdvanceArgs {
   unsigned *counter;       // device words: [0] tiles that have left this launch, [1] tiles that iterated in it (the last tile resets both)
   unsigned *host_done;     // pinned words: [0] receives seq when every tile has left and published, [1] the tiles that iterated
 };
-template <int BT, int NT>
+template <int BT, int NT, bool RS = false>
 __global__ __launch_bounds__(NT) void advance_kernel(KernelArgs a, AdvanceArgs v) {
   extern __shared__ double smem[];
   const int tile = blockIdx.x, tid = threadIdx.x;
@@ -1245,7 +1286,7 @@ __global__ __launch_bounds__(NT) void advance_kernel(KernelArgs a, AdvanceArgs v
     const int done = tid < BT ? is[IS_DONE * BT + tid] : 1;
     if (__syncthreads_and(done)) break;
     iterated = true;
-    iterate_body<BT, NT, false>(a, smem, v.seg_len);
+    iterate_body<BT, NT, false, false, RS>(a, smem, v.seg_len);     // (check_body's scratch ends where the resident state begins)
     // (inlined next to iterate_body the two bodies share one register allocation - 128 VGPRs + spills at 16 waves against
     //  68 for iterate_kernel alone - and every iteration pays ~10 % for it; check_body out of line, as a real function, was
     //  measured twice as slow: the call's register convention puts scratch traffic into the sweeps)
@@ -3558,6 +3599,10 @@ hipError_t launch_advance(const KernelArgs &a, int BT, int tiles, int threads, s
     hipLaunchKernelGGL(kern, dim3(tiles), dim3(threads), lds, st, a, v);
     return hipGetLastError();
   };
+  if (a.rs_off) {       // resident state (lds covers it): the 16-wave tiles that have their CU to themselves
+    if (threads <= 512) return hipErrorInvalidValue;
+    return BT == 1 ? go(&advance_kernel<1, 1024, true>) : go(&advance_kernel<2, 1024, true>);
+  }
   if (threads > 512) return BT == 1 ? go(&advance_kernel<1, 1024>) : go(&advance_kernel<2, 1024>);
   if (BT == 1) return go(&advance_kernel<1, 512>);
   if (BT == 2) return go(&advance_kernel<2, 512>);
@@ -3570,6 +3615,16 @@ hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, s
 #ifdef MI_OSQP_DEBUG_BUILD
   if (a.df && debug_drop_group("iterate") && tiles > 1) tiles--;       // fault injection: a workgroup of the grid never shows up
 #endif
+  if (a.rs_off) {       // resident state (lds covers it): the 16-wave tiles that have their CU to themselves
+    if (a.xs_global || a.wide || a.df || threads <= 512 || threads > 1024 || BT > 2) return hipErrorInvalidValue;
+    auto go = [&](auto kern) -> hipError_t {
+      hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(kern, dim3(tiles), dim3(threads), lds, st, a);
+      return hipGetLastError();
+    };
+    return BT == 1 ? go(&iterate_kernel<1, 1024, false, false, true>) : go(&iterate_kernel<2, 1024, false, false, true>);
+  }
   MI_DISPATCH(iterate_kernel, a);
 }
 hipError_t launch_check(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st) {

@@ -266,6 +266,8 @@ struct mi_osqp_batch {
   std::shared_ptr<const Analysis> anp;        // pattern analysis: shared between the handles of one pattern (analysis cache below)
   int B = 0, BT = 1, ntiles = 0, threads = 512, device = 0, n_cus = 256;
   size_t lds = 0;
+  size_t lds_iter = 0;                        // LDS of the iterate / advance launches: lds + the resident state where it fits (rs_off != 0)
+  int rs_off = 0;                             // KernelArgs::rs_off
   std::vector<QPNumeric> qp;
   bool host_bounds_stale = false;
   hipStream_t stream = nullptr;
@@ -418,6 +420,7 @@ static KernelArgs make_args(mi_osqp_batch *h) {
   a.dscal = h->dscal.p; a.iscal = h->iscal.p;
   a.x_out = h->x_out.p; a.y_out = h->y_out.p;
   a.xs_global = h->global_xs ? h->xs_global.p : nullptr; a.xs_len = (*h->anp).xs_total; a.wide = (*h->anp).wide ? 1 : 0;
+  a.rs_off = h->rs_off;
   a.mw_groups = h->mw_groups; a.mw_bar = h->mw_bar.p; a.mw_scratch = h->mw_scratch.p;
   a.df = (*h->anp).df ? 1 : 0; a.df_shadow = (unsigned)(*h->anp).Next; a.rflag = h->rflag.p;
   {
@@ -871,6 +874,18 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
   h->BT = BT; h->ntiles = (int)((B + BT - 1) / BT);
   h->lds = h->global_xs ? lds_bytes(0, BT, h->threads) : lds_bytes(an.Next + 2 * an.dt.k, BT, h->threads);
   if (h->lds > lds_cap) { g_last_error = "internal: LDS budget exceeded"; return MI_OSQP_ERR_ALLOC; }
+  // Resident state of the iterate (iterate_body RS): x, q, z, y, rho_inv, rho_vec, l, u and D^-1 of a tile stay in LDS for a
+  // whole segment where they fit into what the analysis left of the cap - the extra rows it handed out are not taken back:
+  // that would change the schedules, and with them the summation orders, of patterns that do not fit anyway.  Only for
+  // 16-wave tiles: they have their CU's LDS to themselves, while two 8-wave tiles share a CU and would lose that.  The other
+  // kernels sized by h->lds (check_kernel runs four 512-thread workgroups per CU on large batches) keep their size.
+  h->lds_iter = h->lds; h->rs_off = 0;
+  {
+    const size_t state = sizeof(double) * (size_t)BT * (2 * (size_t)n + 6 * (size_t)m + (size_t)an.N);
+    if (!h->tune.stream_state && !h->global_xs && h->mw_groups <= 0 && h->threads == 1024 && h->lds + state <= lds_cap) {
+      h->rs_off = (int)(h->lds / sizeof(double)); h->lds_iter = h->lds + state;
+    }
+  }
   // ---- device arrays
   size_t T = (size_t)h->ntiles * BT;
   if ((rc = h->fwd.upload(an.fwd)) || (rc = h->bwd.upload(an.bwd)) || (rc = h->chk.upload(an.chk))) return rc;
@@ -1086,6 +1101,7 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
   s.setup_seconds_host = t1 - t0; s.setup_seconds_factor = t_factor; s.setup_seconds_upload = t_upload;
   s.nnz_L_before_tail = an.dt.k ? an.Lp[an.dt.s] : an.nnzL();
   s.solve_groups = h->mw_groups; s.solve_group_threads = h->mw_groups > 0 ? h->mw_threads : 0;
+  s.resident_state = h->rs_off ? 1 : 0; s.lds_bytes_iterate = (int64_t)h->lds_iter;
   if (getenv("MI_OSQP_DEBUG_TIMING"))
     fprintf(stderr, "[mi_osqp] setup B=%d N=%d: analysis+alloc %.1f ms (analysis %.1f), numeric %.1f ms, upload %.1f ms, rest %.1f ms\n", (int)B, an.N,
             1e3 * (t1 - t0), 1e3 * t_analysis, 1e3 * t_factor, 1e3 * t_upload, 1e3 * (now_s() - t1 - t_factor - t_upload));
@@ -1313,7 +1329,7 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
         if (h->mw_groups > 0) spin_lock.lock();
         HIPCHK(hipEventRecord(h->ev0, h->stream));
         if (h->mw_groups > 0) HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), h->stream));
-        HIPCHK(launch_iterate(a, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds, h->stream));
+        HIPCHK(launch_iterate(a, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds_iter, h->stream));
         HIPCHK(hipEventRecord(h->ev1, h->stream));
         {
           // The check of more 16-wave tiles than the CUs hold at once (two each) runs in 8-wave workgroups - four per CU, one round
@@ -2593,7 +2609,7 @@ int mi_osqp_batch_advance(mi_osqp_batch *h, int64_t n_segments) {
   a.info_at_end = 1;
   c.launch_seq++;
   const int par = (int)(c.adv_seq & 1);
-  HIPCHK(launch_advance(a, BT, h->ntiles, h->threads, h->lds, h->stream, (int)std::min<int64_t>(n_segments, 1 << 20), c.L, c.h_is[par], c.h_ds[par],
+  HIPCHK(launch_advance(a, BT, h->ntiles, h->threads, h->lds_iter, h->stream, (int)std::min<int64_t>(n_segments, 1 << 20), c.L, c.h_is[par], c.h_ds[par],
                         n_segments > 1 ? c.stop.p : nullptr, c.launch_seq, c.counter.p, c.h_done));
   HIPCHK(hipEventRecord(c.ev[par], h->stream));
   if (h->st.adaptive_rho) {
