@@ -109,6 +109,7 @@ typedef struct {
   int64_t nnz_L_before_tail;   /* entries of L in the columns before the dense tail (= nnz_L without one): what the two sweeps stream */
   int64_t solve_groups, solve_group_threads;   /* large single QP: workgroups x threads that share its sweeps (0 = one workgroup); never more than the device keeps resident */
   int64_t resident_state, lds_bytes_iterate;   /* 1: the iterate keeps the ADMM state and D^-1 of a tile in LDS across a segment; dynamic LDS of its launches (= lds_bytes when 0) */
+  int64_t pipelined_refactors;   /* rho-update points since setup whose refactorisation ran in chunks, overlapped with the iterate segment behind it */
 } mi_osqp_stats;
 
 typedef struct mi_osqp_solver mi_osqp_solver; /* one QP  */
@@ -420,6 +421,15 @@ int mi_osqp_debug_host_block_factor(int64_t n, int64_t m,
                                     const int64_t *A_colptr, const int64_t *A_rowidx, const double *A_val,
                                     const double *l, const double *u, const mi_osqp_settings *settings,
                                     double *max_rel_diff_L, double *max_rel_diff_Dinv, int64_t *counts);
+
+/* Host only: the chunks of a pipelined refactorisation (solver.hip "pipelined refactorisation").  flagged / active: the
+ * slots (tile * `tile` + b, ascending) that get a new factor / iterate on; chunk_qps flagged slots per chunk, at most
+ * max_chunks refactorisation chunks.  Out: *n_chunks (chunk 0 = tiles without a flagged slot), work_begin[n_chunks + 1]
+ * (chunk c refactors flagged[work_begin[c] .. work_begin[c + 1])), tiles[<= n_active] (the active tiles chunk after
+ * chunk) and tile_begin[n_chunks + 1]; work_begin / tile_begin hold max_chunks + 2 entries. */
+int mi_osqp_debug_refactor_chunks(int64_t n_flagged, const int64_t *flagged, int64_t n_active, const int64_t *active, int64_t tile,
+                                  int64_t chunk_qps, int64_t max_chunks, int64_t *n_chunks, int64_t *work_begin, int64_t *tiles,
+                                  int64_t *tile_begin);
 
 /* Device diagnostics (tile 2, LDS mode only): one KKT solve of the whole batch with
  * per-phase / per-wave shader-clock stamps of two tiles (first, middle).

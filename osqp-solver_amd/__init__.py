@@ -58,7 +58,7 @@ class Stats(C.Structure):
                  "chk_slots", "lds_bytes", "threads_per_block", "dense_tail_rows", "dense_tail_slots")] + \
                [(k, C.c_double) for k in ("setup_seconds_host", "setup_seconds_factor", "setup_seconds_upload")] + \
                [("nnz_L_before_tail", C.c_int64), ("solve_groups", C.c_int64), ("solve_group_threads", C.c_int64),
-                ("resident_state", C.c_int64), ("lds_bytes_iterate", C.c_int64)]
+                ("resident_state", C.c_int64), ("lds_bytes_iterate", C.c_int64), ("pipelined_refactors", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -170,6 +170,7 @@ def lib():
         L.mi_osqp_multi_batch_free.argtypes = [vp]; L.mi_osqp_multi_batch_free.restype = None
         L.mi_osqp_debug_host_kkt_solve.argtypes = [C.c_int64, C.c_int64, ip, ip, dp, ip, ip, dp, dp, dp,
                                                    C.POINTER(Settings), C.c_int64, dp, dp, dp, C.POINTER(Stats)]
+        L.mi_osqp_debug_refactor_chunks.argtypes = [C.c_int64, ip, C.c_int64, ip, C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip]
         L.mi_osqp_prefetch_analysis.argtypes = [C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip, C.c_int64]
         L.mi_osqp_debug_host_block_factor.argtypes = [C.c_int64, C.c_int64, ip, ip, dp, ip, ip, dp, dp, dp,
                                                       C.POINTER(Settings), dp, dp, ip]
@@ -672,6 +673,20 @@ def prefetch_analysis(P, A, B=1, device=-1, check=True):
     if check:
         _chk(rc, "prefetch_analysis")
     return rc
+
+
+def debug_refactor_chunks(flagged, active, tile, chunk_qps, max_chunks=8):
+    """Host-only: the chunks of a pipelined refactorisation.  flagged / active: ascending slots (tile * `tile` + b) that get a new
+    factor / iterate on.  Returns (work, tiles): per chunk the flagged slots it refactors and the tiles it iterates; chunk 0
+    refactors nothing."""
+    f, a = _i64(flagged), _i64(active)
+    nch = C.c_int64()
+    wb = np.zeros(max_chunks + 2, dtype=np.int64); tb = np.zeros(max_chunks + 2, dtype=np.int64)
+    tl = np.zeros(max(1, len(a)), dtype=np.int64)
+    _chk(lib().mi_osqp_debug_refactor_chunks(len(f), _ip(f), len(a), _ip(a), tile, chunk_qps, max_chunks, C.byref(nch), _ip(wb), _ip(tl),
+                                             _ip(tb)), "debug_refactor_chunks")
+    k = int(nch.value)
+    return ([f[wb[c]:wb[c + 1]].tolist() for c in range(k)], [tl[tb[c]:tb[c + 1]].tolist() for c in range(k)])
 
 
 def debug_host_block_factor(P, A, l, u, **settings):

@@ -77,6 +77,9 @@ struct KernelArgs {
   // per-QP entry points (continuous batching): sel[slot] = 0: the slot is not addressed by this launch, j + 1: it is, and
   // its input is row j of the launch's QP-major argument.  null = every QP, row = QP id.
   const int *sel;
+  // iterate launches over a list of tiles (the chunks of a pipelined refactorisation, solver.hip): workgroup j serves tile
+  // tiles[j].  null = the identity.
+  const int *tiles;
 };
 
 // device block refactorisation (row E13); tables are host_core.hpp BlockFactor

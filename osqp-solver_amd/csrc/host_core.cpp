@@ -1027,6 +1027,10 @@ Tuning tuning_from_env() {
   if (const char *e = getenv("MI_OSQP_CONT_RING_KB")) t.cont_ring_kb = std::max(0L, atol(e));
   if (const char *e = getenv("MI_OSQP_ANALYSIS_CACHE")) t.analysis_cache = atoi(e) != 0;
   t.stream_state = getenv("MI_OSQP_STREAM_STATE") != nullptr;
+  if (const char *e = getenv("MI_OSQP_REFACTOR_PIPELINE")) t.refactor_pipeline = atoi(e) != 0;
+  if (const char *e = getenv("MI_OSQP_REFACTOR_PIPELINE_MIN")) t.pipeline_min = std::max(0, atoi(e));
+  if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNKS")) t.pipeline_chunks = std::max(0, std::min(8, atoi(e)));
+  if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNK_QPS")) t.pipeline_chunk_qps = std::max(0, atoi(e));
   AnalysisTuning &a = t.analysis;
   if (const char *e = getenv("MI_OSQP_DENSE_TAIL")) a.dense_tail = atoi(e);
   if (const char *e = getenv("MI_OSQP_ORDERING")) a.ordering = e[0];
@@ -1034,6 +1038,34 @@ Tuning tuning_from_env() {
   if (const char *e = getenv("MI_OSQP_RELAX")) a.relax = atoi(e);
   a.serial = getenv("MI_OSQP_SERIAL_ANALYSIS") != nullptr;
   return t;
+}
+
+RefactorChunks refactor_chunks(const std::vector<int> &flagged, const std::vector<int> &active, int bt, int chunk_qps, int max_chunks) {
+  RefactorChunks rc;
+  const int nq = (int)flagged.size();
+  max_chunks = std::max(1, max_chunks);
+  chunk_qps = std::max(1, chunk_qps);
+  if ((nq + chunk_qps - 1) / chunk_qps > max_chunks) chunk_qps = (nq + max_chunks - 1) / max_chunks;
+  const int n_ref = (nq + chunk_qps - 1) / chunk_qps;
+  rc.n_chunks = 1 + n_ref;
+  rc.work_begin.assign(1, 0);
+  for (int c = 0; c <= n_ref; c++) rc.work_begin.push_back(std::min(nq, c * chunk_qps));
+  // chunk of every active tile: flagged is ascending, so the last entry of a tile is the one that counts
+  std::vector<std::pair<int, int>> tc;        // (chunk, tile)
+  size_t f = 0;
+  for (size_t i = 0; i < active.size(); i++) {
+    const int tile = active[i] / bt;
+    if (i && active[i - 1] / bt == tile) continue;
+    int chunk = 0;
+    while (f < flagged.size() && flagged[f] / bt < tile) f++;
+    for (size_t g = f; g < flagged.size() && flagged[g] / bt == tile; g++) chunk = 1 + (int)g / chunk_qps;
+    tc.emplace_back(chunk, tile);
+  }
+  std::stable_sort(tc.begin(), tc.end(), [](const std::pair<int, int> &x, const std::pair<int, int> &y) { return x.first < y.first; });
+  rc.tile_begin.assign((size_t)rc.n_chunks + 1, 0);
+  for (const auto &p : tc) { rc.tiles.push_back(p.second); rc.tile_begin[(size_t)p.first + 1]++; }
+  for (int c = 0; c < rc.n_chunks; c++) rc.tile_begin[(size_t)c + 1] += rc.tile_begin[c];
+  return rc;
 }
 
 // --------------------------------------------------------------------- analyze

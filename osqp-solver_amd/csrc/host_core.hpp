@@ -58,9 +58,29 @@ struct Tuning {
   long cont_ring_kb = -1;          // MI_OSQP_CONT_RING_KB: staging ring of the per-QP calls
   bool analysis_cache = true;      // MI_OSQP_ANALYSIS_CACHE=0 switches the cache off
   bool stream_state = false;       // MI_OSQP_STREAM_STATE: the iterate streams the ADMM state from global memory even where it fits LDS
+  // refactorisation at a rho-update point pipelined with the iterate segment that follows it (refactor_chunks below)
+  bool refactor_pipeline = true;   // MI_OSQP_REFACTOR_PIPELINE=0: the serial form (every factor first, then one iterate launch)
+  int pipeline_min = 0;            // MI_OSQP_REFACTOR_PIPELINE_MIN: work lists longer than this are pipelined (0 = the CU count)
+  int pipeline_chunks = 0;         // MI_OSQP_REFACTOR_CHUNKS: k > 0 even chunks of the work list (1 .. 8)
+  int pipeline_chunk_qps = 0;      // MI_OSQP_REFACTOR_CHUNK_QPS: chunks of so many QPs, the last one shorter (when pipeline_chunks == 0)
+                                   // both 0 (the measured default): the fewest even chunks of at most one QP per CU - 3 x 202 for 605 QPs
   AnalysisTuning analysis;
 };
 Tuning tuning_from_env();
+
+// Chunks of a pipelined refactorisation.  `flagged` = the slots (tile * bt + b) that get a new factor, ascending; `active` =
+// the slots that iterate on afterwards, ascending.  The flagged slots are cut in order into chunks 1 .. n_chunks - 1 of
+// chunk_qps slots (the last one takes the remainder; at most max_chunks - 1 of them: chunk_qps grows to fit).  Every tile
+// with an active slot belongs to the chunk that holds the LAST of its flagged slots - its iterate may start once that chunk's
+// factors are written - and to chunk 0 when it has none.  Flagged slots of tiles without an active slot (finished at max_iter
+// on a rho-update iteration) are refactored all the same.
+struct RefactorChunks {
+  int n_chunks = 1;
+  std::vector<int> work_begin;     // n_chunks + 1: chunk c refactors flagged[work_begin[c] .. work_begin[c + 1]); chunk 0: none
+  std::vector<int> tiles;          // the active tiles, chunk after chunk, ascending within a chunk
+  std::vector<int> tile_begin;     // n_chunks + 1: chunk c iterates tiles[tile_begin[c] .. tile_begin[c + 1])
+};
+RefactorChunks refactor_chunks(const std::vector<int> &flagged, const std::vector<int> &active, int bt, int chunk_qps, int max_chunks);
 
 // One pull-schedule: every target row t gets  xs[t] -= sum_k val[k] * xs[idx[k]]  (or xs[t] = sum, "store").
 //

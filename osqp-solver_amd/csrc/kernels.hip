@@ -673,7 +673,9 @@ __device__ __forceinline__ TilePtrs<BT> tile_ptrs(const KernelArgs &a, int tile,
 #pragma unroll
   for (int bb = 0; bb < BT; bb++) {
     const size_t slot = t * BT + bb;
-    const bool off = skip_done && p.iscal[IS_DONE * BT + bb] != 0;     // wave-uniform: inside a solve, finished QPs (and padding slots) stream nothing
+    // wave-uniform: inside a solve, finished QPs (and padding slots) stream nothing - nor does a QP whose new factor lost its
+    // inertia (IS_NEED_REFACTOR < 0) in the launch that follows its refactorisation before the host has failed the slot
+    const bool off = skip_done && (p.iscal[IS_DONE * BT + bb] != 0 || p.iscal[IS_NEED_REFACTOR * BT + bb] < 0);
     if (!off) p.act |= 1 << bb;
     const bool wk = !a.use_work || a.use_work[slot] != 0;                // (wave-uniform) working copy or snapshot of the factor
     const double *fv = wk ? a.fwd_val : a.fwd_val0, *bv = wk ? a.bwd_val : a.bwd_val0, *dv = wk ? a.dt_val : a.dt_val0;
@@ -889,7 +891,7 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
   // barriers between phases are grid barriers
   const Mw mw{a.mw_bar, GX && BT == 1 && a.mw_groups > 1 ? (unsigned)a.mw_groups : 1u};
   const bool multi = GX && BT == 1 && mw.G > 1;
-  const int tile = multi ? 0 : blockIdx.x;
+  const int tile = multi ? 0 : (a.tiles ? a.tiles[blockIdx.x] : (int)blockIdx.x);
   const int tid = multi ? blockIdx.x * blockDim.x + threadIdx.x : threadIdx.x, nthr = multi ? blockDim.x * mw.G : blockDim.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nthr >> 6;
   const int b = tid % BT;
@@ -897,7 +899,7 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
   double *unused_scratch;
   double *xs = solve_vector<BT, GX>(a, smem, tile, unused_scratch);
   const TilePtrs<BT> p = tile_ptrs<BT>(a, tile, true);
-  const int done = p.iscal[IS_DONE * BT + b];
+  const int done = p.iscal[IS_DONE * BT + b] | (p.iscal[IS_NEED_REFACTOR * BT + b] < 0);      // (as tile_ptrs: no stores either)
   if (__syncthreads_and(done)) return;
   const double alpha = a.alpha, sigma = a.sigma;
   bool df = false;

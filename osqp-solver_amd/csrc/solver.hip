@@ -151,6 +151,8 @@ static void release_all() {
 
 // The same for pinned host memory and for streams + events: hipHostMalloc costs ~0.5 ms per call and a handle needs four
 // of them, a stream and five events - 2-3 ms of a 4 ms setup for the small QPs of a sequential GOMP run.
+// (pipe_r / pipe_i / pipe_ev: the two streams and the events of a pipelined refactorisation, created by the first handle that
+//  needs them and handed on with the bundle; null until then)
 namespace hostpool {
 static std::mutex mu;
 static std::multimap<size_t, void *> blocks;          // capacity in bytes -> pinned pointer
@@ -186,7 +188,14 @@ static hipError_t alloc(void **p, size_t bytes, size_t *cap) {
 }
 }  // namespace hostpool
 namespace streampool {
-struct Bundle { int dev; hipStream_t stream; hipEvent_t ev[5]; };
+constexpr int kPipeChunks = 8;                      // refactorisation chunks of a pipelined region, at most
+constexpr int kPipeEvents = 3 + 3 * kPipeChunks;    // fork, begin / end of the iterate stream, then (begin, factor done, tail done) per chunk
+struct Bundle { int dev; hipStream_t stream; hipEvent_t ev[5]; hipStream_t pipe_r, pipe_i; hipEvent_t pipe_ev[kPipeEvents]; };
+static void destroy(const Bundle &b) {
+  for (hipEvent_t e : b.ev) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : b.pipe_ev) if (e) (void)hipEventDestroy(e);
+  for (hipStream_t st : {b.stream, b.pipe_r, b.pipe_i}) if (st) (void)hipStreamDestroy(st);
+}
 static std::mutex mu;
 static std::vector<Bundle> idle;
 static bool take(int dev, Bundle &out) {
@@ -200,12 +209,11 @@ static void give(const Bundle &b) {           // (the stream has been synchronis
     std::lock_guard<std::mutex> lk(mu);
     if (idle.size() < 64) { idle.push_back(b); return; }
   }
-  for (hipEvent_t e : b.ev) if (e) (void)hipEventDestroy(e);
-  if (b.stream) (void)hipStreamDestroy(b.stream);
+  destroy(b);
 }
 static void release_all() {
   std::lock_guard<std::mutex> lk(mu);
-  for (Bundle &b : idle) { for (hipEvent_t e : b.ev) if (e) (void)hipEventDestroy(e); if (b.stream) (void)hipStreamDestroy(b.stream); }
+  for (Bundle &b : idle) destroy(b);
   idle.clear();
 }
 }  // namespace streampool
@@ -311,6 +319,11 @@ struct mi_osqp_batch {
   double *pin = nullptr;      // pinned staging of the host update paths (a pageable hipMemcpy runs at ~1 GB/s here, and unevenly)
   size_t pin_n = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, evf0 = nullptr, evf1 = nullptr, evf2 = nullptr;
+  // pipelined refactorisation (solve_impl): stream R of the refactorisation chunks, stream I of the chunk iterates, their events
+  hipStream_t pipe_r = nullptr, pipe_i = nullptr;
+  hipEvent_t pipe_ev[streampool::kPipeEvents] = {};
+  DevBuf<int> tile_list;                      // the active tiles chunk after chunk (KernelArgs::tiles)
+  int64_t pipelined_refactors = 0;            // rho-update points of this handle that took the pipelined form
   double factor_ms_sum = 0.0, dense_ms_sum = 0.0;
   int64_t refactor_launches = 0, refactor_qps = 0, peak_qps = 0;
   double peak_factor_ms = 0.0, peak_tail_ms = 0.0;
@@ -377,11 +390,12 @@ struct mi_osqp_batch {
     if (evp1) (void)hipEventDestroy(evp1);
     hostpool::give(cont.h_done, cont.h_done_cap);
     hostpool::give(h_iscal, h_iscal_cap); hostpool::give(h_dscal, h_dscal_cap); hostpool::give(pin, pin_cap); hostpool::give(h_npos, h_npos_cap);
-    if (stream && ev0 && ev1 && evf0 && evf1 && evf2) streampool::give({device, stream, {ev0, ev1, evf0, evf1, evf2}});
-    else {
-      for (hipEvent_t e : {ev0, ev1, evf0, evf1, evf2}) if (e) (void)hipEventDestroy(e);
-      if (stream) (void)hipStreamDestroy(stream);
-    }
+    if (pipe_r) (void)hipStreamSynchronize(pipe_r);
+    if (pipe_i) (void)hipStreamSynchronize(pipe_i);
+    streampool::Bundle sb{device, stream, {ev0, ev1, evf0, evf1, evf2}, pipe_r, pipe_i, {}};
+    for (int k = 0; k < streampool::kPipeEvents; k++) sb.pipe_ev[k] = pipe_ev[k];
+    if (stream && ev0 && ev1 && evf0 && evf1 && evf2) streampool::give(sb);
+    else streampool::destroy(sb);
   }
 };
 
@@ -864,7 +878,11 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { g_last_error = std::string("device is not gfx950: ") + prop.gcnArchName; return MI_OSQP_ERR_DEVICE; }
   {
     streampool::Bundle sb;
-    if (streampool::take(h->device, sb)) { h->stream = sb.stream; h->ev0 = sb.ev[0]; h->ev1 = sb.ev[1]; h->evf0 = sb.ev[2]; h->evf1 = sb.ev[3]; h->evf2 = sb.ev[4]; }
+    if (streampool::take(h->device, sb)) {
+      h->stream = sb.stream; h->ev0 = sb.ev[0]; h->ev1 = sb.ev[1]; h->evf0 = sb.ev[2]; h->evf1 = sb.ev[3]; h->evf2 = sb.ev[4];
+      h->pipe_r = sb.pipe_r; h->pipe_i = sb.pipe_i;
+      for (int k = 0; k < streampool::kPipeEvents; k++) h->pipe_ev[k] = sb.pipe_ev[k];
+    }
     else {
       HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
       HIPCHK(hipEventCreate(&h->ev0)); HIPCHK(hipEventCreate(&h->ev1));
@@ -1123,6 +1141,20 @@ static int fail_slots(mi_osqp_batch *h, const KernelArgs &a, const std::vector<i
   return 0;
 }
 
+// tail_assemble_kernel / tail_kernel of the ADMM factor: kbt QPs per work tile of the list `work`
+static TailArgs make_tail_args(mi_osqp_batch *h, int kbt, const int *work) {
+  const DenseTail &dt = (*h->anp).dt;
+  TailArgs da{};
+  da.n = (*h->anp).n; da.N = (*h->anp).N; da.s = dt.s; da.k = dt.k; da.kbt = kbt; da.home_bt = h->BT;
+  da.storage = (*h->anp).bf.storage; da.n_slots = dt.n_steps * 64u; da.n_lt = dt.n_lt; da.n_ltcol = dt.n_ltcol; da.n_quads = (uint32_t)(dt.asm_q64.size() / 64);
+  da.nh = h->dt_nh; da.cs_doubles = h->dt_cs_doubles; da.work = work;
+  da.lt_pos = h->dt_lt_pos.p; da.ltcol_col = h->dt_ltcol_col.p; da.tile_tab = h->dt_tile_tab.p; da.wave_tiles = h->dt_wave_tiles.p;
+  da.dt_task = h->dt_task.p; da.dt_task_step = h->dt_task_step.p; da.n_tasks = (uint32_t)(dt.task.size() / 4);
+  da.asm_q64 = h->dt_asm_q64.p; da.diag_tile = h->dt_diag_tile.p; da.src_tile = h->dt_src_tile.p;
+  da.Lblk = h->Lblk.p; da.Dl = h->Dl.p; da.Sd = h->dt_Sd.p; da.dt_val = h->dt_val.p; da.dinv = h->dinv.p; da.npos = h->npos.p; da.iscal = h->iscal.p;
+  return da;
+}
+
 // Row E13 on the device for a list of slots (tile * BT + b): rho vector from the current bounds and rho, KKT
 // assembly, block LDL', scatter into the solve streams.  The work list packs the slots kbt per workgroup.
 // Slots whose new factor has the wrong inertia are appended to *bad (the caller isolates them).
@@ -1169,15 +1201,7 @@ static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::v
   HIPCHK(launch_factor(fa, kbt, wtiles, h->tune.factor_threads, h->stream));
   HIPCHK(hipEventRecord(h->evf1, h->stream));
   if ((*h->anp).dt.k) {      // the tail blocks now hold the Schur complement: invert it into the stream of the symmetric product
-    const DenseTail &dt = (*h->anp).dt;
-    TailArgs da{};
-    da.n = (*h->anp).n; da.N = (*h->anp).N; da.s = dt.s; da.k = dt.k; da.kbt = kbt; da.home_bt = BT;
-    da.storage = (*h->anp).bf.storage; da.n_slots = dt.n_steps * 64u; da.n_lt = dt.n_lt; da.n_ltcol = dt.n_ltcol; da.n_quads = (uint32_t)(dt.asm_q64.size() / 64);
-    da.nh = h->dt_nh; da.cs_doubles = h->dt_cs_doubles; da.work = h->work.p;
-    da.lt_pos = h->dt_lt_pos.p; da.ltcol_col = h->dt_ltcol_col.p; da.tile_tab = h->dt_tile_tab.p; da.wave_tiles = h->dt_wave_tiles.p;
-    da.dt_task = h->dt_task.p; da.dt_task_step = h->dt_task_step.p; da.n_tasks = (uint32_t)(dt.task.size() / 4);
-    da.asm_q64 = h->dt_asm_q64.p; da.diag_tile = h->dt_diag_tile.p; da.src_tile = h->dt_src_tile.p;
-    da.Lblk = h->Lblk.p; da.Dl = h->Dl.p; da.Sd = h->dt_Sd.p; da.dt_val = h->dt_val.p; da.dinv = h->dinv.p; da.npos = h->npos.p; da.iscal = h->iscal.p;
+    TailArgs da = make_tail_args(h, kbt, h->work.p);
     if (pol) { da.dt_val = h->pol_dt.p; da.dinv = h->pol_dinv.p; da.pstat = pol->stat; }
     unsigned long long *d_trace = nullptr;
     const bool tracing = getenv("MI_OSQP_TAIL_TRACE") != nullptr;          // timing stamps only; results are unaffected
@@ -1296,9 +1320,106 @@ static int polish_impl(mi_osqp_batch *h, const KernelArgs &a) {
   return MI_OSQP_OK;
 }
 
+// ------------------------------------------------ pipelined refactorisation
+// A long work list at a rho-update point ("Pipelined refactorisation"): no tile shares anything with
+// another, so a tile may start the next segment as soon as the factors of its own QPs are written.  The work list is cut into
+// chunks (host_core.hpp refactor_chunks).  Stream R runs factor_kernel -> tail_assemble_kernel -> tail_kernel chunk after chunk
+// with an event behind each; stream I runs iterate_kernel over the tiles of a chunk (KernelArgs::tiles) once that chunk's event
+// has fired - chunk 0, the tiles without a flagged QP, at once.  Both fork from the solve stream and join it again, so callers
+// see the ordering they always saw.  Only ordinary LDS-vector batches: no launch here spins on other workgroups.
+static bool pipeline_applies(const mi_osqp_batch *h, int n_ref) {
+  const int longer_than = h->tune.pipeline_min > 0 ? h->tune.pipeline_min : h->n_cus;
+  return h->tune.refactor_pipeline && n_ref > longer_than && h->mw_groups <= 0 && !h->global_xs && !(*h->anp).wide && !(*h->anp).df;
+}
+
+// Refactors the slots of `work` and runs iterations (a.iter_begin, a.iter_end] of the tiles that hold a slot of `active`.
+// Slots whose new factor has the wrong inertia are appended to *bad: their iterate left them alone (tile_ptrs), the caller
+// fails them before the check.  Accounting: see mi_osqp_batch_last_solve_stats / DESIGN.md section 4.
+static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, const std::vector<int> &work, const std::vector<int> &active, std::vector<int> *bad) {
+  using streampool::kPipeChunks; using streampool::kPipeEvents;
+  const double t_begin = now_s();
+  const int BT = h->BT, nq = (int)work.size();
+  int rc;
+  if (!h->pipe_r) HIPCHK(hipStreamCreateWithFlags(&h->pipe_r, hipStreamNonBlocking));
+  if (!h->pipe_i) HIPCHK(hipStreamCreateWithFlags(&h->pipe_i, hipStreamNonBlocking));
+  for (int k = 0; k < kPipeEvents; k++) if (!h->pipe_ev[k]) HIPCHK(hipEventCreate(&h->pipe_ev[k]));
+  hipEvent_t ev_fork = h->pipe_ev[0], ev_i0 = h->pipe_ev[1], ev_i1 = h->pipe_ev[2];
+  auto ev_chunk = [&](int c, int k) { return h->pipe_ev[3 + 3 * (c - 1) + k]; };      // chunk c >= 1; k = 0 begin, 1 factor done, 2 tail done
+  // default: the fewest even chunks that are one round of one-workgroup-per-QP kernels each (headline batch, 605 QPs on 256 CUs:
+  // 3 x 202 beat 2 x 303, 4 x 152, 6 x 101 and 256 + 256 + 93)
+  int n_even = h->tune.pipeline_chunks > 0 ? h->tune.pipeline_chunks : (nq + h->n_cus - 1) / h->n_cus;
+  int chunk_qps = (nq + n_even - 1) / n_even;
+  if (h->tune.pipeline_chunks <= 0 && h->tune.pipeline_chunk_qps > 0) chunk_qps = h->tune.pipeline_chunk_qps;
+  const RefactorChunks ch = refactor_chunks(work, active, BT, chunk_qps, kPipeChunks);
+  // the work list chunk after chunk, each packed kbt slots per workgroup (as device_refactor_slots packs the whole list)
+  const int kbt = nq <= h->n_cus ? 1 : BT;
+  std::vector<int> wl, wl_begin(1, 0);
+  for (int c = 1; c < ch.n_chunks; c++) {
+    wl.insert(wl.end(), work.begin() + ch.work_begin[c], work.begin() + ch.work_begin[c + 1]);
+    wl.resize((wl.size() + kbt - 1) / kbt * kbt, -1);
+    wl_begin.push_back((int)wl.size());
+  }
+  if (h->work.n < wl.size() && (rc = h->work.alloc((size_t)h->ntiles * BT + 4 + (size_t)BT * kPipeChunks))) return rc;
+  if (h->tile_list.n < ch.tiles.size() && (rc = h->tile_list.alloc((size_t)h->ntiles))) return rc;
+  HIPCHK(hipMemcpyAsync(h->work.p, wl.data(), wl.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->tile_list.p, ch.tiles.data(), ch.tiles.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const double t_fork = now_s();
+  HIPCHK(hipEventRecord(ev_fork, h->stream));
+  HIPCHK(hipStreamWaitEvent(h->pipe_r, ev_fork, 0));
+  HIPCHK(hipStreamWaitEvent(h->pipe_i, ev_fork, 0));
+  // ---- stream R
+  FactorArgs fa = make_factor_args(h, 0);
+  const bool tail = (*h->anp).dt.k != 0;
+  for (int c = 1; c < ch.n_chunks; c++) {
+    const int *wc = h->work.p + wl_begin[c - 1];
+    const int slots = wl_begin[c] - wl_begin[c - 1];
+    fa.work = wc;
+    HIPCHK(hipEventRecord(ev_chunk(c, 0), h->pipe_r));
+    HIPCHK(launch_factor(fa, kbt, slots / kbt, h->tune.factor_threads, h->pipe_r));
+    HIPCHK(hipEventRecord(ev_chunk(c, 1), h->pipe_r));
+    if (tail) HIPCHK(launch_tail(make_tail_args(h, kbt, wc), slots, h->dt_lds_asm, h->dt_lds, h->pipe_r));
+    HIPCHK(hipEventRecord(ev_chunk(c, 2), h->pipe_r));
+  }
+  // ---- stream I
+  KernelArgs ai = a;
+  HIPCHK(hipEventRecord(ev_i0, h->pipe_i));
+  for (int c = 0; c < ch.n_chunks; c++) {
+    const int nt = ch.tile_begin[c + 1] - ch.tile_begin[c];
+    if (c) HIPCHK(hipStreamWaitEvent(h->pipe_i, ev_chunk(c, 2), 0));
+    if (!nt) continue;
+    ai.tiles = h->tile_list.p + ch.tile_begin[c];
+    HIPCHK(launch_iterate(ai, BT, nt, h->threads, h->lds_iter, h->pipe_i));
+  }
+  HIPCHK(hipEventRecord(ev_i1, h->pipe_i));
+  // ---- join (stream I has waited for every chunk of R), flags of the new factors
+  HIPCHK(hipStreamWaitEvent(h->stream, ev_i1, 0));
+  HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)h->ntiles * IS_COUNT * BT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const double t_end = now_s();
+  float f_ms = 0.f, d_ms = 0.f, r_ms = 0.f, i_ms = 0.f;
+  for (int c = 1; c < ch.n_chunks; c++) {
+    float f = 0.f, d = 0.f;
+    HIPCHK(hipEventElapsedTime(&f, ev_chunk(c, 0), ev_chunk(c, 1))); HIPCHK(hipEventElapsedTime(&d, ev_chunk(c, 1), ev_chunk(c, 2)));
+    f_ms += f; d_ms += tail ? d : 0.f;
+  }
+  HIPCHK(hipEventElapsedTime(&r_ms, ev_fork, ev_chunk(ch.n_chunks - 1, 2)));
+  HIPCHK(hipEventElapsedTime(&i_ms, ev_i0, ev_i1));
+  // refactor_s: up to the last chunk's event; device_s: what remained exposed of the iterate, up to the join - together the wall time
+  const double wall = t_end - t_begin, ref_s = std::min(wall, (t_fork - t_begin) + 1e-3 * r_ms);
+  h->last_refactor_s += ref_s; h->last_device_s += wall - ref_s;
+  h->kernel_ms_sum += i_ms; h->kernel_launches++; h->last_launches++;       // the span of stream I as one launch: it contains waiting
+  h->factor_ms_sum += f_ms; h->dense_ms_sum += d_ms; h->refactor_launches++; h->refactor_qps += nq;
+  if (nq >= h->peak_qps) { h->peak_qps = nq; h->peak_factor_ms = f_ms; h->peak_tail_ms = d_ms; }
+  h->pipelined_refactors++;
+  for (int s : work)
+    if (h->h_iscal[(size_t)(s / BT) * IS_COUNT * BT + IS_NEED_REFACTOR * BT + s % BT] < 0) bad->push_back(s);
+  return 0;
+}
+
 // The ADMM loop runs in segments that end at every termination-check / rho-update
 // point: iterate_kernel (E6-E10) -> check_kernel (E11-E14) -> host reads the flags,
 // runs the device refactorisation for the QPs whose rho changed, and continues.
+// (a long work list: the refactorisation and the iterate of the next segment are pipelined, pipelined_refactor_iterate)
 static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream) {
   hipStream_t keep = h->stream;
   struct Restore { mi_osqp_batch *h; hipStream_t s; ~Restore() { h->stream = s; } } restore{h, keep};
@@ -1316,21 +1437,28 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
     for (int q = 0; q < h->B; q++) if (h->failed[q]) bad.push_back(q);
     if ((rc = fail_slots(h, a, bad, 0))) return rc;
   }
+  auto segment_end = [&](int iter) {       // the next termination-check / rho-update point after iteration `iter`
+    int seg_end = (int)S.max_iter;
+    if (S.check_termination > 0) seg_end = std::min<int64_t>(seg_end, (iter / S.check_termination + 1) * S.check_termination);
+    if (S.adaptive_rho && S.adaptive_rho_interval > 0)
+      seg_end = std::min<int64_t>(seg_end, (iter / S.adaptive_rho_interval + 1) * S.adaptive_rho_interval);
+    return seg_end;
+  };
   auto loop = [&]() -> int {
     int iter = 0;
+    bool iterated = false;       // the segment's iterations have run already, pipelined with the refactorisation before them
     while (true) {
-      int seg_end = (int)S.max_iter;
-      if (S.check_termination > 0) seg_end = std::min<int64_t>(seg_end, (iter / S.check_termination + 1) * S.check_termination);
-      if (S.adaptive_rho && S.adaptive_rho_interval > 0)
-        seg_end = std::min<int64_t>(seg_end, (iter / S.adaptive_rho_interval + 1) * S.adaptive_rho_interval);
+      const int seg_end = segment_end(iter);
       a.iter_begin = iter; a.iter_end = seg_end; a.info_at_end = 1;
       {
         std::unique_lock<std::mutex> spin_lock(spin_mutex(h->device), std::defer_lock);
         if (h->mw_groups > 0) spin_lock.lock();
-        HIPCHK(hipEventRecord(h->ev0, h->stream));
-        if (h->mw_groups > 0) HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), h->stream));
-        HIPCHK(launch_iterate(a, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds_iter, h->stream));
-        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        if (!iterated) {
+          HIPCHK(hipEventRecord(h->ev0, h->stream));
+          if (h->mw_groups > 0) HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), h->stream));
+          HIPCHK(launch_iterate(a, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds_iter, h->stream));
+          HIPCHK(hipEventRecord(h->ev1, h->stream));
+        }
         {
           // The check of more 16-wave tiles than the CUs hold at once (two each) runs in 8-wave workgroups - four per CU, one round
           // instead of two; the check schedule is walked stream by stream by however many waves there are, row by row in the
@@ -1350,9 +1478,12 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
         g_last_error = why + " (the handle is back in the state of its last setup / update, cold-started)";
         return rc;
       }
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-      h->last_device_s += ms * 1e-3; h->kernel_ms_sum += ms; h->kernel_launches++; h->last_launches++;
+      if (!iterated) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        h->last_device_s += ms * 1e-3; h->kernel_ms_sum += ms; h->kernel_launches++; h->last_launches++;
+      }
+      iterated = false;
       iter = seg_end;
       // QPs still iterating / asking for a refactorisation.  A QP that runs into max_iter at a rho-update iteration
       // has finished AND asks for its refactorisation: upstream adapts rho (and refactors) before it leaves the loop,
@@ -1371,7 +1502,14 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
         std::vector<int> bad;             // QPs whose refactorisation lost the inertia
         int rc2;
         // work list: the flagged QPs of the whole batch (fewer, fuller tiles = fewer rounds over the CUs)
-        if ((rc2 = device_refactor_slots(h, std::move(work), &bad))) return rc2;
+        if (!active.empty() && pipeline_applies(h, n_ref)) {
+          // a long list: its chunks overlap with the next segment's iterations, chunk after chunk
+          KernelArgs nx = a;
+          nx.iter_begin = iter; nx.iter_end = segment_end(iter); nx.info_at_end = 1;
+          if ((rc2 = pipelined_refactor_iterate(h, nx, work, active, &bad))) return rc2;
+          iterated = true;
+          tr = now_s();         // (the region has done its own accounting)
+        } else if ((rc2 = device_refactor_slots(h, std::move(work), &bad))) return rc2;
         // a rho update that makes the factor lose its inertia ends THAT QP as kNonConvex ([EXT] osqp_solve: adapt_rho
         // fails -> OSQP_NON_CVX, break); every other QP of the batch goes on
         if ((rc2 = fail_slots(h, a, bad, iter))) return rc2;
@@ -1389,7 +1527,12 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
     return MI_OSQP_OK;
   };
   rc = loop();
-  if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+  if (rc) {
+    if (h->pipe_r) (void)hipStreamSynchronize(h->pipe_r);
+    if (h->pipe_i) (void)hipStreamSynchronize(h->pipe_i);
+    (void)hipStreamSynchronize(h->stream);
+    return rc;
+  }
   HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)nslots * IS_COUNT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   for (int qi = 0; qi < h->B; qi++)
@@ -1582,6 +1725,7 @@ int mi_osqp_batch_get_scaling(mi_osqp_batch *h, double *D, double *E, double *c)
 int mi_osqp_batch_get_stats(mi_osqp_batch *h, mi_osqp_stats *st) {
   if (!h || !st) return MI_OSQP_ERR_NULL;
   *st = h->stats;
+  st->pipelined_refactors = h->pipelined_refactors;
   return MI_OSQP_OK;
 }
 
@@ -2934,6 +3078,19 @@ int mi_osqp_solve(mi_osqp_solver *h, mi_osqp_info *info) {
 }
 int mi_osqp_get_primal(mi_osqp_solver *h, double *x) { return h ? mi_osqp_batch_get_primal(h->b, x) : MI_OSQP_ERR_NULL; }
 int mi_osqp_get_dual(mi_osqp_solver *h, double *y) { return h ? mi_osqp_batch_get_dual(h->b, y) : MI_OSQP_ERR_NULL; }
+int mi_osqp_debug_refactor_chunks(int64_t n_flagged, const int64_t *flagged, int64_t n_active, const int64_t *active, int64_t tile,
+                                  int64_t chunk_qps, int64_t max_chunks, int64_t *n_chunks, int64_t *work_begin, int64_t *tiles,
+                                  int64_t *tile_begin) {
+  if (!n_chunks || !work_begin || !tiles || !tile_begin || (n_flagged > 0 && !flagged) || (n_active > 0 && !active)) return MI_OSQP_ERR_NULL;
+  if (n_flagged < 0 || n_active < 0 || tile < 1 || chunk_qps < 1 || max_chunks < 1) return MI_OSQP_ERR_INVALID_DATA;
+  const std::vector<int> f(flagged, flagged + n_flagged), a(active, active + n_active);
+  const RefactorChunks ch = refactor_chunks(f, a, (int)tile, (int)chunk_qps, (int)max_chunks);
+  *n_chunks = ch.n_chunks;
+  std::copy(ch.work_begin.begin(), ch.work_begin.end(), work_begin);
+  std::copy(ch.tiles.begin(), ch.tiles.end(), tiles);
+  std::copy(ch.tile_begin.begin(), ch.tile_begin.end(), tile_begin);
+  return MI_OSQP_OK;
+}
 int mi_osqp_get_stats(mi_osqp_solver *h, mi_osqp_stats *st) { return h ? mi_osqp_batch_get_stats(h->b, st) : MI_OSQP_ERR_NULL; }
 
 // ------------------------------------------------------------ multi-GPU batch
