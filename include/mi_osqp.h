@@ -110,6 +110,8 @@ typedef struct {
   int64_t solve_groups, solve_group_threads;   /* large single QP: workgroups x threads that share its sweeps (0 = one workgroup); never more than the device keeps resident */
   int64_t resident_state, lds_bytes_iterate;   /* 1: the iterate keeps the ADMM state and D^-1 of a tile in LDS across a segment; dynamic LDS of its launches (= lds_bytes when 0) */
   int64_t pipelined_refactors;   /* rho-update points since setup whose refactorisation ran in chunks, overlapped with the iterate segment behind it */
+  int64_t resident_factor_steps, lds_bytes_factor;   /* resident head of S^-1: 512 B steps of the dense-tail stream every wave of a tile keeps in registers and LDS across a segment (0 = streamed); LDS of its part, which the iterate launches take on top of lds_bytes_iterate */
+  int64_t dense_tail_tasks, dense_tail_waves_used, dense_tail_wave_tasks_max;   /* deal of the dense-tail product: 64 x 64 block tasks, waves of a tile that own at least one, most tasks of one wave */
 } mi_osqp_stats;
 
 typedef struct mi_osqp_solver mi_osqp_solver; /* one QP  */

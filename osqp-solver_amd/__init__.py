@@ -58,7 +58,9 @@ class Stats(C.Structure):
                  "chk_slots", "lds_bytes", "threads_per_block", "dense_tail_rows", "dense_tail_slots")] + \
                [(k, C.c_double) for k in ("setup_seconds_host", "setup_seconds_factor", "setup_seconds_upload")] + \
                [("nnz_L_before_tail", C.c_int64), ("solve_groups", C.c_int64), ("solve_group_threads", C.c_int64),
-                ("resident_state", C.c_int64), ("lds_bytes_iterate", C.c_int64), ("pipelined_refactors", C.c_int64)]
+                ("resident_state", C.c_int64), ("lds_bytes_iterate", C.c_int64), ("pipelined_refactors", C.c_int64),
+                ("resident_factor_steps", C.c_int64), ("lds_bytes_factor", C.c_int64),
+                ("dense_tail_tasks", C.c_int64), ("dense_tail_waves_used", C.c_int64), ("dense_tail_wave_tasks_max", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

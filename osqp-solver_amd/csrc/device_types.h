@@ -57,6 +57,7 @@ struct KernelArgs {
   double *xs_global;                    // non-null: the solve vector lives here ([tile][xs_len][BT]) instead of LDS
   int xs_len;                           // length of the solve vector: Analysis::Next >= n + m
   int rs_off;                           // iterate / advance launches: LDS offset (in doubles) of the resident state (iterate_body RS), 0 = streamed
+  int rf_off;                           // iterate launches: LDS offset (in doubles) of the LDS part of the resident head of S^-1 (iterate_body RF), 0 = streamed
   int wide;                             // 32-bit gather / row indices (Schedule::idxw64): vectors of 65 535 entries and more; needs xs_global, BT = 1
   // settings (row S)
   double sigma, alpha, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, rho_tolerance;
@@ -154,6 +155,9 @@ bool factor_fits_lds(const FactorArgs &a, int threads);      // the LDS-resident
 int max_coresident_groups(int threads, size_t lds, int n_cus);
 int max_coresident_factor_groups(int threads, int n_cus);
 hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st);
+// resident head of S^-1 of the resident iterate (kernels.hip dense_tail_apply_rf): steps per wave in all / in LDS
+int rf_head_steps();
+int rf_lds_steps();
 hipError_t launch_check(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st);
 // up to max_segments segments of seg_len iterations + check per tile in one launch (advance_kernel; LDS-resident tiles only);
 // flags / solutions of the tiles it touched go to the pinned host images host_is / host_ds

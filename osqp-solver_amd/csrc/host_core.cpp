@@ -654,6 +654,13 @@ static void build_dense_tail(Analysis &an, int nw) {
   dt.task.clear(); dt.src.clear();
   dt.wave_task.assign(nw + 1, 0u); dt.wave_step.assign(nw + 1, 0u); dt.tail_bar.assign(nw, 0u);
   dt.n_steps = 0;
+  // The deal: round robin over the waves, every phase starting where the one before it ended - the tasks of all phases
+  // spread over the waves as evenly as they can (k = 448, 16 waves: 28 tasks, twelve waves get two and four get one; a
+  // rotation by one wave per phase left waves 10 - 15 without any), within a phase a wave gets at most ceil(tasks / nw).
+  // The deal does not enter the arithmetic: a task's sums stay inside the task, the targets of a phase are disjoint and
+  // the phases are separated by barriers - the product is bit for bit the same under every deal.
+  std::vector<size_t> phase_first(phases.size(), 0);      // tasks of the phases before
+  for (size_t ph = 1; ph < phases.size(); ph++) phase_first[ph] = phase_first[ph - 1] + phases[ph - 1].size();
   for (int w = 0; w < nw; w++) {
     dt.wave_task[w] = (uint32_t)(dt.task.size() / 4); dt.wave_step[w] = dt.n_steps;
     int last_phase = 0;
@@ -661,7 +668,7 @@ static void build_dense_tail(Analysis &an, int nw) {
       const std::vector<T> &v = phases[ph];
       bool first = true;
       for (size_t t = 0; t < v.size(); t++) {
-        if ((int)((t + (size_t)ph) % (size_t)nw) != w) continue;       // round robin, rotated per phase
+        if ((int)((t + phase_first[ph]) % (size_t)nw) != w) continue;
         const bool diag = v[t].flags & DT_DIAG;
         const uint32_t nsteps = diag ? 32u : 64u, s0 = diag ? 1u : 0u;
         uint32_t nbar = 0;
@@ -1027,6 +1034,7 @@ Tuning tuning_from_env() {
   if (const char *e = getenv("MI_OSQP_CONT_RING_KB")) t.cont_ring_kb = std::max(0L, atol(e));
   if (const char *e = getenv("MI_OSQP_ANALYSIS_CACHE")) t.analysis_cache = atoi(e) != 0;
   t.stream_state = getenv("MI_OSQP_STREAM_STATE") != nullptr;
+  t.stream_factor = getenv("MI_OSQP_STREAM_FACTOR") != nullptr;
   if (const char *e = getenv("MI_OSQP_REFACTOR_PIPELINE")) t.refactor_pipeline = atoi(e) != 0;
   if (const char *e = getenv("MI_OSQP_REFACTOR_PIPELINE_MIN")) t.pipeline_min = std::max(0, atoi(e));
   if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNKS")) t.pipeline_chunks = std::max(0, std::min(8, atoi(e)));

@@ -58,6 +58,7 @@ struct Tuning {
   long cont_ring_kb = -1;          // MI_OSQP_CONT_RING_KB: staging ring of the per-QP calls
   bool analysis_cache = true;      // MI_OSQP_ANALYSIS_CACHE=0 switches the cache off
   bool stream_state = false;       // MI_OSQP_STREAM_STATE: the iterate streams the ADMM state from global memory even where it fits LDS
+  bool stream_factor = false;      // MI_OSQP_STREAM_FACTOR: the resident iterate streams all of S^-1 in every iteration (no resident head)
   // refactorisation at a rho-update point pipelined with the iterate segment that follows it (refactor_chunks below)
   bool refactor_pipeline = true;   // MI_OSQP_REFACTOR_PIPELINE=0: the serial form (every factor first, then one iterate launch)
   int pipeline_min = 0;            // MI_OSQP_REFACTOR_PIPELINE_MIN: work lists longer than this are pipelined (0 = the CU count)

@@ -780,6 +780,107 @@ __device__ __forceinline__ void dense_tail_apply(const DenseTailDev &dt, const m
   for (uint32_t nb = as_const(dt.tail_bar)[wave]; nb; nb--) lds_barrier();
 }
 
+// Resident head of the S^-1 stream (iterate_body RF; one QP per tile, 16 waves): the first H = R + RL steps of a wave's first
+// task stay on chip across the iterations of one iterate_body call - steps [0, RL) in LDS (`hl`: this lane's slot of step 0,
+// [wave][step][lane], written and read by the same lane: no barrier), steps [RL, H) in the registers `keep` (constant
+// indices only).  Every task is 32 or 64 steps long, so with H <= 32 the head lies inside the first task whatever its kind,
+// and with H a multiple of the ring depth the ring takes the rest of the task in whole revolutions.
+// R = 8, RL = 8 (113 VGPRs, no scratch): with 24 or 16 register steps, both tried, the kernel spills 21 VGPRs at the 128 a
+// wave may have at 16 waves per CU - a form that spills is not taken at any R ("Resident head of S^-1").
+// `first` (the call's first iteration) issues the head's loads - the same raw_buffer_load_b64 at the same offsets as
+// dense_tail_apply, the null descriptor of a finished or failed QP returning 0 - and keeps what they return; later iterations
+// load nothing for the head and start the ring at begin + H.  Every launch reloads the head: the new factor of a rho update,
+// a reset, an objective or an A update needs no invalidation.  Same barriers, same tj / ti loads, same fma order and
+// rotations, same flush: bitwise the result of dense_tail_apply<1, 1, PF>.  A wave without a task keeps nothing.
+// The ring's loads past a wave's range, which dense_tail_apply issues and drops, are left out here: what follows the range
+// is the head of the next wave, which nobody else loads any more - they would cost HBM traffic instead of an L2 hit.
+#ifndef MI_RF_R
+#define MI_RF_R 8
+#endif
+#ifndef MI_RF_RL
+#define MI_RF_RL 8
+#endif
+template <int R, int RL, int PF>
+__device__ __forceinline__ void dense_tail_apply_rf(const DenseTailDev &dt, const mi_rsrc &vals, const double *xt, double *yr, double *yc,
+                                                    double (&keep)[R], double *hl, bool first, int wave, int lane) {
+  constexpr int H = R + RL;
+  static_assert(H % PF == 0 && H <= 32 && RL <= PF, "the head is whole ring revolutions inside the shortest task");
+  mi_cptr tk = as_const(dt.task);
+  uint32_t t = as_const(dt.wave_task)[wave];
+  const uint32_t begin = as_const(dt.wave_step)[wave], end = as_const(dt.wave_step)[wave + 1];
+  if (begin < end) {
+    double rv[PF], tj, ti, accr = 0.0, accc = 0.0;
+    uint32_t I0 = tk[4 * t], J0 = tk[4 * t + 1], nst = tk[4 * t + 3], flags;
+    auto ld = [&](uint32_t step) {
+      const mi_u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(vals, (uint32_t)lane * 8u, step * 512u, 0);
+      return __hiloint2double((int)w.y, (int)w.x);
+    };
+    auto fma_step = [&](double v) {
+      accc = fma(v, ti, accc);
+      accr = fma(v, tj, accr);
+      ti = rol1_d(ti); accr = rol1_d(accr);
+    };
+    auto flush = [&]() {                                          // the task is complete: add its two 64-vectors of sums
+      const uint32_t il = ((uint32_t)lane + (flags & 1u) + nst) & 63u;
+      double *rvec = (flags & 2u) ? yc : yr, *cvec = (flags & 2u) ? yr : yc;
+      rvec[I0 + il] += accr;
+      cvec[J0 + (uint32_t)lane] += accc;
+      t++;
+    };
+    {
+      const uint32_t fl = tk[4 * t + 2];
+      for (uint32_t nb = fl >> 8; nb; nb--) lds_barrier();
+      flags = fl & 255u;
+      tj = xt[J0 + (uint32_t)lane];
+      ti = xt[I0 + (((uint32_t)lane + (flags & 1u)) & 63u)];
+    }
+    // ---- the head
+    if (first) {
+#pragma unroll
+      for (int st = 0; st < RL; st++) rv[st] = ld(begin + (uint32_t)st);
+#pragma unroll
+      for (int st = 0; st < R; st++) keep[st] = ld(begin + (uint32_t)(RL + st));
+#pragma unroll
+      for (int st = 0; st < RL; st++) hl[st * 64] = rv[st];
+    } else {
+#pragma unroll
+      for (int st = 0; st < RL; st++) rv[st] = hl[st * 64];
+    }
+#pragma unroll
+    for (int st = 0; st < RL; st++) fma_step(rv[st]);
+    const uint32_t p0 = begin + (uint32_t)H;                              // the ring takes over here; its first revolution flies under the register part
+    if (p0 < end) {
+#pragma unroll
+      for (int st = 0; st < PF; st++) rv[st] = ld(p0 + (uint32_t)st);
+    }
+#pragma unroll
+    for (int st = 0; st < R; st++) fma_step(keep[st]);
+    uint32_t left = nst - (uint32_t)H;
+    if (left == 0) flush();
+    for (uint32_t pos = p0 + PF; pos < end + PF; pos += PF) {     // this revolution consumes steps [pos - PF, pos) and loads [pos, pos + PF)
+      if (left == 0) {                                            // the next task starts (task lengths are multiples of PF)
+        I0 = tk[4 * t]; J0 = tk[4 * t + 1]; nst = tk[4 * t + 3];
+        const uint32_t fl = tk[4 * t + 2];
+        for (uint32_t nb = fl >> 8; nb; nb--) lds_barrier();
+        flags = fl & 255u; left = nst;
+        tj = xt[J0 + (uint32_t)lane];
+        ti = xt[I0 + (((uint32_t)lane + (flags & 1u)) & 63u)];
+        accr = 0.0; accc = 0.0;
+      }
+      if (pos < end) {
+#pragma unroll
+        for (int st = 0; st < PF; st++) { fma_step(rv[st]); rv[st] = ld(pos + (uint32_t)st); }
+      } else {
+#pragma unroll
+        for (int st = 0; st < PF; st++) fma_step(rv[st]);
+      }
+      left -= PF;
+      if (left == 0) flush();
+    }
+  }
+  for (uint32_t nb = as_const(dt.tail_bar)[wave]; nb; nb--) lds_barrier();
+}
+
 // what happens between the forward and the backward sweep: D^-1 on the rows before the dense tail, S^-1 on the tail
 template <int BT, bool GX>
 __device__ __forceinline__ void kkt_middle(const KernelArgs &a, const double *dinv, const mi_rsrc (&vdt)[BT], int act, double *xs,
@@ -823,6 +924,22 @@ __device__ __forceinline__ void kkt_middle(const KernelArgs &a, const double *di
     for (int e = tid; e < k * BT; e += nthr) xs[(size_t)s * BT + e] = yr[e] + yc[e];
     __syncthreads();
   }
+}
+
+// kkt_middle of the resident iterate with the resident head of S^-1 (one QP per tile, LDS vector, dense tail)
+template <int R, int RL>
+__device__ __forceinline__ void kkt_middle_rf(const KernelArgs &a, const double *dinv, const mi_rsrc &vdt, double *xs, double (&keep)[R],
+                                              double *hl, bool first, int tid, int nthr, int wave, int lane) {
+  const int s = a.dt.s, k = a.dt.k;
+  double *yr = xs + (size_t)a.xs_len, *yc = yr + (size_t)k;
+  for (int e = tid; e < a.N; e += nthr) {
+    if (e < s) xs[(size_t)a.xloc[e]] *= dinv[e];
+    else { yr[e - s] = dinv[e] * xs[e]; yc[e - s] = 0.0; }
+  }
+  __syncthreads();
+  dense_tail_apply_rf<R, RL, 2 * MI_DT_PF>(a.dt, vdt, xs + (size_t)s, yr, yc, keep, hl, first, wave, lane);
+  for (int e = tid; e < k; e += nthr) xs[(size_t)s + e] = yr[e] + yc[e];
+  __syncthreads();
 }
 
 // K solve on the LDS vector: fwd levels, D^-1, bwd levels (row E7)
@@ -884,9 +1001,13 @@ __device__ __forceinline__ void kkt_solve_lds(const KernelArgs &a, const TilePtr
 // the pass that builds the first right-hand side, x / z / y stored by the last iteration.  Only this workgroup touches
 // them in between and nobody reads them before check_kernel.  Same expressions in the same order: the results are
 // bitwise those of the streaming form.  A compile-time flag for the reason given at solve_vector.
-template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false>
+// RF (resident head of S^-1, with RS, one QP per tile, dense tail): the first MI_RF_R + MI_RF_RL steps of every wave's first
+// product task stay in registers and in LDS behind the resident state (KernelArgs::rf_off) from the call's first iteration
+// on (dense_tail_apply_rf).  A compile-time flag for the same reason.
+template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false, bool RF = false>
 __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, int n_iter) {
   static_assert(!RS || (!GX && !WIDE), "the resident state goes with the LDS solve vector");
+  static_assert(!RF || (RS && BT == 1 && NT == 1024), "the resident head goes with the resident state of a 16-wave tile of one QP");
   // multi-workgroup mode (global vector, one QP): the grid is ONE tile; thread / wave numbers run over the grid and the
   // barriers between phases are grid barriers
   const Mw mw{a.mw_bar, GX && BT == 1 && a.mw_groups > 1 ? (unsigned)a.mw_groups : 1u};
@@ -912,6 +1033,12 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
   const double *const Q = RS ? X + (size_t)n * BT : p.q, *const RI = RS ? Y + (size_t)m * BT : p.rho_inv;
   const double *const RV = RS ? RI + (size_t)m * BT : p.rho_vec, *const LO = RS ? RV + (size_t)m * BT : p.l;
   const double *const UP = RS ? LO + (size_t)m * BT : p.u, *const DI = RS ? UP + (size_t)m * BT : p.dinv;
+  double keep[RF ? MI_RF_R : 1];
+#pragma unroll
+  for (int st = 0; st < (RF ? MI_RF_R : 1); st++) keep[st] = 0.0;
+  double *hl = nullptr;
+  (void)keep; (void)hl;
+  if constexpr (RF) hl = smem + a.rf_off + (size_t)(wave * MI_RF_RL) * 64 + lane;
   // ---- E6 of the first iteration: rhs into the permuted solve vector
   for (int e = tid; e < N * BT; e += nthr) {
     const int i = e / BT;
@@ -943,7 +1070,8 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
     // ---- E7
     if constexpr (RS) {                                       // kkt_solve_lds with D^-1 from LDS
       run_tri<BT, MI_PFV_NT(NT, GX), GX, 0, WIDE>(a.fwd, p.vfwd, xs, wave, lane);
-      kkt_middle<BT, GX>(a, DI, p.vdt, p.act, xs, tid, nthr, wave, lane);
+      if constexpr (RF) kkt_middle_rf<MI_RF_R, MI_RF_RL>(a, DI, p.vdt[0], xs, keep, hl, iter == 1, tid, nthr, wave, lane);
+      else kkt_middle<BT, GX>(a, DI, p.vdt, p.act, xs, tid, nthr, wave, lane);
       run_tri<BT, MI_PFV_NT(NT, GX), GX, 0, WIDE>(a.bwd, p.vbwd, xs, wave, lane);
     } else {
       kkt_solve_lds<BT, MI_PFV_NT(NT, GX), GX, WIDE>(a, p, xs, tid, nthr, wave, nw, lane, mw);
@@ -1021,10 +1149,10 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
     if constexpr (GX) wg_or_grid_barrier(mw); else __syncthreads();
   }
 }
-template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false>
+template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false, bool RF = false>
 __global__ __launch_bounds__(NT) void iterate_kernel(KernelArgs a) {
   extern __shared__ double smem[];
-  iterate_body<BT, NT, GX, WIDE, RS>(a, smem, a.iter_end - a.iter_begin);
+  iterate_body<BT, NT, GX, WIDE, RS, RF>(a, smem, a.iter_end - a.iter_begin);
 }
 
 // E11-E14 after a segment of n_iter iterations: residuals, termination and infeasibility tests, rho estimate / update
@@ -3611,6 +3739,8 @@ hipError_t launch_advance(const KernelArgs &a, int BT, int tiles, int threads, s
   return go(&advance_kernel<4, 512>);
 }
 
+int rf_head_steps() { return MI_RF_R + MI_RF_RL; }
+int rf_lds_steps() { return MI_RF_RL; }
 hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st) {
   if (getenv("MI_OSQP_DEBUG_HIP")) fprintf(stderr, "[mi_osqp] launch_iterate: df %d wide %d xs_global %p BT %d tiles %d threads %d lds %zu groups %d bar %p\n", a.df, a.wide, (void *)a.xs_global, BT, tiles, threads, lds, a.mw_groups, (void *)a.mw_bar);
   if (a.df) { if (tiles != 1 || BT != 1 || !a.xs_global || !a.wide || !a.mw_bar || a.mw_groups < 1) return hipErrorInvalidValue; tiles = a.mw_groups; }
@@ -3625,8 +3755,13 @@ hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, s
       hipLaunchKernelGGL(kern, dim3(tiles), dim3(threads), lds, st, a);
       return hipGetLastError();
     };
+    if (a.rf_off) {     // resident head of S^-1 (lds covers its LDS part)
+      if (BT != 1 || !a.dt.k || threads != 1024) return hipErrorInvalidValue;
+      return go(&iterate_kernel<1, 1024, false, false, true, true>);
+    }
     return BT == 1 ? go(&iterate_kernel<1, 1024, false, false, true>) : go(&iterate_kernel<2, 1024, false, false, true>);
   }
+  if (a.rf_off) return hipErrorInvalidValue;
   MI_DISPATCH(iterate_kernel, a);
 }
 hipError_t launch_check(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st) {

@@ -276,6 +276,8 @@ struct mi_osqp_batch {
   size_t lds = 0;
   size_t lds_iter = 0;                        // LDS of the iterate / advance launches: lds + the resident state where it fits (rs_off != 0)
   int rs_off = 0;                             // KernelArgs::rs_off
+  size_t lds_factor = 0;                      // LDS part of the resident head of S^-1, behind the resident state (iterate launches only)
+  int rf_off = 0, rf_steps = 0;               // KernelArgs::rf_off; steps per wave the head keeps (registers + LDS), 0 = streamed
   std::vector<QPNumeric> qp;
   bool host_bounds_stale = false;
   hipStream_t stream = nullptr;
@@ -415,6 +417,17 @@ static Settings to_settings(const mi_osqp_settings *s) {
   return t;
 }
 
+// the deal of the dense-tail product over the waves of a tile (host_core.cpp build_dense_tail), for stats()
+static void dense_tail_deal_stats(const DenseTail &dt, mi_osqp_stats &s) {
+  s.dense_tail_tasks = s.dense_tail_waves_used = s.dense_tail_wave_tasks_max = 0;
+  if (!dt.k) return;
+  s.dense_tail_tasks = (int64_t)dt.task.size() / 4;
+  for (int w = 0; w < dt.nw; w++) {
+    const int64_t c = (int64_t)dt.wave_task[w + 1] - (int64_t)dt.wave_task[w];
+    s.dense_tail_waves_used += c > 0; s.dense_tail_wave_tasks_max = std::max(s.dense_tail_wave_tasks_max, c);
+  }
+}
+
 static size_t lds_bytes(int N, int BT, int threads) {
   int nw = threads / 64;
   return ((size_t)N * BT + (size_t)nw * 14 * BT + 14 * BT) * sizeof(double);
@@ -434,7 +447,7 @@ static KernelArgs make_args(mi_osqp_batch *h) {
   a.dscal = h->dscal.p; a.iscal = h->iscal.p;
   a.x_out = h->x_out.p; a.y_out = h->y_out.p;
   a.xs_global = h->global_xs ? h->xs_global.p : nullptr; a.xs_len = (*h->anp).xs_total; a.wide = (*h->anp).wide ? 1 : 0;
-  a.rs_off = h->rs_off;
+  a.rs_off = h->rs_off; a.rf_off = h->rf_off;
   a.mw_groups = h->mw_groups; a.mw_bar = h->mw_bar.p; a.mw_scratch = h->mw_scratch.p;
   a.df = (*h->anp).df ? 1 : 0; a.df_shadow = (unsigned)(*h->anp).Next; a.rflag = h->rflag.p;
   {
@@ -904,6 +917,16 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
       h->rs_off = (int)(h->lds / sizeof(double)); h->lds_iter = h->lds + state;
     }
   }
+  // Resident head of S^-1 (iterate_body RF): a tile of ONE QP with the resident state and a dense tail keeps the first
+  // rf_head_steps() steps of every wave's first product task on chip across a segment - rf_lds_steps() of them in LDS behind
+  // the resident state where that fits the cap as well, the rest in registers (no LDS part, no head: the kernel has one form).
+  h->lds_factor = 0; h->rf_off = 0; h->rf_steps = 0;
+  if (h->rs_off && BT == 1 && an.dt.k > 0 && !h->tune.stream_factor) {
+    const size_t part = (size_t)(h->threads / 64) * rf_lds_steps() * 64 * sizeof(double);
+    if (h->lds_iter + part <= lds_cap) {
+      h->rf_off = (int)(h->lds_iter / sizeof(double)); h->lds_factor = part; h->rf_steps = rf_head_steps();
+    }
+  }
   // ---- device arrays
   size_t T = (size_t)h->ntiles * BT;
   if ((rc = h->fwd.upload(an.fwd)) || (rc = h->bwd.upload(an.bwd)) || (rc = h->chk.upload(an.chk))) return rc;
@@ -1120,6 +1143,8 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
   s.nnz_L_before_tail = an.dt.k ? an.Lp[an.dt.s] : an.nnzL();
   s.solve_groups = h->mw_groups; s.solve_group_threads = h->mw_groups > 0 ? h->mw_threads : 0;
   s.resident_state = h->rs_off ? 1 : 0; s.lds_bytes_iterate = (int64_t)h->lds_iter;
+  s.resident_factor_steps = h->rf_steps; s.lds_bytes_factor = (int64_t)h->lds_factor;
+  dense_tail_deal_stats(an.dt, s);
   if (getenv("MI_OSQP_DEBUG_TIMING"))
     fprintf(stderr, "[mi_osqp] setup B=%d N=%d: analysis+alloc %.1f ms (analysis %.1f), numeric %.1f ms, upload %.1f ms, rest %.1f ms\n", (int)B, an.N,
             1e3 * (t1 - t0), 1e3 * t_analysis, 1e3 * t_factor, 1e3 * t_upload, 1e3 * (now_s() - t1 - t_factor - t_upload));
@@ -1388,7 +1413,7 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
     if (c) HIPCHK(hipStreamWaitEvent(h->pipe_i, ev_chunk(c, 2), 0));
     if (!nt) continue;
     ai.tiles = h->tile_list.p + ch.tile_begin[c];
-    HIPCHK(launch_iterate(ai, BT, nt, h->threads, h->lds_iter, h->pipe_i));
+    HIPCHK(launch_iterate(ai, BT, nt, h->threads, h->lds_iter + h->lds_factor, h->pipe_i));
   }
   HIPCHK(hipEventRecord(ev_i1, h->pipe_i));
   // ---- join (stream I has waited for every chunk of R), flags of the new factors
@@ -1456,7 +1481,7 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
         if (!iterated) {
           HIPCHK(hipEventRecord(h->ev0, h->stream));
           if (h->mw_groups > 0) HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), h->stream));
-          HIPCHK(launch_iterate(a, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds_iter, h->stream));
+          HIPCHK(launch_iterate(a, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds_iter + h->lds_factor, h->stream));
           HIPCHK(hipEventRecord(h->ev1, h->stream));
         }
         {
@@ -3308,8 +3333,10 @@ int mi_osqp_debug_host_kkt_solve(int64_t n, int64_t m, const int64_t *Pp, const 
   if (validate_settings(s)) return MI_OSQP_ERR_INVALID_SETTINGS;
   Analysis an;
   // tile > 1: the dataflow form for tile - 1 workgroups per QP (global solve vector, no dense tail)
-  const AnalysisTuning tune = tuning_from_env().analysis;
-  int rc = tile > 1 ? analyze(n, m, Pp, Pi, Ap, Ai, tune, an, 8, 1, -1, 0, (int)tile - 1) : analyze(n, m, Pp, Pi, Ap, Ai, tune, an);
+  const Tuning tu = tuning_from_env();
+  const AnalysisTuning tune = tu.analysis;
+  const int nwaves = tu.threads ? tu.threads / 64 : 8;      // (MI_OSQP_THREADS: the schedules of that many waves per tile)
+  int rc = tile > 1 ? analyze(n, m, Pp, Pi, Ap, Ai, tune, an, 8, 1, -1, 0, (int)tile - 1) : analyze(n, m, Pp, Pi, Ap, Ai, tune, an, nwaves);
   if (rc) return rc;
   QPNumeric Q;
   load_qp(an, s, Pv, nullptr, Av, l, u, Q);
@@ -3330,6 +3357,8 @@ int mi_osqp_debug_host_kkt_solve(int64_t n, int64_t m, const int64_t *Pp, const 
     st->fwd_slots = (int64_t)an.fwd.phys_steps() * 64; st->bwd_slots = (int64_t)an.bwd.phys_steps() * 64; st->chk_slots = (int64_t)an.chk.phys_steps() * 64;
     st->dense_tail_rows = an.dt.k; st->dense_tail_slots = (int64_t)an.dt.n_steps * 64;
     st->nnz_L_before_tail = an.dt.k ? an.Lp[an.dt.s] : an.nnzL();
+    st->threads_per_block = 64 * (tile > 1 ? 8 : nwaves);
+    dense_tail_deal_stats(an.dt, *st);
   }
   return MI_OSQP_OK;
 }
