@@ -77,7 +77,8 @@ typedef struct {
   int64_t verbose;                /* 0 here; the reference passes 1 (log only) */
   /* solution polishing (OSQP polish.c, README "Polishing"): after every blocking solve, each QP that ended kOptimal solves
    * the reduced KKT system of the active set guessed from its final iterate and keeps the result when its residuals are
-   * smaller.  Not available in the continuous mode: mi_osqp_batch_solve_begin_some refuses a handle with polish = 1. */
+   * smaller.  The continuous mode polishes on demand instead (mi_osqp_batch_polish_some, with polish_refine_iter and delta
+   * of the handle): mi_osqp_batch_solve_begin_some refuses a handle with polish = 1. */
   int64_t polish;                 /* 0    */
   int64_t polish_refine_iter;     /* 3    (>= 0) */
   double  delta;                  /* 1e-6 (> 0): regularisation of the reduced KKT matrix */
@@ -248,10 +249,14 @@ int mi_osqp_batch_last_solve_stats(mi_osqp_batch *h, int64_t *total_iters, int64
                                    double *device_seconds, double *refactor_seconds, int64_t *refactor_count,
                                    double *compact_seconds);
 /* Polishing of the last solve: QPs polished (those that ended kOptimal), QPs whose polished solution was accepted, and the
- * seconds the polish took on the device (HIP events: active set, polish factor, polish kernel).  Zeros without polish. */
+ * seconds the polish took on the device (HIP events: active set, polish factor, polish kernel).  Zeros without polish.
+ * In the continuous mode: the counts of the last poll() that reported polished QPs; seconds = 0 (not measured there: nothing
+ * waits for the polish). */
 int mi_osqp_batch_last_polish_stats(mi_osqp_batch *h, int64_t *polished, int64_t *accepted, double *seconds);
 /* (tests) the active set of the last polish, act[B][m]: -1 lower-active, +1 upper-active, 0 inactive (all 0 for QPs that
- * were not polished, and before the first polish). */
+ * were not polished, and before the first polish).  After mi_osqp_batch_polish_some: per QP, the active set of its last
+ * polish; in the continuous mode the call waits for the work enqueued on the handle (polishes included) and does not end
+ * the mode. */
 int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act);
 
 /* ------------------------------------------------------ continuous batching
@@ -275,6 +280,7 @@ int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act);
  *                                                              follows the launch in stream order
  *     poll(wait, ...)                                          which QPs finished in the oldest advance not polled yet
  *     get_primal_some / get_dual_some / get_info_some          results of finished QPs (host memory, no device access)
+ *     polish_some                                              polish finished kOptimal QPs on demand; reported once more
  *
  * Every QP takes exactly the iterations of a mi_osqp_batch_solve of its own: same exit code, iteration count, rho updates
  * and solution, bit for bit.  Nothing here waits for the device except poll() (and a full staging ring); at most two
@@ -301,7 +307,31 @@ int mi_osqp_batch_poll(mi_osqp_batch *h, int64_t wait, int64_t *n_finished, int6
 int mi_osqp_batch_get_primal_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, double *x_out /*[n_ids][n]*/);
 int mi_osqp_batch_get_dual_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, double *y_out /*[n_ids][m]*/);
 int mi_osqp_batch_get_info_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, mi_osqp_info *info /*[n_ids]*/);
-int64_t mi_osqp_batch_running(mi_osqp_batch *h);      /* QPs whose solve has been begun and not been reported by poll() */
+int64_t mi_osqp_batch_running(mi_osqp_batch *h);      /* QPs whose solve (or polish) has been begun and not been reported by poll() */
+/* Polish the listed QPs now (OSQP polish.c; settings polish_refine_iter and delta of the handle), without waiting for the
+ * device and without disturbing the QPs that are iterating - in an SQP loop only the last, accepted QP of a trajectory is
+ * worth the refactorisation that a polish costs.  The handle must be in the continuous mode (else MI_OSQP_ERR_INVALID_DATA).
+ * A QP is polishable from the poll() that reports it with status_val = 1 until a call changes its data or iterate or begins
+ * a solve of it (reinit_some, update_A_bounds_some, update_q_some, warm_start_x_some, warm_start_y_some, solve_begin_some,
+ * mi_gomp_relinearise_some for the QPs it updates) or polishes it: once per solve.  All or nothing: an id out of range,
+ * listed twice, still running or not polishable gives MI_OSQP_ERR_INVALID_DATA (text in mi_osqp_last_error()) and nothing
+ * is enqueued or changed.  n_ids = 0: nothing happens.  (MI_OSQP_ERR_DEVICE / _ALLOC are not refusals: part of the chain
+ * may have been enqueued.)
+ *
+ * The call enqueues, in stream order behind everything enqueued so far: the active sets of the listed QPs, their polish
+ * factors, the polish, the publication of the results.  (The first polish of a handle also allocates the polish buffers.)
+ * The listed QPs count as running again (mi_osqp_batch_running; no per-QP call accepts them) and are reported a SECOND time by
+ * the poll() of the first advance enqueued AFTER this call - that advance need not have anything to iterate; the poll() of an
+ * advance enqueued before it does not report them: the publication moves the QP's epoch, like the begin of a solve.  Then
+ * get_primal_some / get_dual_some / get_info_some return the polished x, y, obj_val, pri_res, dua_res and status_polish = 1 -
+ * or, with status_polish = -1 (the polished point was not better, or its KKT matrix not quasi-definite), those of the ADMM
+ * solve, unchanged bit for bit.  An accepted point is the QP's iterate, i.e. its next warm start.  Every result - x, y, the
+ * three scalars, status_polish, the active set - is bit for bit that of a blocking mi_osqp_batch_solve with polish = 1 on the
+ * same data.  Several calls may be enqueued before a poll.  A blocking call that ends the continuous mode finds every enqueued
+ * polish executed: the whole-batch getters return the polished solutions and status_polish. */
+int mi_osqp_batch_polish_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids);
+/* (tests) times the staging ring of the per-QP calls has wrapped since setup (a wrap waits for the handle's stream) */
+int64_t mi_osqp_batch_ring_wraps(mi_osqp_batch *h);
 
 /* ------------------------------------------- GOMP re-linearisation on the device
  * The step before and the step after the solver path in the reference's SQP loop - the re-linearised 3-D / obstacle rows

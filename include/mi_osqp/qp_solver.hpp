@@ -362,6 +362,15 @@ class ContinuousQPSolver {
     out.resize((size_t)std::max<int64_t>(nf, 0));
     return out;
   }
+  // Polish the listed slots (mi_osqp_batch_polish_some): each finished with kOptimal and untouched since, e.g. the accepted
+  // QP of an SQP loop.  Does not wait; the slots count as running and poll() reports them once more after the next
+  // advance(), then result() / last_info().status_polish are those of the polished solve.  false: refused, nothing enqueued.
+  bool polish(const std::vector<long long> &ids) {
+    if (ids.empty()) return true;
+    const int rc = mi_osqp_batch_polish_some(h_, (int64_t)ids.size(), reinterpret_cast<const int64_t *>(ids.data()));
+    if (rc != MI_OSQP_OK) std::cerr << "ContinuousQPSolver: polish refused: " << mi_osqp_error_name(rc) << " (" << mi_osqp_last_error() << ")" << std::endl;
+    return rc == MI_OSQP_OK;
+  }
   // QPSolver::solve, second half: exit code and primal solution of a finished slot
   std::pair<OsqpExitCode, QPVector> result(long long id) {
     const int64_t i = id;

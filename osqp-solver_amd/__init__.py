@@ -132,12 +132,15 @@ def lib():
         L.mi_osqp_batch_update_A_bounds_some.argtypes = [vp, C.c_int64, ip, dp, dp, dp]
         L.mi_osqp_batch_warm_start_x_some.argtypes = [vp, C.c_int64, ip, dp]
         L.mi_osqp_batch_solve_begin_some.argtypes = [vp, C.c_int64, ip]
+        L.mi_osqp_batch_polish_some.argtypes = [vp, C.c_int64, ip]
         L.mi_osqp_batch_advance.argtypes = [vp, C.c_int64]
         L.mi_osqp_batch_poll.argtypes = [vp, C.c_int64, ip, ip, C.c_int64]
         L.mi_osqp_batch_get_primal_some.argtypes = [vp, C.c_int64, ip, dp]
         L.mi_osqp_batch_get_dual_some.argtypes = [vp, C.c_int64, ip, dp]
         L.mi_osqp_batch_get_info_some.argtypes = [vp, C.c_int64, ip, C.POINTER(Info)]
         L.mi_osqp_batch_running.argtypes = [vp]; L.mi_osqp_batch_running.restype = C.c_int64
+        L.mi_osqp_batch_ring_wraps.argtypes = [vp]; L.mi_osqp_batch_ring_wraps.restype = C.c_int64
+        L.mi_osqp_release_device_cache.argtypes = []; L.mi_osqp_release_device_cache.restype = None
         L.mi_osqp_setup.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, ip, ip, dp, dp, ip, ip, dp, dp, dp, C.POINTER(Settings)]
         L.mi_osqp_update_A.argtypes = [vp, ip, ip, dp]
         L.mi_osqp_update_bounds.argtypes = [vp, dp, dp]
@@ -437,6 +440,12 @@ class BatchSolver:
         ids = _i64(ids)
         _chk(lib().mi_osqp_batch_solve_begin_some(self._h, len(ids), _ip(ids)), "solve_begin_some")
 
+    def polish_some(self, ids):
+        """Polish the listed QPs (finished kOptimal, untouched since) without waiting; they count as running and are reported
+        once more by the poll() of the next advance().  Refused as a whole (MiOsqpError, code 1) if any id does not qualify."""
+        ids = _i64(ids)
+        _chk(lib().mi_osqp_batch_polish_some(self._h, len(ids), _ip(ids)), "polish_some")
+
     def advance(self, n_segments=1):
         _chk(lib().mi_osqp_batch_advance(self._h, n_segments), "advance")
 
@@ -449,6 +458,10 @@ class BatchSolver:
 
     def running(self):
         return int(lib().mi_osqp_batch_running(self._h))
+
+    def ring_wraps(self):
+        """(tests) times the staging ring of the per-QP calls has wrapped since setup"""
+        return int(lib().mi_osqp_batch_ring_wraps(self._h))
 
     def primal_some(self, ids):
         ids = _i64(ids); x = np.empty((len(ids), self.n))

@@ -146,6 +146,10 @@ struct PolishArgs {
 };
 // active set of every kOptimal QP from its final iterate, stat = 1 for those QPs, 0 for the others
 hipError_t launch_polish_active(const KernelArgs &a, const PolishArgs &p, int BT, hipStream_t st);
+// continuous mode (mi_osqp_batch_polish_some): the active sets and marks of the listed slots only; and, behind polish_kernel,
+// their results into the pinned image host_stat[slot] (1 accepted, -1 not), marks down, epochs up (IS_EPOCH, fenced)
+hipError_t launch_polish_active_list(const KernelArgs &a, const PolishArgs &p, const int *slots, int nslots, int BT, hipStream_t st);
+hipError_t launch_polish_publish(const KernelArgs &a, const PolishArgs &p, const int *slots, int nslots, int *host_stat, int BT, hipStream_t st);
 // a = the handle's arguments with the polish factor's streams / dinv / dense-tail stream (use_work null)
 hipError_t launch_polish(const KernelArgs &a, const PolishArgs &p, int BT, int tiles, int threads, size_t lds, int n_cus, hipStream_t st);
 hipError_t launch_factor(const FactorArgs &a, int BT, int tiles, int threads, hipStream_t st);

@@ -1704,6 +1704,38 @@ __global__ void polish_active_kernel(KernelArgs a, PolishArgs pa, int BT) {
   }
   pa.act[(size_t)slot * m + j] = s;
 }
+// The same for a list of slots (continuous mode, mi_osqp_batch_polish_some): one workgroup per listed slot, the other slots'
+// active sets and marks are left alone (an earlier call's QPs may be waiting for their report).
+__global__ void polish_active_list_kernel(KernelArgs a, PolishArgs pa, const int *__restrict__ slots, int BT) {
+  const int slot = slots[blockIdx.x], m = a.m;
+  if (slot < 0 || slot >= a.B) return;
+  const size_t t = (size_t)slot / BT, b = (size_t)slot % BT;
+  const bool cand = a.iscal[(t * IS_COUNT + IS_STATUS) * BT + b] == 1;
+  for (int j = threadIdx.x; j < m; j += blockDim.x) {
+    signed char s = 0;
+    if (cand) {
+      const size_t k = (t * m + j) * BT + b;
+      const double z = a.z[k], y = a.y[k];
+      if (z - a.l[k] < -y) s = -1;
+      else if (a.u[k] - z < y) s = 1;
+    }
+    pa.act[(size_t)slot * m + j] = s;
+  }
+  if (threadIdx.x == 0) pa.stat[slot] = cand ? 1 : 0;
+}
+// End of a polish_some chain, after polish_kernel: the listed slots' results go to the pinned image poll() reads and their
+// marks are taken down (pa.stat = 1 means "to polish" to the next call's polish_kernel), then - behind a system-scope fence,
+// the polished solutions are in host memory - the slots' epochs move: the epoch validates the rest, as in start_slots_kernel.
+__global__ void polish_publish_kernel(KernelArgs a, PolishArgs pa, const int *__restrict__ slots, int nslots, int *host_stat, int BT) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nslots) return;
+  const int slot = slots[j];
+  if (slot < 0 || slot >= a.B) return;
+  host_stat[slot] = pa.stat[slot] == 1 ? 1 : -1;
+  pa.stat[slot] = 0;
+  __threadfence_system();
+  a.iscal[((size_t)(slot / BT) * IS_COUNT + IS_EPOCH) * BT + slot % BT] += 1;
+}
 
 // After the polish factor (a's streams / dinv / dense-tail stream are the polish factor's): for the QPs marked 1
 //   s = K_d^-1 b, then refine_iter rounds of  s += K_d^-1 (b - K s)      K_d = [[P + d I, A~'], [A~, -d I]], K: d = 0
@@ -3047,10 +3079,10 @@ __global__ void start_slots_kernel(KernelArgs a, const int *__restrict__ slots, 
   }
   __syncthreads();
   if (tid == 0) {
-    // the slot stays idle (IS_DONE) until an advance launch activates it: this kernel may run next to an advance launch
-    // that must not pick the QP up half-prepared.  Everything else first, the pending mark last.
-    // (An advance launch that publishes this slot's flags in between must not make the host take the slot's previous,
-    //  finished solve for the new one: the pending mark is up before the epoch moves.)
+    // the slot stays idle (IS_DONE) until the next advance launch activates it.  The handle's one stream orders this kernel
+    // against the advance launches (it never runs next to one); the order below - everything else first, then the pending
+    // mark, then the epoch - is kept so that flags published at any point between these stores could not make the host take
+    // the slot's previous, finished solve for the new one.
     is[IS_STATUS * BT + b] = -10; is[IS_ITER * BT + b] = 0; is[IS_NEED_REFACTOR * BT + b] = 0;
     is[IS_CUR * BT + b] = 0;
     if (clear[blockIdx.x]) is[IS_RHO_UPDATES * BT + b] = 0;
@@ -3786,6 +3818,16 @@ hipError_t launch_kkt_solve(const KernelArgs &a, int BT, int tiles, int threads,
 hipError_t launch_polish_active(const KernelArgs &a, const PolishArgs &p, int BT, hipStream_t st) {
   const size_t total = (size_t)a.B * ((size_t)a.m + 1);
   hipLaunchKernelGGL(polish_active_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, p, BT);
+  return hipGetLastError();
+}
+hipError_t launch_polish_active_list(const KernelArgs &a, const PolishArgs &p, const int *slots, int nslots, int BT, hipStream_t st) {
+  if (!nslots) return hipSuccess;
+  hipLaunchKernelGGL(polish_active_list_kernel, dim3(nslots), dim3(256), 0, st, a, p, slots, BT);
+  return hipGetLastError();
+}
+hipError_t launch_polish_publish(const KernelArgs &a, const PolishArgs &p, const int *slots, int nslots, int *host_stat, int BT, hipStream_t st) {
+  if (!nslots) return hipSuccess;
+  hipLaunchKernelGGL(polish_publish_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, st, a, p, slots, nslots, host_stat, BT);
   return hipGetLastError();
 }
 hipError_t launch_polish(const KernelArgs &a, const PolishArgs &p, int BT, int tiles, int threads, size_t lds, int n_cus, hipStream_t st) {

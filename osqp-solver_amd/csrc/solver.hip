@@ -369,6 +369,7 @@ struct mi_osqp_batch {
     // staging ring of the per-QP calls: regions are handed out once per call and recycled when the ring wraps (after a
     // synchronisation), so a call never waits for an earlier call's copy
     char *ring_h = nullptr; size_t ring_cap = 0, ring_h_cap = 0, ring_head = 0;
+    int64_t ring_wraps = 0;                  // times the ring has wrapped (mi_osqp_batch_ring_wraps)
     DevBuf<char> ring_d;
     DevBuf<int> work;                        // device-built refactorisation work list of an advance
     // The per-QP calls (new data, equilibration, refactorisation, warm start, begin) and the refactorisations after rho
@@ -381,6 +382,12 @@ struct mi_osqp_batch {
     double *keepA = nullptr, *keepl = nullptr, *keepu = nullptr;   // a mi_gomp_scene's QP-major copy of the raw rows: reinit / update keep it current
     DevBuf<unsigned> counter;                // tiles that have left the advance launch in flight
     unsigned *h_done = nullptr; size_t h_done_cap = 0;      // pinned: [0] sequence number of the last advance launch that is over, [1] tiles that iterated in it
+    // polishing on demand (mi_osqp_batch_polish_some).  Per QP: polishable = poll() reported its solve kOptimal and nothing has
+    // touched it since; polishing = a polish is enqueued and not reported yet (the QP counts as running); pol_status = the
+    // status_polish of its last solve.  h_pstat: pinned [slot] image polish_publish_kernel writes the results into.
+    std::vector<char> polishable, polishing;
+    std::vector<int> pol_status;
+    int *h_pstat = nullptr; size_t h_pstat_cap = 0;
   } cont;
   ~mi_osqp_batch() {
     DevGuard guard(device);
@@ -390,7 +397,7 @@ struct mi_osqp_batch {
     if (cont.ev_adv) (void)hipEventDestroy(cont.ev_adv);
     if (evp0) (void)hipEventDestroy(evp0);
     if (evp1) (void)hipEventDestroy(evp1);
-    hostpool::give(cont.h_done, cont.h_done_cap);
+    hostpool::give(cont.h_done, cont.h_done_cap); hostpool::give(cont.h_pstat, cont.h_pstat_cap);
     hostpool::give(h_iscal, h_iscal_cap); hostpool::give(h_dscal, h_dscal_cap); hostpool::give(pin, pin_cap); hostpool::give(h_npos, h_npos_cap);
     if (pipe_r) (void)hipStreamSynchronize(pipe_r);
     if (pipe_i) (void)hipStreamSynchronize(pipe_i);
@@ -1293,27 +1300,33 @@ static int refactor_qps(mi_osqp_batch *h, std::vector<int> qps) {
 }
 
 // ------------------------------------------------------------------- polish
+// the polish buffers of a handle, allocated at its first polish (the blocking polish below and mi_osqp_batch_polish_some)
+static int ensure_polish_buffers(mi_osqp_batch *h) {
+  if (h->pol_stat.p) return MI_OSQP_OK;
+  const Analysis &an = (*h->anp);
+  const size_t T = (size_t)h->ntiles * h->BT;
+  int rc;
+  if ((rc = h->pol_fwd.alloc(h->fwd_val.n)) || (rc = h->pol_fwd.zero(h->stream)) || (rc = h->pol_bwd.alloc(h->bwd_val.n)) ||
+      (rc = h->pol_bwd.zero(h->stream)) || (rc = h->pol_dinv.alloc(h->dinv.n)) || (rc = h->pol_dinv.zero(h->stream)) ||
+      (rc = h->pol_sol.alloc(T * an.N)) || (rc = h->pol_act.alloc(std::max<size_t>(1, T * an.m))) || (rc = h->pol_act.zero(h->stream)) ||
+      (rc = h->pol_stat.alloc(T)) || (rc = h->pol_stat.zero(h->stream))) return rc;
+  if (an.dt.k && ((rc = h->pol_dt.alloc(h->dt_val.n)) || (rc = h->pol_dt.zero(h->stream)))) return rc;
+  if (!h->evp0) HIPCHK(hipEventCreate(&h->evp0));
+  if (!h->evp1) HIPCHK(hipEventCreate(&h->evp1));
+  return MI_OSQP_OK;
+}
+
 // Solution polishing after a blocking solve (OSQP polish.c on the scaled data): the active set of
 // every kOptimal QP (polish_active_kernel), the reduced KKT matrix of those QPs factored in the handle's own pattern into
 // the polish buffers (device_refactor_slots in polish mode: same work list / grouped workgroups / dense tail as a
 // refactorisation), then polish_kernel: solve + refinement, projection, residuals, acceptance and write-back.  `a` = the
 // solve's arguments (its x_out receives the polished solutions).  No per-QP host work beyond the work list.
 static int polish_impl(mi_osqp_batch *h, const KernelArgs &a) {
-  const Analysis &an = (*h->anp);
   const int BT = h->BT, ntl = h->ntiles;
-  const size_t T = (size_t)ntl * BT;
   int rc;
   h->pol_count = h->pol_accepted = 0; h->pol_seconds = 0.0;
   h->pol_status.assign((size_t)h->B, 0);
-  if (!h->pol_stat.p) {
-    if ((rc = h->pol_fwd.alloc(h->fwd_val.n)) || (rc = h->pol_fwd.zero(h->stream)) || (rc = h->pol_bwd.alloc(h->bwd_val.n)) ||
-        (rc = h->pol_bwd.zero(h->stream)) || (rc = h->pol_dinv.alloc(h->dinv.n)) || (rc = h->pol_dinv.zero(h->stream)) ||
-        (rc = h->pol_sol.alloc(T * an.N)) || (rc = h->pol_act.alloc(std::max<size_t>(1, T * an.m))) || (rc = h->pol_act.zero(h->stream)) ||
-        (rc = h->pol_stat.alloc(T)) || (rc = h->pol_stat.zero(h->stream))) return rc;
-    if (an.dt.k && ((rc = h->pol_dt.alloc(h->dt_val.n)) || (rc = h->pol_dt.zero(h->stream)))) return rc;
-    if (!h->evp0) HIPCHK(hipEventCreate(&h->evp0));
-    if (!h->evp1) HIPCHK(hipEventCreate(&h->evp1));
-  }
+  if ((rc = ensure_polish_buffers(h))) return rc;
   std::vector<int> work;                // the QPs that ended kOptimal (h_iscal: copied at the end of the solve)
   for (int q = 0; q < h->B; q++)
     if (h->h_iscal[(size_t)(q / BT) * IS_COUNT * BT + IS_STATUS * BT + q % BT] == 1) work.push_back(q);
@@ -1564,6 +1577,7 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
     h->last_total_iters += h->h_iscal[(size_t)(qi / BT) * IS_COUNT * BT + IS_ITER * BT + qi % BT];
   h->solved_once = true;
   if (h->st.polish && (rc = polish_impl(h, a))) return rc;
+  if (!h->st.polish) { h->pol_status.clear(); h->pol_count = h->pol_accepted = 0; }      // (what polish_some left: every QP has been solved again)
   return MI_OSQP_OK;
 }
 
@@ -1720,6 +1734,7 @@ int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act) {
   const size_t cnt = (size_t)h->B * (*h->anp).m;
   if (!h->pol_act.p) { memset(act, 0, cnt); return MI_OSQP_OK; }
   DevGuard guard(h->device);
+  if (h->cont.on) HIPCHK(hipStreamSynchronize(h->stream));      // (polish_some only enqueues; the continuous mode goes on)
   if (cnt) HIPCHK(hipMemcpy(act, h->pol_act.p, cnt, hipMemcpyDeviceToHost));
   return MI_OSQP_OK;
 }
@@ -2430,6 +2445,9 @@ static int cont_enter(mi_osqp_batch *h) {
   c.L = segment_length(h->st);
   c.running.assign((size_t)B, 0); c.clear_rho.assign((size_t)B, 0); c.epoch.assign((size_t)B, 0);
   c.info.assign((size_t)B, mi_osqp_info{});
+  c.polishable.assign((size_t)B, 0); c.polishing.assign((size_t)B, 0);
+  c.pol_status.assign((size_t)B, 0);
+  if (!h->st.polish && h->pol_status.size() == (size_t)B) c.pol_status = h->pol_status;      // (an earlier continuous phase polished)
   c.n_running = 0; c.adv_seq = c.polled_seq = 0; c.launch_seq = 0;
   const size_t icnt = (size_t)h->ntiles * IS_COUNT * BT;
   { const int rc0 = ensure_advance_buffers(h); if (rc0) return rc0; }
@@ -2495,6 +2513,15 @@ static int cont_leave(mi_osqp_batch *h) {
   // the solutions of the finished QPs, for the whole-batch getters
   HIPCHK(hipMemcpy(h->x_out.p, c.xh, (size_t)h->B * (*h->anp).n * sizeof(double), hipMemcpyHostToDevice));
   if ((*h->anp).m) HIPCHK(hipMemcpy(h->y_out.p, c.yh, (size_t)h->B * (*h->anp).m * sizeof(double), hipMemcpyHostToDevice));
+  // every enqueued polish has run: those not reported yet have their result in the pinned image
+  if (!h->st.polish) {
+    bool any = !h->pol_status.empty();
+    for (int q = 0; q < h->B; q++) {
+      if (c.polishing[(size_t)q]) c.pol_status[(size_t)q] = c.h_pstat[q];
+      any = any || c.pol_status[(size_t)q] != 0;
+    }
+    if (any) h->pol_status = c.pol_status;
+  }
   c.on = false; c.n_running = 0;
   h->host_bounds_stale = h->host_rho_stale = true;
   return MI_OSQP_OK;
@@ -2506,7 +2533,7 @@ static int ring_take(mi_osqp_batch *h, size_t bytes, RingSpan &out) {
   mi_osqp_batch::Cont &c = h->cont;
   bytes = (bytes + 255) & ~(size_t)255;
   if (bytes > c.ring_cap) { g_last_error = "per-QP call larger than the staging ring"; return MI_OSQP_ERR_ALLOC; }
-  if (c.ring_head + bytes > c.ring_cap) { HIPCHK(hipStreamSynchronize(h->stream)); c.ring_head = 0; }      // everything handed out so far has been consumed
+  if (c.ring_head + bytes > c.ring_cap) { HIPCHK(hipStreamSynchronize(h->stream)); c.ring_head = 0; c.ring_wraps++; }      // everything handed out so far has been consumed
   out.host = c.ring_h + c.ring_head; out.dev = c.ring_d.p + c.ring_head;
   c.ring_head += bytes;
   return MI_OSQP_OK;
@@ -2520,7 +2547,7 @@ static int ring_reserve(mi_osqp_batch *h, size_t bytes, int spans) {
   mi_osqp_batch::Cont &c = h->cont;
   bytes += (size_t)256 * (size_t)spans;
   if (bytes > c.ring_cap) { g_last_error = "per-QP call larger than the staging ring"; return MI_OSQP_ERR_ALLOC; }
-  if (c.ring_head + bytes > c.ring_cap) { HIPCHK(hipStreamSynchronize(h->stream)); c.ring_head = 0; }
+  if (c.ring_head + bytes > c.ring_cap) { HIPCHK(hipStreamSynchronize(h->stream)); c.ring_head = 0; c.ring_wraps++; }
   return MI_OSQP_OK;
 }
 static int ring_upload(mi_osqp_batch *h, const RingSpan &sp, size_t bytes) {
@@ -2570,13 +2597,19 @@ static int snapshot_some(mi_osqp_batch *h, const int *d_ids, int nq, hipStream_t
 }
 
 // the refactorisation kernels for a device-resident work list of `count` entries (slots, -1 = none): one QP per workgroup,
-// no group sharing (other handles' kernels may hold the CUs: nothing here may spin on a co-resident partner)
-static int enqueue_refactor_list(mi_osqp_batch *h, const int *d_work, int count) {
+// no group sharing (other handles' kernels may hold the CUs: nothing here may spin on a co-resident partner).
+// pol != null: the polish factor of the listed slots instead, as in device_refactor_slots: into the polish buffers; the ADMM
+// factor, the rho vectors and the flags stay as they are, a wrong inertia sets pol->stat[slot] = -1.
+static int enqueue_refactor_list(mi_osqp_batch *h, const int *d_work, int count, const PolishArgs *pol = nullptr) {
   if (count <= 0) return MI_OSQP_OK;
   const Analysis &an = (*h->anp);
   hipStream_t st = h->stream;
   FactorArgs fa = make_factor_args(h, 0);
   fa.work = d_work; fa.mw_groups = 0;
+  if (pol) {
+    fa.pmask = pol->act; fa.arow = h->rz_arow.p; fa.pstat = pol->stat; fa.pdelta = h->st.delta; fa.sigma = h->st.delta;
+    fa.fwd_val = h->pol_fwd.p; fa.bwd_val = h->pol_bwd.p; fa.dinv = h->pol_dinv.p; fa.use_work = nullptr;
+  }
   HIPCHK(launch_factor(fa, 1, count, h->tune.factor_threads, st));
   if (an.dt.k) {
     const DenseTail &dt = an.dt;
@@ -2589,6 +2622,7 @@ static int enqueue_refactor_list(mi_osqp_batch *h, const int *d_work, int count)
     da.asm_q64 = h->dt_asm_q64.p; da.diag_tile = h->dt_diag_tile.p; da.src_tile = h->dt_src_tile.p;
     da.Lblk = fa.Lblk; da.Dl = fa.Dl; da.Sd = h->dt_Sd.p; da.dt_val = h->dt_val.p; da.dinv = h->dinv.p; da.npos = h->npos.p; da.iscal = h->iscal.p;
     da.trace = nullptr;
+    if (pol) { da.dt_val = h->pol_dt.p; da.dinv = h->pol_dinv.p; da.pstat = pol->stat; }
     HIPCHK(launch_tail(da, count, h->dt_lds_asm, h->dt_lds, st));
   }
   return MI_OSQP_OK;
@@ -2637,7 +2671,7 @@ static int cont_new_data(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, co
   HIPCHK(launch_scatter(r.pa_out, h->chk_val.p, h->chk.src.p, d_ids, nq, pa_len, h->chk.view(an.chk), h->BT, us));
   if ((rc = enqueue_refactor_list(h, d_ids, nq))) return rc;
   if ((rc = snapshot_some(h, d_ids, nq, us))) return rc;
-  for (int64_t j = 0; j < n_ids; j++) { h->cont.clear_rho[(size_t)ids[j]] = 1; h->failed[(size_t)ids[j]] = 0; }
+  for (int64_t j = 0; j < n_ids; j++) { h->cont.clear_rho[(size_t)ids[j]] = 1; h->failed[(size_t)ids[j]] = 0; h->cont.polishable[(size_t)ids[j]] = 0; }
   h->host_scaling_stale = true; h->host_bounds_stale = true; h->host_rho_stale = true;
   return MI_OSQP_OK;
 }
@@ -2682,6 +2716,7 @@ int mi_osqp_batch_warm_start_x_some(mi_osqp_batch *h, int64_t n_ids, const int64
   KernelArgs a = make_args(h);
   a.sel = d_sel;
   HIPCHK(launch_warm_start(a, h->BT, h->ntiles, h->threads, h->lds, h->stream, (const double *)sp.dev));
+  for (int64_t j = 0; j < n_ids; j++) h->cont.polishable[(size_t)ids[j]] = 0;
   return MI_OSQP_OK;
 }
 
@@ -2703,7 +2738,7 @@ int mi_osqp_batch_update_q_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *
   if ((rc = ring_upload(h, sp, cnt * sizeof(double)))) return rc;
   HIPCHK(launch_lin_cost((const double *)sp.dev, d_ids, h->q.p, h->rawq.p, h->Dsc.p, h->dscal.p, (int)n_ids, n, h->BT,
                          h->st.scaling ? 1 : 0, h->stream));
-  for (int64_t j = 0; j < n_ids; j++) h->cont.clear_rho[(size_t)ids[j]] = 1;
+  for (int64_t j = 0; j < n_ids; j++) { h->cont.clear_rho[(size_t)ids[j]] = 1; h->cont.polishable[(size_t)ids[j]] = 0; }
   h->host_scaling_stale = true;
   return MI_OSQP_OK;
 }
@@ -2727,6 +2762,7 @@ int mi_osqp_batch_warm_start_y_some(mi_osqp_batch *h, int64_t n_ids, const int64
   KernelArgs a = make_args(h);
   a.sel = d_sel;
   HIPCHK(launch_warm_start_y(a, h->ntiles * h->BT, h->BT, h->stream, (const double *)sp.dev));
+  for (int64_t j = 0; j < n_ids; j++) h->cont.polishable[(size_t)ids[j]] = 0;
   return MI_OSQP_OK;
 }
 
@@ -2755,6 +2791,65 @@ int mi_osqp_batch_solve_begin_some(mi_osqp_batch *h, int64_t n_ids, const int64_
   for (int64_t j = 0; j < n_ids; j++) {
     const size_t q = (size_t)ids[j];
     if (!c.running[q]) { c.running[q] = 1; c.n_running++; }
+    c.epoch[q]++;
+    c.polishable[q] = 0; c.pol_status[q] = 0;
+  }
+  return MI_OSQP_OK;
+}
+
+// Polish the listed QPs - finished, reported kOptimal by poll() and untouched since - without waiting for the device
+// (mi_osqp.h): active set of the listed slots, their polish factors (one QP per workgroup, the list path of the
+// refactorisations), polish_kernel over the tiles (a tile without a marked QP leaves at once; the tile partner of a polished
+// QP may be in the middle of its solve: the kernel stores to the marked QPs only, and the tile scratch it uses - out1, out2,
+// pol_sol - is ordered against the advance launches by the stream), publication.  All or nothing as far as refusals go: a
+// refused call has enqueued and changed nothing (a HIP error in the middle of the chain is not a refusal: like every
+// MI_OSQP_ERR_DEVICE it leaves the handle's device state undefined, here with marks that may still be up).  The QPs count as running until the poll of the next advance reports them a second time: the epoch
+// the publication kernel moves is what tells that report from the one of the solve (an advance enqueued BEFORE this call
+// publishes the old epoch and reports nothing).  The marks (pol_stat = 1) are up only within one call's chain, so a second
+// call before the report neither polishes the first call's QPs again nor loses their results (the pinned image keeps them).
+int mi_osqp_batch_polish_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids) {
+  CallTimer timer_("batch_polish_some");
+  if (!h || (n_ids > 0 && !ids)) return MI_OSQP_ERR_NULL;
+  mi_osqp_batch::Cont &c = h->cont;
+  if (!c.on) { g_last_error = "polish_some: the handle is not in the continuous mode"; return MI_OSQP_ERR_INVALID_DATA; }
+  if (n_ids < 0 || n_ids > h->B) { g_last_error = "polish_some: more ids than QPs"; return MI_OSQP_ERR_INVALID_DATA; }
+  if (!n_ids) return MI_OSQP_OK;
+  {
+    std::vector<char> seen((size_t)h->B, 0);
+    for (int64_t j = 0; j < n_ids; j++) {
+      const int64_t q = ids[j];
+      const char *why = nullptr;
+      if (q < 0 || q >= h->B) why = " is out of range";
+      else if (seen[(size_t)q]) why = " is listed twice";
+      else if (c.running[(size_t)q]) why = " is still running";
+      else if (!c.polishable[(size_t)q]) why = " is not polishable (not reported kOptimal, changed since, or polished already)";
+      if (why) { g_last_error = "polish_some: QP " + std::to_string(q) + why; return MI_OSQP_ERR_INVALID_DATA; }
+      seen[(size_t)q] = 1;
+    }
+  }
+  DevGuard guard(h->device);
+  int rc;
+  const int BT = h->BT, nq = (int)n_ids;
+  if ((rc = ensure_polish_buffers(h))) return rc;           // (the one-time allocation: the only thing here that may wait)
+  if (!c.h_pstat) {
+    HIPCHK(hostpool::alloc((void **)&c.h_pstat, (size_t)h->ntiles * BT * sizeof(int), &c.h_pstat_cap));
+    for (int s = 0; s < h->ntiles * BT; s++) c.h_pstat[s] = 0;
+  }
+  int *d_ids = nullptr;
+  if ((rc = cont_stage_ids(h, n_ids, ids, &d_ids, nullptr))) return rc;
+  KernelArgs a = make_args(h);
+  a.x_out = c.xh; a.y_out = c.yh;
+  PolishArgs pa{h->pol_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter};
+  HIPCHK(launch_polish_active_list(a, pa, d_ids, nq, BT, h->stream));
+  if ((rc = enqueue_refactor_list(h, d_ids, nq, &pa))) return rc;
+  KernelArgs ap = a;
+  ap.fwd_val = h->pol_fwd.p; ap.bwd_val = h->pol_bwd.p; ap.dinv = h->pol_dinv.p; ap.dt_val = h->pol_dt.p; ap.use_work = nullptr;
+  HIPCHK(launch_polish(ap, pa, BT, h->ntiles, h->threads, h->lds, h->n_cus, h->stream));
+  HIPCHK(launch_polish_publish(a, pa, d_ids, nq, c.h_pstat, BT, h->stream));
+  for (int64_t j = 0; j < n_ids; j++) {
+    const size_t q = (size_t)ids[j];
+    c.polishable[q] = 0; c.polishing[q] = 1;
+    c.running[q] = 1; c.n_running++;
     c.epoch[q]++;
   }
   return MI_OSQP_OK;
@@ -2825,7 +2920,7 @@ int mi_osqp_batch_poll(mi_osqp_batch *h, int64_t wait, int64_t *n_finished, int6
     return ti[IS_DONE * BT + b] != 0 && ti[IS_PENDING * BT + b] == 0 && ti[IS_EPOCH * BT + b] == c.epoch[(size_t)q];
   };
   // (the caller's buffer must take every finished QP of this advance: with less room nothing is consumed)
-  int64_t would = 0;
+  int64_t would = 0, n_pol = 0, n_acc = 0;
   for (int q = 0; q < h->B; q++) would += finished(q) ? 1 : 0;
   if (would > capacity || (would > 0 && !ids_out)) { *n_finished = would; g_last_error = "poll: ids_out too small"; return MI_OSQP_ERR_INVALID_DATA; }
   for (int q = 0; q < h->B; q++) {
@@ -2838,9 +2933,19 @@ int mi_osqp_batch_poll(mi_osqp_batch *h, int64_t wait, int64_t *n_finished, int6
     I.obj_val = td[DS_OBJ * BT + b]; I.pri_res = td[DS_PRI_RES * BT + b]; I.dua_res = td[DS_DUA_RES * BT + b];
     I.rho_updates = ti[IS_RHO_UPDATES * BT + b]; I.rho_estimate = td[DS_RHO_EST * BT + b]; I.rho = td[DS_RHO * BT + b];
     if (ti[IS_NEED_REFACTOR * BT + b] < 0) h->failed[(size_t)q] = 1;
+    if (c.polishing[(size_t)q]) {      // the second report of a polished QP: (the image is valid: the epoch moved after it was written)
+      c.polishing[(size_t)q] = 0;
+      c.pol_status[(size_t)q] = c.h_pstat[q];
+      n_pol++; n_acc += c.h_pstat[q] == 1;
+    } else {
+      c.pol_status[(size_t)q] = 0;
+      c.polishable[(size_t)q] = I.status_val == 1;
+    }
+    I.status_polish = c.pol_status[(size_t)q];
     c.running[q] = 0; c.n_running--;
     ids_out[nf++] = q;
   }
+  if (n_pol) { h->pol_count = n_pol; h->pol_accepted = n_acc; h->pol_seconds = 0.0; }
   c.polled_seq = seq;
   *n_finished = nf;
   return MI_OSQP_OK;
@@ -2876,6 +2981,7 @@ int mi_osqp_batch_get_info_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *
   return MI_OSQP_OK;
 }
 int64_t mi_osqp_batch_running(mi_osqp_batch *h) { return h && h->cont.on ? h->cont.n_running : 0; }
+int64_t mi_osqp_batch_ring_wraps(mi_osqp_batch *h) { return h ? h->cont.ring_wraps : 0; }
 
 }  // extern "C"
 
