@@ -171,6 +171,9 @@ int mi_osqp_solve(mi_osqp_solver *h, mi_osqp_info *info);
 int mi_osqp_get_primal(mi_osqp_solver *h, double *x_out);
 int mi_osqp_get_dual(mi_osqp_solver *h, double *y_out);
 int mi_osqp_get_stats(mi_osqp_solver *h, mi_osqp_stats *st);
+/* Settings after setup (see "settings updates" below); a large single QP - one workgroup or the dataflow grid - included. */
+int mi_osqp_get_settings(mi_osqp_solver *h, mi_osqp_settings *out);
+int mi_osqp_update_settings(mi_osqp_solver *h, const mi_osqp_settings *s);
 void mi_osqp_free(mi_osqp_solver *h);
 
 /* --------------------------------------------------------------------- batch
@@ -259,6 +262,39 @@ int mi_osqp_batch_last_polish_stats(mi_osqp_batch *h, int64_t *polished, int64_t
  * the mode. */
 int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act);
 
+/* ---------------------------------------------------------- settings updates
+ * OSQP 0.6.x osqp_update_* (README "Settings updates").  update_settings takes a whole struct - get, change fields, update:
+ *   changeable  rho, max_iter, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, alpha, scaled_termination, check_termination,
+ *               warm_start, polish, polish_refine_iter, delta, verbose (the fields with an osqp_update_*);
+ *   fixed       sigma, scaling, adaptive_rho, adaptive_rho_interval, adaptive_rho_tolerance must be those in force
+ *               (adaptive_rho_interval = 0 is also accepted where setup derived the interval from 0).
+ * A struct that differs in a fixed field, or whose values setup would refuse, gives MI_OSQP_ERR_INVALID_SETTINGS: nothing is
+ * changed, no device is touched, the reason is in mi_osqp_last_error().  mi_osqp_settings_update_check is that decision as a
+ * host function of two structs (it cannot know where an interval came from and accepts 0 against any interval in force).
+ * get_settings returns the settings in force: the resolved adaptive_rho_interval, the clamped rho of the last scalar update -
+ * not the rho a QP has adapted to, which mi_osqp_info.rho reports.
+ *
+ * Fields other than rho take effect at the next solve; nothing on the device changes: iterates, every QP's rho, the factor
+ * and the count of rho updates are kept.  A changed check_termination does not move adaptive_rho_interval (derived at setup).
+ * A rho that differs from the settings' rho is osqp_update_rho: settings.rho = min(max(rho, 1e-6), 1e6), every QP's rho
+ * becomes that value and every QP is refactored on the device with the rho vector derived from it (equality rows 1e3 * rho,
+ * free rows at the minimum); iterates and the count of rho updates are kept, the state mi_osqp_batch_reset returns to is
+ * retaken, mi_osqp_batch_reinit_some starts from the new settings.rho.  A QP whose new KKT matrix loses its inertia ends its
+ * next solve as kNonConvex; the others are not affected.
+ * update_rho_each / update_rho_some: the same with one value per QP (clamped likewise); settings.rho is not touched.  A value
+ * that is not > 0 (NaN included) gives MI_OSQP_ERR_INVALID_SETTINGS and nothing changes.
+ *
+ * Continuous mode: update_rho_some is one of its per-QP calls (idle QPs, ids in range and not repeated, else
+ * MI_OSQP_ERR_INVALID_DATA; all or nothing; enqueued in stream order, nothing waits).  update_settings is refused with
+ * MI_OSQP_ERR_INVALID_DATA while mi_osqp_batch_running() > 0 and otherwise accepted without leaving the mode (a new rho is
+ * applied like update_rho_some over all QPs; polish = 1 is stored, and solve_begin_some goes on refusing such a handle).
+ * update_rho_each and the multi-batch forms end the continuous mode like every blocking call. */
+int mi_osqp_settings_update_check(const mi_osqp_settings *in_force, const mi_osqp_settings *wanted);   /* host only */
+int mi_osqp_batch_get_settings(mi_osqp_batch *h, mi_osqp_settings *out);
+int mi_osqp_batch_update_settings(mi_osqp_batch *h, const mi_osqp_settings *s);
+int mi_osqp_batch_update_rho_each(mi_osqp_batch *h, const double *rho /*[B]*/);
+int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *rho /*[n_ids]*/);
+
 /* ------------------------------------------------------ continuous batching
  * The reference's SQP loop is per trajectory: solve -> check -> re-linearise -> update -> solve again
  * ([REF] src/gomp-solver.h:70-88), with a fresh QPSolver per horizon segment ([REF] src/gomp-solver.h:61-65).  The QPs of a
@@ -281,6 +317,7 @@ int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act);
  *     poll(wait, ...)                                          which QPs finished in the oldest advance not polled yet
  *     get_primal_some / get_dual_some / get_info_some          results of finished QPs (host memory, no device access)
  *     polish_some                                              polish finished kOptimal QPs on demand; reported once more
+ *     update_rho_some                                          a new rho for QPs that are not iterating ("settings updates")
  *
  * Every QP takes exactly the iterations of a mi_osqp_batch_solve of its own: same exit code, iteration count, rho updates
  * and solution, bit for bit.  Nothing here waits for the device except poll() (and a full staging ring); at most two
@@ -313,6 +350,7 @@ int64_t mi_osqp_batch_running(mi_osqp_batch *h);      /* QPs whose solve (or pol
  * worth the refactorisation that a polish costs.  The handle must be in the continuous mode (else MI_OSQP_ERR_INVALID_DATA).
  * A QP is polishable from the poll() that reports it with status_val = 1 until a call changes its data or iterate or begins
  * a solve of it (reinit_some, update_A_bounds_some, update_q_some, warm_start_x_some, warm_start_y_some, solve_begin_some,
+ * update_rho_some - and update_settings with a new rho, for every QP -,
  * mi_gomp_relinearise_some for the QPs it updates) or polishes it: once per solve.  All or nothing: an id out of range,
  * listed twice, still running or not polishable gives MI_OSQP_ERR_INVALID_DATA (text in mi_osqp_last_error()) and nothing
  * is enqueued or changed.  n_ids = 0: nothing happens.  (MI_OSQP_ERR_DEVICE / _ALLOC are not refusals: part of the chain
@@ -392,6 +430,10 @@ int mi_osqp_multi_batch_update_P(mi_osqp_multi *h, const int64_t *P_colptr, cons
 int mi_osqp_multi_batch_update_P_A(mi_osqp_multi *h, const int64_t *P_colptr, const int64_t *P_rowidx, const double *P_val,
                                    const int64_t *A_colptr, const int64_t *A_rowidx, const double *A_val);    /* osqp_update_P_A */
 int mi_osqp_multi_batch_warm_start_y(mi_osqp_multi *h, const double *y);                           /* osqp_warm_start_y */
+/* settings updates, fanned out per shard (all shards hold the same settings; a refusal changes no shard) */
+int mi_osqp_multi_batch_get_settings(mi_osqp_multi *h, mi_osqp_settings *out);
+int mi_osqp_multi_batch_update_settings(mi_osqp_multi *h, const mi_osqp_settings *s);
+int mi_osqp_multi_batch_update_rho_each(mi_osqp_multi *h, const double *rho /*[B]*/);
 int mi_osqp_multi_batch_solve(mi_osqp_multi *h);
 /* The same without waiting (every shard has one long-lived worker thread; all calls of this section run on them): solve_async
  * returns once the shards have their job, wait() joins them and returns the first shard error.  Any other multi-batch call

@@ -130,6 +130,14 @@ class QPSolver {
     return {static_cast<OsqpExitCode>(info.exit_code), x};
   }
 
+  // Not in the reference: settings after construction (mi_osqp.h "settings updates" - get, change fields, update).  Throws
+  // std::invalid_argument, like update(), for a struct the core refuses; nothing has changed then.
+  mi_osqp_settings settings() const { mi_osqp_settings s; mi_osqp_default_settings(&s); (void)mi_osqp_get_settings(h_, &s); return s; }
+  void updateSettings(const mi_osqp_settings &s) {
+    const int rc = mi_osqp_update_settings(h_, &s);
+    if (rc != MI_OSQP_OK) throw std::invalid_argument(std::string(mi_osqp_error_name(rc)) + " (" + mi_osqp_last_error() + ")");
+  }
+
   int setup_status() const { return status_; }
   const mi_osqp_info &last_info() const { return last_; }
 
@@ -264,6 +272,20 @@ class BatchQPSolver {
     return mi_osqp_batch_update_bounds(h_, lbuf_.data(), ubuf_.data()) == MI_OSQP_OK;
   }
 
+  // settings after construction, as QPSolver::updateSettings; updateRho: one rho per QP, every QP refactored
+  mi_osqp_settings settings() const { mi_osqp_settings s; mi_osqp_default_settings(&s); (void)mi_osqp_batch_get_settings(h_, &s); return s; }
+  void updateSettings(const mi_osqp_settings &s) {
+    const bool new_rho = s.rho != settings().rho;
+    const int rc = mi_osqp_batch_update_settings(h_, &s);
+    if (rc != MI_OSQP_OK) throw std::invalid_argument(std::string(mi_osqp_error_name(rc)) + " (" + mi_osqp_last_error() + ")");
+    if (new_rho) pristine_ = false;          // (the snapshot has been retaken with the new rho: reinit() no longer applies)
+  }
+  void updateRho(const std::vector<double> &rho) {
+    const int rc = (long long)rho.size() == K_ ? mi_osqp_batch_update_rho_each(h_, rho.data()) : (int)MI_OSQP_ERR_INVALID_DATA;
+    if (rc != MI_OSQP_OK) throw std::invalid_argument(std::string(mi_osqp_error_name(rc)) + " (" + mi_osqp_last_error() + ")");
+    pristine_ = false;
+  }
+
   int setup_status() const { return status_; }
   const std::vector<mi_osqp_info> &last_infos() const { return infos_; }
   long long size() const { return K_; }
@@ -369,6 +391,15 @@ class ContinuousQPSolver {
     if (ids.empty()) return true;
     const int rc = mi_osqp_batch_polish_some(h_, (int64_t)ids.size(), reinterpret_cast<const int64_t *>(ids.data()));
     if (rc != MI_OSQP_OK) std::cerr << "ContinuousQPSolver: polish refused: " << mi_osqp_error_name(rc) << " (" << mi_osqp_last_error() << ")" << std::endl;
+    return rc == MI_OSQP_OK;
+  }
+  // A new rho for the listed idle slots (mi_osqp_batch_update_rho_some): refactored in stream order, nothing waits; the slots
+  // stop being polishable.  false: refused (a slot running, listed twice or out of range, a rho that is not > 0), nothing enqueued.
+  bool updateRho(const std::vector<long long> &ids, const std::vector<double> &rho) {
+    if (ids.empty() && rho.empty()) return true;
+    const int rc = ids.size() == rho.size() ? mi_osqp_batch_update_rho_some(h_, (int64_t)ids.size(), reinterpret_cast<const int64_t *>(ids.data()), rho.data())
+                                            : (int)MI_OSQP_ERR_INVALID_DATA;
+    if (rc != MI_OSQP_OK) std::cerr << "ContinuousQPSolver: rho update refused: " << mi_osqp_error_name(rc) << " (" << mi_osqp_last_error() << ")" << std::endl;
     return rc == MI_OSQP_OK;
   }
   // QPSolver::solve, second half: exit code and primal solution of a finished slot

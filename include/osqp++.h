@@ -19,6 +19,13 @@
 // Statuses as upstream: kFailedPrecondition before a successful Init, kInvalidArgument for a wrong length or shape or a
 // changed sparsity pattern (the core extracts the upper triangle of an objective matrix given with both).
 //
+// The fourteen settings updates of osqp-cpp - UpdateRho, UpdateMaxIter, UpdateEpsAbs, UpdateEpsRel, UpdateEpsPrimInf,
+// UpdateEpsDualInf, UpdateAlpha, UpdateDelta, UpdatePolish, UpdatePolishRefineIter, UpdateWarmStart, UpdateScaledTermination,
+// UpdateCheckTermination, UpdateTimeLimit - go through mi_osqp_get_settings / mi_osqp_update_settings (README "Settings
+// updates"): kFailedPrecondition before a successful Init, kInvalidArgument for a value the core refuses (nothing changes).
+// UpdateRho refactors the KKT matrix on the device; the others take effect at the next Solve.  UpdateTimeLimit validates
+// (>= 0) and stores the value, which is then ignored like the time_limit given to Init.
+//
 // polish, polish_refine_iter and delta map onto the core's solution polishing (mi_osqp_settings, README "Polishing").
 // Settings that the MI355X core does not implement are validated like upstream and otherwise ignored: time_limit,
 // adaptive_rho_fraction (the wall-clock rule; the deterministic interval 4 * check_termination stands in for "auto",
@@ -121,7 +128,7 @@ class OsqpSolver {
   OsqpSolver() = default;
   OsqpSolver(OsqpSolver &&o) noexcept { *this = std::move(o); }
   OsqpSolver &operator=(OsqpSolver &&o) noexcept {
-    if (this != &o) { reset(); h_ = o.h_; n_ = o.n_; m_ = o.m_; x_ = std::move(o.x_); y_ = std::move(o.y_); info_ = o.info_; o.h_ = nullptr; }
+    if (this != &o) { reset(); h_ = o.h_; n_ = o.n_; m_ = o.m_; x_ = std::move(o.x_); y_ = std::move(o.y_); info_ = o.info_; time_limit_ = o.time_limit_; o.h_ = nullptr; }
     return *this;
   }
   OsqpSolver(const OsqpSolver &) = delete;
@@ -244,8 +251,37 @@ class OsqpSolver {
                                          reinterpret_cast<const int64_t *>(A.outerIndexPtr()),
                                          reinterpret_cast<const int64_t *>(A.innerIndexPtr()), A.valuePtr()), "osqp_update_P_A");
   }
+  // settings updates (osqp_update_*): get the settings in force, change one field, update
+  absl::Status UpdateRho(double rho_new) { return update_setting("osqp_update_rho", [&](mi_osqp_settings &s) { s.rho = rho_new; }); }
+  absl::Status UpdateMaxIter(int max_iter_new) { return update_setting("osqp_update_max_iter", [&](mi_osqp_settings &s) { s.max_iter = max_iter_new; }); }
+  absl::Status UpdateEpsAbs(double eps_abs_new) { return update_setting("osqp_update_eps_abs", [&](mi_osqp_settings &s) { s.eps_abs = eps_abs_new; }); }
+  absl::Status UpdateEpsRel(double eps_rel_new) { return update_setting("osqp_update_eps_rel", [&](mi_osqp_settings &s) { s.eps_rel = eps_rel_new; }); }
+  absl::Status UpdateEpsPrimInf(double eps_prim_inf_new) { return update_setting("osqp_update_eps_prim_inf", [&](mi_osqp_settings &s) { s.eps_prim_inf = eps_prim_inf_new; }); }
+  absl::Status UpdateEpsDualInf(double eps_dual_inf_new) { return update_setting("osqp_update_eps_dual_inf", [&](mi_osqp_settings &s) { s.eps_dual_inf = eps_dual_inf_new; }); }
+  absl::Status UpdateAlpha(double alpha_new) { return update_setting("osqp_update_alpha", [&](mi_osqp_settings &s) { s.alpha = alpha_new; }); }
+  absl::Status UpdateDelta(double delta_new) { return update_setting("osqp_update_delta", [&](mi_osqp_settings &s) { s.delta = delta_new; }); }
+  absl::Status UpdatePolish(bool polish_new) { return update_setting("osqp_update_polish", [&](mi_osqp_settings &s) { s.polish = polish_new ? 1 : 0; }); }
+  absl::Status UpdatePolishRefineIter(int polish_refine_iter_new) { return update_setting("osqp_update_polish_refine_iter", [&](mi_osqp_settings &s) { s.polish_refine_iter = polish_refine_iter_new; }); }
+  absl::Status UpdateWarmStart(bool warm_start_new) { return update_setting("osqp_update_warm_start", [&](mi_osqp_settings &s) { s.warm_start = warm_start_new ? 1 : 0; }); }
+  absl::Status UpdateScaledTermination(bool scaled_termination_new) { return update_setting("osqp_update_scaled_termination", [&](mi_osqp_settings &s) { s.scaled_termination = scaled_termination_new ? 1 : 0; }); }
+  absl::Status UpdateCheckTermination(c_int check_termination_new) { return update_setting("osqp_update_check_termination", [&](mi_osqp_settings &s) { s.check_termination = check_termination_new; }); }
+  absl::Status UpdateTimeLimit(double time_limit_new) {
+    if (!h_) return not_initialized();
+    if (!(time_limit_new >= 0.0)) return MI_OSQP_SHIM_STATUS(kInvalidArgument, "osqp_update_time_limit: time_limit must be nonnegative");
+    time_limit_ = time_limit_new;           // (stored, not enforced: the core has no wall-clock rule)
+    return MI_OSQP_SHIM_OK();
+  }
 
  private:
+  template <class F>
+  absl::Status update_setting(const char *where, F &&change) {
+    if (!h_) return not_initialized();
+    mi_osqp_settings s;
+    const int rc = mi_osqp_get_settings(h_, &s);
+    if (rc != MI_OSQP_OK) return from_error(rc, where);
+    change(s);
+    return from_error(mi_osqp_update_settings(h_, &s), where);
+  }
   void reset() { if (h_) mi_osqp_free(h_); h_ = nullptr; n_ = m_ = 0; }
   static absl::Status not_initialized() { return MI_OSQP_SHIM_STATUS(kFailedPrecondition, "OsqpSolver is not initialized."); }
   static absl::Status from_error(int rc, const char *where) {
@@ -262,6 +298,7 @@ class OsqpSolver {
   std::vector<double> x_, y_;
   mi_osqp_info info_{};
   int last_error_ = 0;
+  double time_limit_ = 0.0;
 };
 
 }  // namespace osqp

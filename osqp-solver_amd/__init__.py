@@ -107,6 +107,16 @@ def lib():
         L.mi_osqp_batch_warm_start_y.argtypes = [vp, dp]
         L.mi_osqp_batch_update_q_some.argtypes = [vp, C.c_int64, ip, dp]
         L.mi_osqp_batch_warm_start_y_some.argtypes = [vp, C.c_int64, ip, dp]
+        L.mi_osqp_settings_update_check.argtypes = [C.POINTER(Settings), C.POINTER(Settings)]
+        L.mi_osqp_batch_get_settings.argtypes = [vp, C.POINTER(Settings)]
+        L.mi_osqp_batch_update_settings.argtypes = [vp, C.POINTER(Settings)]
+        L.mi_osqp_batch_update_rho_each.argtypes = [vp, dp]
+        L.mi_osqp_batch_update_rho_some.argtypes = [vp, C.c_int64, ip, dp]
+        L.mi_osqp_get_settings.argtypes = [vp, C.POINTER(Settings)]
+        L.mi_osqp_update_settings.argtypes = [vp, C.POINTER(Settings)]
+        L.mi_osqp_multi_batch_get_settings.argtypes = [vp, C.POINTER(Settings)]
+        L.mi_osqp_multi_batch_update_settings.argtypes = [vp, C.POINTER(Settings)]
+        L.mi_osqp_multi_batch_update_rho_each.argtypes = [vp, dp]
         L.mi_osqp_batch_solve.argtypes = [vp]
         L.mi_osqp_batch_get_primal.argtypes = [vp, dp]
         L.mi_osqp_batch_get_dual.argtypes = [vp, dp]
@@ -216,6 +226,49 @@ def default_settings(**kw):
     return s
 
 
+class HandleSettings(Settings):
+    """The `settings` attribute of a solver: the fields hold the settings in force (they follow update_settings), and calling
+    it - solver.settings() - reads them from the handle and returns them as a fresh Settings."""
+
+    def bind(self, getter):
+        self._getter = getter
+        return self
+
+    def __call__(self):
+        out = Settings()
+        self._getter(out)
+        C.memmove(C.byref(self), C.byref(out), C.sizeof(Settings))
+        return out
+
+
+def settings_update_check(in_force, wanted):
+    """Host only: the mi_osqp_error update_settings(wanted) would return on a handle whose settings are `in_force`."""
+    return int(lib().mi_osqp_settings_update_check(C.byref(in_force), C.byref(wanted)))
+
+
+def _handle_settings(kw, get_name, owner):
+    """default_settings(**kw) as a HandleSettings whose call reads the handle of `owner` (held weakly) through `get_name`."""
+    import weakref
+    hs = HandleSettings()
+    C.memmove(C.byref(hs), C.byref(default_settings(**kw)), C.sizeof(Settings))
+    ref = weakref.ref(owner)
+
+    def getter(out):
+        _chk(getattr(lib(), get_name)(ref()._h, C.byref(out)), get_name)
+    return hs.bind(getter)
+
+
+def _update_settings(self, fn_name, fields):
+    """get, set the given fields, update: the whole struct goes to the C-ABI, which refuses it as a whole."""
+    s = self.settings()
+    for k, v in fields.items():
+        if not hasattr(s, k):
+            raise KeyError(k)
+        setattr(s, k, v)
+    _chk(getattr(lib(), fn_name)(self._h, C.byref(s)), fn_name)
+    return self.settings()
+
+
 def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
@@ -261,7 +314,7 @@ class BatchSolver:
         q = None if q is None else _f64(q)
         self._Pp, self._Pi = _i64(P.indptr), _i64(P.indices)
         self._Ap, self._Ai = _i64(A.indptr), _i64(A.indices)
-        self.settings = default_settings(**settings)
+        self.settings = _handle_settings(settings, "mi_osqp_batch_get_settings", self)
         self._h = C.c_void_p()
         rc = L.mi_osqp_batch_setup(C.byref(self._h), self.B, self.n, self.m, _ip(self._Pp), _ip(self._Pi), _dp(Px),
                                    _dp(q), _ip(self._Ap), _ip(self._Ai), _dp(Ax), _dp(l), _dp(u),
@@ -363,6 +416,22 @@ class BatchSolver:
     def warm_start_y(self, y):
         y = _f64(y).reshape(self.B, -1)
         _chk(lib().mi_osqp_batch_warm_start_y(self._h, _dp(y)), "warm_start_y")
+
+    # ---- settings updates (OSQP osqp_update_*; mi_osqp.h "settings updates").  self.settings() returns the settings in force.
+    def update_settings(self, **fields):
+        """Change the given settings (rho, max_iter, eps_*, alpha, scaled_termination, check_termination, warm_start, polish,
+        polish_refine_iter, delta, verbose); a new rho refactors every QP.  Returns the settings in force."""
+        return _update_settings(self, "mi_osqp_batch_update_settings", fields)
+
+    def update_rho_each(self, rho):
+        """One rho per QP ([B]); every QP is refactored.  settings.rho is not touched."""
+        rho = _f64(rho).reshape(self.B)
+        _chk(lib().mi_osqp_batch_update_rho_each(self._h, _dp(rho)), "update_rho_each")
+
+    def update_rho_some(self, ids, rho):
+        """Continuous mode: a new rho for the listed idle QPs, enqueued without waiting."""
+        ids = _i64(ids); rho = _f64(rho).reshape(len(ids))
+        _chk(lib().mi_osqp_batch_update_rho_some(self._h, len(ids), _ip(ids), _dp(rho)), "update_rho_some")
 
     def reset(self):
         _chk(lib().mi_osqp_batch_reset(self._h), "reset")
@@ -535,7 +604,7 @@ class MultiBatchSolver:
         q = None if q is None else _f64(q)
         self._Pp, self._Pi = _i64(P.indptr), _i64(P.indices)
         self._Ap, self._Ai = _i64(A.indptr), _i64(A.indices)
-        self.settings = default_settings(**settings)
+        self.settings = _handle_settings(settings, "mi_osqp_multi_batch_get_settings", self)
         devs = _i64(list(devices))
         self._h = C.c_void_p()
         _chk(L.mi_osqp_multi_batch_setup(C.byref(self._h), len(devs), _ip(devs), self.B, self.n, self.m, _ip(self._Pp),
@@ -620,6 +689,13 @@ class MultiBatchSolver:
         y = _f64(y).reshape(self.B, -1)
         _chk(lib().mi_osqp_multi_batch_warm_start_y(self._h, _dp(y)), "multi warm_start_y")
 
+    def update_settings(self, **fields):
+        return _update_settings(self, "mi_osqp_multi_batch_update_settings", fields)
+
+    def update_rho_each(self, rho):
+        rho = _f64(rho).reshape(self.B)
+        _chk(lib().mi_osqp_multi_batch_update_rho_each(self._h, _dp(rho)), "multi update_rho_each")
+
 
 class QPSolver:
     """Python twin of the reference class QPSolver
@@ -642,6 +718,10 @@ class QPSolver:
 
     def setWarmStart(self, x):
         self._b.warm_start_x(x)
+
+    def update_settings(self, **fields):
+        """osqp-cpp's Update* methods in one call (BatchSolver.update_settings); returns the settings in force."""
+        return self._b.update_settings(**fields)
 
     def solve(self):
         info = self._b.solve()[0]

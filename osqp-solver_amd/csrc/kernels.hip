@@ -3118,6 +3118,22 @@ hipError_t launch_fresh_slots(const KernelArgs &a, const int *slots, int nslots,
   hipLaunchKernelGGL(fresh_slots_kernel, dim3(nslots), dim3(256), 0, st, a, slots, BT, rho0);
   return hipGetLastError();
 }
+// osqp_update_rho, first half, for the listed slots (slots == null: the slots 0 .. nslots-1): the new rho of each - rho[j], or
+// rho_all for all of them - becomes the slot's DS_RHO.  Iterates, the rho estimate, the count of rho updates and every flag stay:
+// the refactorisation enqueued behind this kernel (factor_kernel) rebuilds the rho vectors and the factor from DS_RHO.
+__global__ void set_rho_slots_kernel(KernelArgs a, const int *__restrict__ slots, const double *__restrict__ rho, double rho_all, int nslots, int BT) {
+  const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (j >= nslots) return;
+  const int slot = slots ? slots[j] : j;
+  if (slot < 0) return;
+  const size_t tile = (size_t)slot / BT, b = (size_t)slot % BT;
+  a.dscal[(tile * DS_COUNT + DS_RHO) * BT + b] = rho ? rho[j] : rho_all;
+}
+hipError_t launch_set_rho_slots(const KernelArgs &a, const int *slots, const double *rho, double rho_all, int nslots, int BT, hipStream_t st) {
+  if (nslots <= 0) return hipSuccess;
+  hipLaunchKernelGGL(set_rho_slots_kernel, dim3((nslots + 255) / 256), dim3(256), 0, st, a, slots, rho, rho_all, nslots, BT);
+  return hipGetLastError();
+}
 // The refactorisation work list of a launch that nobody on the host has looked at: the slots whose rho changed in the
 // check that has just run (flag 1), packed in front, -1 behind them.  One workgroup.
 __global__ __launch_bounds__(1024) void worklist_kernel(const int *__restrict__ iscal, int *work, int nslots, int BT) {

@@ -270,6 +270,7 @@ struct SchedBufs {
 
 struct mi_osqp_batch {
   Settings st;
+  bool rho_interval_auto = false;             // setup derived st.adaptive_rho_interval from 0 (a settings update may pass 0 again)
   Tuning tune;                                // the MI_OSQP_* switches, read once at setup (tuning_from_env)
   std::shared_ptr<const Analysis> anp;        // pattern analysis: shared between the handles of one pattern (analysis cache below)
   int B = 0, BT = 1, ntiles = 0, threads = 512, device = 0, n_cus = 256;
@@ -873,8 +874,10 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
   double t0 = now_s();
   if (B <= 0 || !Pp || !Ap || (m > 0 && (!l || !u)) || (Pp[n] > 0 && !Pv) || (Ap[n] > 0 && !Av)) return MI_OSQP_ERR_INVALID_DATA;
   if (validate_settings(h->st)) return MI_OSQP_ERR_INVALID_SETTINGS;
-  if (h->st.adaptive_rho && !h->st.adaptive_rho_interval)   // deterministic "auto" (upstream non-PROFILING rule)
+  if (h->st.adaptive_rho && !h->st.adaptive_rho_interval) {   // deterministic "auto" (upstream non-PROFILING rule)
+    h->rho_interval_auto = true;
     h->st.adaptive_rho_interval = h->st.check_termination ? 4 * h->st.check_termination : 100;
+  }
   for (int64_t k = 0; k < B * m; k++) if (l[k] > u[k]) return MI_OSQP_ERR_INVALID_DATA;
   int BT = 1, max_extra = -1;
   const size_t lds_cap = 160 * 1024 - 1024;
@@ -2985,6 +2988,160 @@ int64_t mi_osqp_batch_ring_wraps(mi_osqp_batch *h) { return h ? h->cont.ring_wra
 
 }  // extern "C"
 
+// ------------------------------------------------------------------ settings updates
+// OSQP 0.6.x osqp_update_* (README "Settings updates").  Every field but rho is read by the host loop / passed to the kernels
+// with each launch (make_args), so storing it is the whole update; a new rho is osqp_update_rho: DS_RHO of the QPs
+// (set_rho_slots_kernel), the refactorisation that derives the rho vectors from it, the snapshot mi_osqp_batch_reset returns
+// to.  Iterates and the count of rho updates stay (upstream restarts the count in data updates only).
+
+static mi_osqp_settings from_settings(const Settings &t) {
+  mi_osqp_settings s;
+  s.rho = t.rho; s.sigma = t.sigma; s.scaling = t.scaling; s.adaptive_rho = t.adaptive_rho;
+  s.adaptive_rho_interval = t.adaptive_rho_interval; s.adaptive_rho_tolerance = t.adaptive_rho_tolerance;
+  s.max_iter = t.max_iter; s.eps_abs = t.eps_abs; s.eps_rel = t.eps_rel; s.eps_prim_inf = t.eps_prim_inf;
+  s.eps_dual_inf = t.eps_dual_inf; s.alpha = t.alpha; s.scaled_termination = t.scaled_termination;
+  s.check_termination = t.check_termination; s.warm_start = t.warm_start; s.verbose = t.verbose;
+  s.polish = t.polish; s.polish_refine_iter = t.polish_refine_iter; s.delta = t.delta;
+  return s;
+}
+static double clamp_rho(double r) { return std::min(std::max(r, kRhoMin), kRhoMax); }
+
+// May `w` replace `cur`?  The fields without an osqp_update_* must be those in force (adaptive_rho_interval = 0 stands for the
+// interval setup resolved "auto" to), the rest must be valid.  The reason of a refusal goes to g_last_error.
+static int settings_update_decide(const mi_osqp_settings &cur, const mi_osqp_settings &w) {
+  const char *fixed = nullptr;
+  if (!(w.sigma == cur.sigma)) fixed = "sigma";
+  else if (w.scaling != cur.scaling) fixed = "scaling";
+  else if (w.adaptive_rho != cur.adaptive_rho) fixed = "adaptive_rho";
+  else if (w.adaptive_rho_interval != cur.adaptive_rho_interval && w.adaptive_rho_interval != 0) fixed = "adaptive_rho_interval";
+  else if (!(w.adaptive_rho_tolerance == cur.adaptive_rho_tolerance)) fixed = "adaptive_rho_tolerance";
+  if (fixed) { g_last_error = std::string("settings update: ") + fixed + " is fixed at setup"; return MI_OSQP_ERR_INVALID_SETTINGS; }
+  Settings t = to_settings(&w);
+  t.adaptive_rho_interval = cur.adaptive_rho_interval;
+  if (validate_settings(t)) { g_last_error = "settings update: a value is out of range (nothing changed)"; return MI_OSQP_ERR_INVALID_SETTINGS; }
+  return MI_OSQP_OK;
+}
+
+static int check_rho_values(int64_t count, const double *rho) {
+  for (int64_t j = 0; j < count; j++)
+    if (!(rho[j] > 0.0)) { g_last_error = "rho update: entry " + std::to_string(j) + " is not > 0 (nothing changed)"; return MI_OSQP_ERR_INVALID_SETTINGS; }
+  return MI_OSQP_OK;
+}
+
+// blocking form: rho of every QP (rho_each[B], or rho_all), one refactorisation of the whole batch, the snapshot
+static int set_rho_blocking(mi_osqp_batch *h, const double *rho_each, double rho_all) {
+  const int B = h->B;
+  int rc;
+  const double *d_rho = nullptr;
+  if (rho_each) {
+    if ((rc = ensure_stage(h, (size_t)B, 0)) || (rc = ensure_pin(h, (size_t)B))) return rc;
+    for (int q = 0; q < B; q++) h->pin[q] = clamp_rho(rho_each[q]);
+    HIPCHK(hipMemcpyAsync(h->stage.p, h->pin, (size_t)B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    d_rho = h->stage.p;
+  }
+  HIPCHK(launch_set_rho_slots(make_args(h), nullptr, d_rho, rho_all, B, h->BT, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->host_rho_stale = true;
+  std::vector<int> all(B);
+  for (int i = 0; i < B; i++) all[i] = i;
+  if ((rc = refactor_qps(h, std::move(all)))) return rc;          // (the one-launch list path: factor_kernel derives the rho vectors)
+  return snapshot(h);
+}
+
+// continuous form, for idle QPs: enqueued in stream order behind everything enqueued so far, nothing waits.  The ids have
+// been checked (cont_check_ids, no repeats), the values too.
+static int set_rho_continuous(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *rho) {
+  const int nq = (int)n_ids;
+  int rc;
+  int *d_ids = nullptr;
+  RingSpan sp;
+  if ((rc = ring_reserve(h, (size_t)nq * (sizeof(int) + sizeof(double)), 2))) return rc;
+  if ((rc = cont_stage_ids(h, n_ids, ids, &d_ids, nullptr)) || (rc = ring_take(h, (size_t)nq * sizeof(double), sp))) return rc;
+  for (int j = 0; j < nq; j++) ((double *)sp.host)[j] = clamp_rho(rho[j]);
+  if ((rc = ring_upload(h, sp, (size_t)nq * sizeof(double)))) return rc;
+  HIPCHK(launch_set_rho_slots(make_args(h), d_ids, (const double *)sp.dev, 0.0, nq, h->BT, h->stream));
+  if ((rc = enqueue_refactor_list(h, d_ids, nq))) return rc;
+  if ((rc = snapshot_some(h, d_ids, nq, h->stream))) return rc;
+  for (int64_t j = 0; j < n_ids; j++) { h->failed[(size_t)ids[j]] = 0; h->cont.polishable[(size_t)ids[j]] = 0; }
+  h->host_rho_stale = true;
+  return MI_OSQP_OK;
+}
+
+extern "C" {
+
+int mi_osqp_settings_update_check(const mi_osqp_settings *in_force, const mi_osqp_settings *wanted) {
+  if (!in_force || !wanted) return MI_OSQP_ERR_NULL;
+  return settings_update_decide(*in_force, *wanted);
+}
+
+int mi_osqp_batch_get_settings(mi_osqp_batch *h, mi_osqp_settings *out) {
+  if (!h || !out) return MI_OSQP_ERR_NULL;
+  *out = from_settings(h->st);
+  return MI_OSQP_OK;
+}
+
+int mi_osqp_batch_update_settings(mi_osqp_batch *h, const mi_osqp_settings *s) {
+  CallTimer timer_("batch_update_settings");
+  if (!h || !s) return MI_OSQP_ERR_NULL;
+  const mi_osqp_settings cur = from_settings(h->st);
+  int rc;
+  if ((rc = settings_update_decide(cur, *s))) return rc;
+  if (s->adaptive_rho_interval == 0 && cur.adaptive_rho_interval != 0 && !h->rho_interval_auto) {
+    g_last_error = "settings update: adaptive_rho_interval is fixed at setup (0 is accepted where setup derived it from 0)";
+    return MI_OSQP_ERR_INVALID_SETTINGS;
+  }
+  mi_osqp_batch::Cont &c = h->cont;
+  if (c.on && c.n_running > 0) {
+    g_last_error = "settings update: " + std::to_string(c.n_running) + " QPs are running (poll them first)";
+    return MI_OSQP_ERR_INVALID_DATA;
+  }
+  const bool new_rho = s->rho != h->st.rho;
+  const double rho = clamp_rho(s->rho);
+  Settings t = to_settings(s);
+  t.sigma = h->st.sigma; t.scaling = h->st.scaling; t.adaptive_rho = h->st.adaptive_rho;
+  t.adaptive_rho_interval = h->st.adaptive_rho_interval; t.adaptive_rho_tolerance = h->st.adaptive_rho_tolerance;
+  t.rho = new_rho ? rho : h->st.rho;
+  h->st = t;
+  if (c.on) c.L = segment_length(h->st);
+  if (!new_rho) return MI_OSQP_OK;
+  DevGuard guard(h->device);
+  if (!c.on) return set_rho_blocking(h, nullptr, rho);
+  std::vector<int64_t> ids((size_t)h->B);
+  for (int q = 0; q < h->B; q++) ids[(size_t)q] = q;
+  const std::vector<double> each((size_t)h->B, rho);
+  return set_rho_continuous(h, h->B, ids.data(), each.data());
+}
+
+int mi_osqp_batch_update_rho_each(mi_osqp_batch *h, const double *rho) {
+  CallTimer timer_("batch_update_rho_each");
+  if (!h || !rho) return MI_OSQP_ERR_NULL;
+  int rc;
+  if ((rc = check_rho_values(h->B, rho))) return rc;
+  DevGuard guard(h->device);
+  if ((rc = cont_leave(h))) return rc;
+  return set_rho_blocking(h, rho, 0.0);
+}
+
+int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *rho) {
+  CallTimer timer_("batch_update_rho_some");
+  if (!h || (n_ids > 0 && !rho)) return MI_OSQP_ERR_NULL;
+  int rc;
+  if ((rc = check_rho_values(n_ids, rho))) return rc;
+  DevGuard guard(h->device);
+  if ((rc = cont_enter(h)) || (rc = cont_check_ids(h, n_ids, ids, true))) return rc;
+  if (!n_ids) return MI_OSQP_OK;
+  {
+    std::vector<char> seen((size_t)h->B, 0);
+    for (int64_t j = 0; j < n_ids; j++) {
+      if (seen[(size_t)ids[j]]) { g_last_error = "update_rho_some: QP " + std::to_string(ids[j]) + " is listed twice"; return MI_OSQP_ERR_INVALID_DATA; }
+      seen[(size_t)ids[j]] = 1;
+    }
+  }
+  return set_rho_continuous(h, n_ids, ids, rho);
+}
+
+}  // extern "C"
+
 // ------------------------------------------------------------------ gomp scene
 // SURVEY 8(f) rank 2 on the device: the re-linearised 3-D / obstacle rows of the GOMP constraint matrix
 // ([REF] src/constraints/constraint-builder.h:90-136) and the feasibility check that decides the SQP loop
@@ -3223,6 +3380,8 @@ int mi_osqp_debug_refactor_chunks(int64_t n_flagged, const int64_t *flagged, int
   return MI_OSQP_OK;
 }
 int mi_osqp_get_stats(mi_osqp_solver *h, mi_osqp_stats *st) { return h ? mi_osqp_batch_get_stats(h->b, st) : MI_OSQP_ERR_NULL; }
+int mi_osqp_get_settings(mi_osqp_solver *h, mi_osqp_settings *out) { return h ? mi_osqp_batch_get_settings(h->b, out) : MI_OSQP_ERR_NULL; }
+int mi_osqp_update_settings(mi_osqp_solver *h, const mi_osqp_settings *s) { return h ? mi_osqp_batch_update_settings(h->b, s) : MI_OSQP_ERR_NULL; }
 
 // ------------------------------------------------------------ multi-GPU batch
 // block partition of the batch over the devices, one host thread per shard, no data-path collective.
@@ -3393,6 +3552,35 @@ int mi_osqp_multi_batch_update_P_A(mi_osqp_multi *h, const int64_t *Pp, const in
 int mi_osqp_multi_batch_warm_start_y(mi_osqp_multi *h, const double *y) {
   if (!h || !y) return MI_OSQP_ERR_NULL;
   return multi_fan_out(h, [&](size_t k) { return mi_osqp_batch_warm_start_y(h->shard[k], y + h->begin[k] * h->m); });
+}
+// settings updates: every shard holds the same settings, so shard 0 decides for all before any shard changes
+int mi_osqp_multi_batch_get_settings(mi_osqp_multi *h, mi_osqp_settings *out) {
+  if (!h || !out) return MI_OSQP_ERR_NULL;
+  if (h->async_pending) { const int rc0 = multi_join(h); if (rc0) return rc0; }
+  return mi_osqp_batch_get_settings(h->shard[0], out);
+}
+int mi_osqp_multi_batch_update_settings(mi_osqp_multi *h, const mi_osqp_settings *s) {
+  if (!h || !s) return MI_OSQP_ERR_NULL;
+  if (h->async_pending) { const int rc0 = multi_join(h); if (rc0) return rc0; }
+  const mi_osqp_settings cur = from_settings(h->shard[0]->st);
+  int rc;
+  if ((rc = settings_update_decide(cur, *s))) return rc;
+  if (s->adaptive_rho_interval == 0 && cur.adaptive_rho_interval != 0 && !h->shard[0]->rho_interval_auto) {
+    g_last_error = "settings update: adaptive_rho_interval is fixed at setup (0 is accepted where setup derived it from 0)";
+    return MI_OSQP_ERR_INVALID_SETTINGS;
+  }
+  return multi_fan_out(h, [&](size_t k) -> int {
+    mi_osqp_batch *b = h->shard[k];
+    DevGuard guard(b->device);
+    const int rc_ = cont_leave(b);
+    return rc_ ? rc_ : mi_osqp_batch_update_settings(b, s);
+  });
+}
+int mi_osqp_multi_batch_update_rho_each(mi_osqp_multi *h, const double *rho) {
+  if (!h || !rho) return MI_OSQP_ERR_NULL;
+  const int rc = check_rho_values(h->B, rho);
+  if (rc) return rc;
+  return multi_fan_out(h, [&](size_t k) { return mi_osqp_batch_update_rho_each(h->shard[k], rho + h->begin[k]); });
 }
 int mi_osqp_multi_batch_solve(mi_osqp_multi *h) {
   if (!h) return MI_OSQP_ERR_NULL;
