@@ -375,7 +375,7 @@ int64_t mi_osqp_batch_ring_wraps(mi_osqp_batch *h);
  * The step before and the step after the solver path in the reference's SQP loop - the re-linearised 3-D / obstacle rows
  * of the constraint matrix (ConstraintBuilder::withObstacles, [REF] src/constraints/constraint-builder.h:90-136) and the
  * feasibility check that ends the loop (GOMPSolver::isSolutionOK, [REF] src/gomp-solver.h:141-199) - for collision balls
- * whose kinematics are built-in models (the reference binds arbitrary host callbacks, [REF] src/utils.h:21-22,33-42; those
+ * whose kinematics are built-in models or a DH chain (the reference binds arbitrary host callbacks, [REF] src/utils.h:21-22,33-42; those
  * stay on the host path of include/mi_osqp/gomp.hpp).  A scene belongs to one batch handle whose QPs have the reference's
  * GOMP row layout ([REF] constraint-builder.h:34-44) for `dims` joints and `waypoints` waypoints; it keeps the raw
  * constraint data of every QP on the device, so an SQP step moves one trajectory to the device and one flag back. */
@@ -384,7 +384,8 @@ typedef enum {
   MI_GOMP_MODEL_UR5E_WRIST3 = 2,   /*   wrist-3 joint (forward_kinematics_6_back)                                      */
   MI_GOMP_MODEL_UR5E_ELBOW = 3,    /*   elbow joint                                                                    */
   MI_GOMP_MODEL_YAW_2LINK = 4,     /* 3 joints: yaw, shoulder, elbow; param = {link 1, link 2, base height}            */
-  MI_GOMP_MODEL_TABLE = 5          /* 3 joints: p = (q0, q1, q2), constant 3 x 3 Jacobian in param (known-answer tests) */
+  MI_GOMP_MODEL_TABLE = 5,         /* 3 joints: p = (q0, q1, q2), constant 3 x 3 Jacobian in param (known-answer tests) */
+  MI_GOMP_MODEL_DH_CHAIN = 6       /* any serial arm: the scene's mi_gomp_chain; param = {frame k, centre c in frame k}  */
 } mi_gomp_model;
 typedef struct { int32_t model; int32_t is_gripper; double radius; double param[12]; } mi_gomp_ball;   /* = RobotBall */
 typedef struct { double dir[2]; double point[3]; int32_t below; int32_t reserved; } mi_gomp_line;       /* = HorizontalLine */
@@ -393,6 +394,20 @@ typedef struct mi_gomp_scene mi_gomp_scene;
 int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints,
                          int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                          const double *con_lo, const double *con_hi);
+/* A serial chain of revolute joints by its standard DH table, T_i = Rz(q_i + theta0_i) Tz(d_i) Tx(a_i) Rx(alpha_i) for
+ * i = 0 .. n_joints-1 (the convention of include/mi_osqp/ur5e_kinematics.hpp; host twin: include/mi_osqp/dh_kinematics.hpp).
+ * Frame k (1 <= k <= n_joints) is the frame after k joints, with origin o_k and rotation R_k.  A ball of
+ * MI_GOMP_MODEL_DH_CHAIN is fixed in one of them: param[0] = k, param[1..3] = its centre c in frame k; its position is
+ * p = o_k + R_k c and column j of its Jacobian z_j x (p - o_j) for j < k (z_j, o_j: axis and origin of joint j), 0 for j >= k. */
+typedef struct { int32_t n_joints; int32_t reserved; double a[8], d[8], alpha[8], theta0[8]; } mi_gomp_chain;
+/* mi_gomp_scene_create with one chain for the scene's MI_GOMP_MODEL_DH_CHAIN balls (n_joints = dims); balls of the other
+ * models of that `dims` may stand beside them.  chain == NULL: exactly mi_gomp_scene_create, which refuses model 6.
+ * Refused on the host, before any device call, with *out = NULL, the handle usable and the reason in mi_osqp_last_error():
+ * a chain ball without a chain (MI_OSQP_ERR_NULL); n_joints != dims or outside 1..8, a non-finite chain or ball
+ * parameter, param[0] not an integer in 1..n_joints (MI_OSQP_ERR_INVALID_DATA). */
+int mi_gomp_scene_create_chain(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints,
+                               const mi_gomp_chain *chain, int64_t n_balls, const mi_gomp_ball *balls,
+                               int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi);
 void mi_gomp_scene_free(mi_gomp_scene *sc);          /* before mi_osqp_batch_free of its handle; one scene per handle */
 /* While a scene exists, mi_osqp_batch_reinit_some / _update_A_bounds_some of its handle also keep the QPs' raw constraint
  * data (as ConstraintBuilder::build() produced it) in the scene, so nothing extra is needed when a trajectory enters the

@@ -1,0 +1,79 @@
+// dh_kinematics.hpp -- forward kinematics / position Jacobians of any serial arm of revolute joints given by its standard
+// DH table (mi_gomp_chain in mi_osqp.h), for collision balls fixed anywhere in a link frame: the host twin of the device
+// model MI_GOMP_MODEL_DH_CHAIN.
+//
+//     T_i = Rz(q_i + theta0_i) Tz(d_i) Tx(a_i) Rx(alpha_i),  i = 0 .. n_joints-1     (as ur5e_kinematics.hpp, theta0 = 0 there)
+//     frame k (1 <= k <= n_joints): after k joints, origin o_k, rotation R_k
+//     a ball at c in frame k:  p = o_k + R_k c,  Jacobian column j = z_j x (p - o_j) for j < k, 0 for j >= k
+//
+//   mi_osqp::dh::point(chain, q, frame, c, p, J)       p[3] and (J non-null) the 3 x n_joints row-major Jacobian
+//   miosqp_ref::dhBall(chain, frame, c, radius, grip)   a RobotBall whose callbacks call it and which names the device model,
+//                                                       so ContinuousGOMPSolver (device_assembly, dh_chain = chain) can
+//                                                       re-linearise on the GPU
+#pragma once
+
+#include <array>
+#include <cmath>
+#include <tuple>
+
+#include "../mi_osqp.h"
+#include "gomp.hpp"
+
+namespace mi_osqp {
+namespace dh {
+
+constexpr int kMaxJoints = 8;
+
+inline void point(const mi_gomp_chain &ch, const double *q, int frame, const double c[3], double p[3], double *J /* 3 x n row-major, or null */) {
+  const int n = ch.n_joints;
+  double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, o[3] = {0, 0, 0};
+  double oj[kMaxJoints][3], zj[kMaxJoints][3];
+  for (int i = 0; i < frame && i < n && i < kMaxJoints; i++) {
+    for (int r = 0; r < 3; r++) { oj[i][r] = o[r]; zj[i][r] = R[r][2]; }
+    const double th = q[i] + ch.theta0[i];
+    const double ct = std::cos(th), st = std::sin(th), ca = std::cos(ch.alpha[i]), sa = std::sin(ch.alpha[i]);
+    const double T[3][4] = {{ct, -st * ca, st * sa, ch.a[i] * ct}, {st, ct * ca, -ct * sa, ch.a[i] * st}, {0.0, sa, ca, ch.d[i]}};
+    double G[3][3], g[3];
+    for (int r = 0; r < 3; r++) {
+      for (int k = 0; k < 3; k++) G[r][k] = R[r][0] * T[0][k] + R[r][1] * T[1][k] + R[r][2] * T[2][k];
+      g[r] = R[r][0] * T[0][3] + R[r][1] * T[1][3] + R[r][2] * T[2][3] + o[r];
+    }
+    for (int r = 0; r < 3; r++) { for (int k = 0; k < 3; k++) R[r][k] = G[r][k]; o[r] = g[r]; }
+  }
+  for (int r = 0; r < 3; r++) p[r] = o[r] + (R[r][0] * c[0] + R[r][1] * c[1] + R[r][2] * c[2]);
+  if (!J) return;
+  for (int j = 0; j < n; j++) {
+    double col[3] = {0, 0, 0};
+    if (j < frame) {
+      const double r[3] = {p[0] - oj[j][0], p[1] - oj[j][1], p[2] - oj[j][2]};
+      col[0] = zj[j][1] * r[2] - zj[j][2] * r[1];
+      col[1] = zj[j][2] * r[0] - zj[j][0] * r[2];
+      col[2] = zj[j][0] * r[1] - zj[j][1] * r[0];
+    }
+    for (int ax = 0; ax < 3; ax++) J[ax * n + j] = col[ax];
+  }
+}
+
+}  // namespace dh
+}  // namespace mi_osqp
+
+namespace miosqp_ref {
+
+// A collision ball of radius `radius` centred at c in frame `frame` of the chain.  fk / jacobian (3 x n_joints, row-major)
+// are what the sequential, lock-step and host-assembling drivers call; the built-in model is what the device path reads.
+inline RobotBall dhBall(const mi_gomp_chain &chain, int frame, const std::array<double, 3> &c, double radius, bool is_gripper = false) {
+  ForwardKinematicsFun fk = [chain, frame, c](double *q) {
+    double p[3];
+    mi_osqp::dh::point(chain, q, frame, c.data(), p, nullptr);
+    return std::tuple<double, double, double>{p[0], p[1], p[2]};
+  };
+  JacobianFun jac = [chain, frame, c](double *out, double *q) {
+    double p[3];
+    mi_osqp::dh::point(chain, q, frame, c.data(), p, out);
+  };
+  RobotBall b(std::move(fk), std::move(jac), radius, is_gripper);
+  b.withBuiltin(MI_GOMP_MODEL_DH_CHAIN, {(double)frame, c[0], c[1], c[2]});
+  return b;
+}
+
+}  // namespace miosqp_ref

@@ -750,8 +750,11 @@ class ContinuousGOMPSolver {
   std::atomic<int> solver_reuses{0};   // stages whose solver was kept from the previous run()
   // Re-linearise on the device (mi_gomp_scene: FK / Jacobians of built-in kinematic models, row assembly, feasibility check,
   // update from device-resident rows) instead of on the stage's host thread.  Needs every ball to name its model
-  // (RobotBall::withBuiltin); the trajectories then agree with the host path to round-off (device sin / cos), not bitwise.
+  // (RobotBall::withBuiltin; dhBall() does for the links of any serial arm, see dh_chain); the trajectories then agree with the host path to round-off (device sin / cos), not bitwise.
   bool device_assembly = false;
+  // The DH chain of the balls made by dhBall() (include/mi_osqp/dh_kinematics.hpp, MI_GOMP_MODEL_DH_CHAIN): the device path
+  // needs it next to them; without it such balls keep the planner on the host callbacks.
+  std::optional<mi_gomp_chain> dh_chain;
   int pipeline_depth = 1;              // 2: a stage enqueues its next advance before it looks at the previous one's results
   int segments_per_advance = 4;        // a launch runs on until a QP of the stage finishes, at most that many segments
   // per stage: {waypoints, advances, seconds admitting, waiting for the device, processing finished QPs, idle}
@@ -874,7 +877,7 @@ class ContinuousGOMPSolver {
 
   bool useDevice() const {
     if (!device_assembly) return false;
-    for (const RobotBall &b : mappers) if (!b.builtin_model) return false;
+    for (const RobotBall &b : mappers) if (!b.builtin_model || (b.builtin_model == MI_GOMP_MODEL_DH_CHAIN && !dh_chain)) return false;
     return true;
   }
   void makeScene(Stage &st) {
@@ -895,8 +898,10 @@ class ContinuousGOMPSolver {
     }
     double lo[3], hi[3];
     for (int k = 0; k < 3; ++k) { lo[k] = con_3d.first ? (*con_3d.first)[k] : -INF; hi[k] = con_3d.second ? (*con_3d.second)[k] : INF; }
-    const int rc = mi_gomp_scene_create(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, (int64_t)balls.size(), balls.data(),
-                                        (int64_t)lines.size(), lines.data(), lo, hi);
+    const int rc = dh_chain ? mi_gomp_scene_create_chain(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, &*dh_chain, (int64_t)balls.size(),
+                                                         balls.data(), (int64_t)lines.size(), lines.data(), lo, hi)
+                            : mi_gomp_scene_create(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, (int64_t)balls.size(), balls.data(),
+                                                   (int64_t)lines.size(), lines.data(), lo, hi);
     if (rc != MI_OSQP_OK) std::fprintf(stderr, "ContinuousGOMPSolver: device scene failed (%s): falling back to the host path\n", mi_osqp_error_name(rc));
   }
 

@@ -242,7 +242,11 @@ hipError_t launch_copy_flagged_streams(double *dst, const double *src, const int
 hipError_t launch_copy_slot_rows(double *dst, const double *src, const int *slots, int nslots, int len, int BT, hipStream_t st);
 // ---- GOMP re-linearisation on the device (solver.hip "gomp scene"): ConstraintBuilder::withObstacles + isSolutionOK for
 // built-in kinematic models ([REF] src/constraints/constraint-builder.h:90-136, src/gomp-solver.h:141-199)
-enum { MI_GM_UR5E_FLANGE = 1, MI_GM_UR5E_WRIST3 = 2, MI_GM_UR5E_ELBOW = 3, MI_GM_YAW_2LINK = 4, MI_GM_TABLE = 5 };
+enum { MI_GM_UR5E_FLANGE = 1, MI_GM_UR5E_WRIST3 = 2, MI_GM_UR5E_ELBOW = 3, MI_GM_YAW_2LINK = 4, MI_GM_TABLE = 5, MI_GM_DH_CHAIN = 6 };
+#define MI_GOMP_MAXD 8
+// the scene's DH chain (mi_gomp_chain) as the kernel reads it: cos / sin of alpha taken once on the host; travels by value
+// in the kernel arguments - every lane reads the same entry, at an index known at compile time (dh_point)
+struct GompChainDev { int n_joints, pad; double a[MI_GOMP_MAXD], d[MI_GOMP_MAXD], ca[MI_GOMP_MAXD], sa[MI_GOMP_MAXD], theta0[MI_GOMP_MAXD]; };
 struct GompBallDev { int model, is_gripper; double radius; double param[12]; };
 struct GompLineDev { double D[3], A[3]; int below, pad; };
 struct GompArgs {
@@ -255,6 +259,7 @@ struct GompArgs {
   const double *traj;            // [n_ids][n]: the trajectories to linearise around (row = position in the list)
   double *A, *l, *u;             // the kept raw constraint data, [B][nnzA] / [B][m] by QP: the 3-D rows are rewritten
   int *ok;                       // [n_ids]: isSolutionOK of the trajectory
+  GompChainDev chain;            // MI_GM_DH_CHAIN balls: param[0] = frame, param[1..3] = centre in that frame (n_joints = 0: none)
 };
 hipError_t launch_gomp_relinearise(const GompArgs &g, hipStream_t st);
 hipError_t launch_gather_status(const int *iscal, int32_t *status, int32_t *iters, int B, int BT, hipStream_t st);

@@ -3583,8 +3583,43 @@ __device__ __forceinline__ void ur5e_point(const double *q, int frame, double *p
     for (int ax = 0; ax < 3; ax++) J[ax * 6 + j] = col[ax];
   }
 }
-#define MI_GOMP_MAXD 8
-__device__ __forceinline__ void gomp_fk_jac(const GompBallDev &b, int D, const double *q, double *p, double *J) {
+// A ball fixed at c in frame `frame` of the scene's DH chain, T_i = Rz(q_i + theta0_i) Tz(d_i) Tx(a_i) Rx(alpha_i): p = o_k + R_k c,
+// Jacobian column j = z_j x (p - o_j) for j < frame.  The frame differs from lane to lane and the number of joints from scene
+// to scene, so nothing here is indexed by either: both passes run over all MI_GOMP_MAXD joints, fully unrolled, and a joint
+// at or beyond the ball's frame leaves the running frame as it is (an array indexed by a runtime frame would live in
+// scratch).  Pass 1 walks the chain to the ball's frame for p; pass 2 walks it again and forms each column as it reaches
+// the joint's axis and origin, instead of keeping all eight of them.  J8: 3 x MI_GOMP_MAXD row-major, zero from `frame` on.
+__device__ __forceinline__ void dh_advance(double (&R)[3][3], double (&o)[3], double ct, double st, double ca, double sa, double a, double d, bool on) {
+  const double T[3][4] = {{ct, -st * ca, st * sa, a * ct}, {st, ct * ca, -ct * sa, a * st}, {0.0, sa, ca, d}};
+  double G[3][3], g[3];
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) G[r][c] = R[r][0] * T[0][c] + R[r][1] * T[1][c] + R[r][2] * T[2][c];
+    g[r] = R[r][0] * T[0][3] + R[r][1] * T[1][3] + R[r][2] * T[2][3] + o[r];
+  }
+  for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[r][c] = on ? G[r][c] : R[r][c]; o[r] = on ? g[r] : o[r]; }
+}
+__device__ __forceinline__ void dh_point(const GompChainDev &ch, const double *q, int frame, const double *c, double *p, double *J8) {
+  double ct[MI_GOMP_MAXD], st[MI_GOMP_MAXD];
+  double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, o[3] = {0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < MI_GOMP_MAXD; i++) {
+    const double th = i < frame ? q[i] + ch.theta0[i] : 0.0;
+    ct[i] = cos(th); st[i] = sin(th);
+    dh_advance(R, o, ct[i], st[i], ch.ca[i], ch.sa[i], ch.a[i], ch.d[i], i < frame);
+  }
+  for (int r = 0; r < 3; r++) p[r] = o[r] + (R[r][0] * c[0] + R[r][1] * c[1] + R[r][2] * c[2]);
+  double S[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, s[3] = {0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < MI_GOMP_MAXD; j++) {
+    const double r[3] = {p[0] - s[0], p[1] - s[1], p[2] - s[2]};
+    const bool on = j < frame;
+    J8[0 * MI_GOMP_MAXD + j] = on ? S[1][2] * r[2] - S[2][2] * r[1] : 0.0;
+    J8[1 * MI_GOMP_MAXD + j] = on ? S[2][2] * r[0] - S[0][2] * r[2] : 0.0;
+    J8[2 * MI_GOMP_MAXD + j] = on ? S[0][2] * r[1] - S[1][2] * r[0] : 0.0;
+    dh_advance(S, s, ct[j], st[j], ch.ca[j], ch.sa[j], ch.a[j], ch.d[j], on);
+  }
+}
+__device__ __forceinline__ void gomp_fk_jac(const GompChainDev &ch, const GompBallDev &b, int D, const double *q, double *p, double *J) {
   for (int k = 0; k < 3 * D; k++) J[k] = 0.0;
   if (b.model == MI_GM_UR5E_FLANGE || b.model == MI_GM_UR5E_WRIST3 || b.model == MI_GM_UR5E_ELBOW) {
     double J6[18];
@@ -3599,6 +3634,13 @@ __device__ __forceinline__ void gomp_fk_jac(const GompBallDev &b, int D, const d
     J[0 * D + 0] = -r * s0; J[0 * D + 1] = c0 * dr1; J[0 * D + 2] = c0 * dr2;
     J[1 * D + 0] = r * c0;  J[1 * D + 1] = s0 * dr1; J[1 * D + 2] = s0 * dr2;
     J[2 * D + 0] = 0.0;     J[2 * D + 1] = L1 * cos(q[1]) + L2 * cos(q[1] + q[2]); J[2 * D + 2] = L2 * cos(q[1] + q[2]);
+  } else if (b.model == MI_GM_DH_CHAIN) {          // frame param[0] of the scene's chain (D joints), centre param[1..3] in it
+    double J8[3 * MI_GOMP_MAXD], qz[MI_GOMP_MAXD];
+#pragma unroll
+    for (int j = 0; j < MI_GOMP_MAXD; j++) qz[j] = j < D ? q[j] : 0.0;
+    dh_point(ch, qz, (int)b.param[0], b.param + 1, p, J8);
+#pragma unroll
+    for (int j = 0; j < MI_GOMP_MAXD; j++) if (j < D) for (int ax = 0; ax < 3; ax++) J[ax * D + j] = J8[ax * MI_GOMP_MAXD + j];
   } else {                                         // MI_GM_TABLE (tests): p = (q0, q1, q2), J = the 3 x 3 table in param (D = 3)
     p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
     for (int ax = 0; ax < 3; ax++) for (int j = 0; j < 3 && j < D; j++) J[ax * D + j] = b.param[ax * 3 + j];
@@ -3622,7 +3664,7 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
   for (int e = tid; e < NB * W; e += blockDim.x) {
     const int w = e % W;
     for (int j = 0; j < D; j++) q[j] = traj[(size_t)w * D + j];
-    gomp_fk_jac(g.balls[e / W], D, q, p, J);
+    gomp_fk_jac(g.chain, g.balls[e / W], D, q, p, J);
     for (int k = 0; k < 3; k++) smem[(size_t)e * 3 + k] = p[k];
   }
   __syncthreads();
@@ -3640,7 +3682,7 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
     const int bi = e / W, w = e % W;
     const GompBallDev &ball = g.balls[bi];
     for (int j = 0; j < D; j++) q[j] = traj[(size_t)w * D + j];
-    gomp_fk_jac(ball, D, q, p, J);
+    gomp_fk_jac(g.chain, ball, D, q, p, J);
     const double *xyz = smem + (size_t)bi * W * 3;
     double Jq[3];
     for (int ax = 0; ax < 3; ax++) { double sacc = 0.0; for (int j = 0; j < D; j++) sacc += J[ax * D + j] * q[j]; Jq[ax] = sacc; }

@@ -3148,12 +3148,14 @@ int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t
 // ([REF] src/gomp-solver.h:141-199), for balls whose kinematics are built-in models.  The scene keeps the raw constraint
 // data of every QP of a batch handle on the device; re-linearising a QP rewrites its 3-D rows there (gomp_relinearise_kernel)
 // and runs QPSolver::update from them - no A values cross PCIe in an SQP step, only the trajectory (n doubles) and one flag.
+// Besides the built-in models a scene may hold one DH chain (mi_gomp_chain) with balls fixed in its link frames.
 struct mi_gomp_scene {
   mi_osqp_batch *h = nullptr;
   int dims = 0, W = 0, n_balls = 0, n_lines = 0, row0 = 0, n_rows3d = 0;
   double con_lo[3] = {-1e30, -1e30, -1e30}, con_hi[3] = {1e30, 1e30, 1e30};
   DevBuf<GompBallDev> balls;
   DevBuf<GompLineDev> lines;
+  GompChainDev chain{};                       // the DH chain of the MI_GM_DH_CHAIN balls (n_joints 0: the scene has none)
   DevBuf<int> aidx;
   DevBuf<double> A, l, u;                     // QP-major raw rows as ConstraintBuilder::build() lays them out
   int *h_ok = nullptr; size_t h_ok_cap = 0;   // the kernel's verdicts (pinned host memory)
@@ -3180,6 +3182,7 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
   g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
   for (int k = 0; k < 3; k++) { g.con_lo[k] = sc->con_lo[k]; g.con_hi[k] = sc->con_hi[k]; }
   g.A = sc->A.p; g.l = sc->l.p; g.u = sc->u.p; g.ok = sc->h_ok;
+  g.chain = sc->chain;
   HIPCHK(launch_gomp_relinearise(g, st));
   HIPCHK(hipEventRecord(sc->ev, st));
   HIPCHK(hipEventSynchronize(sc->ev));
@@ -3187,13 +3190,39 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
   return MI_OSQP_OK;
 }
 
-extern "C" {
-
-int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, int64_t n_balls, const mi_gomp_ball *balls,
-                         int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
+// mi_gomp_scene_create (chain null: model 6 is refused as it always was) and mi_gomp_scene_create_chain.  Everything that can
+// be refused is refused here on the host, the checks that need no handle first.
+static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain, bool chain_entry,
+                             int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
   if (!out) return MI_OSQP_ERR_NULL;
   *out = nullptr;
-  if (!h || (n_balls > 0 && !balls) || (n_lines > 0 && !lines)) return MI_OSQP_ERR_NULL;
+  if ((n_balls > 0 && !balls) || (n_lines > 0 && !lines)) return MI_OSQP_ERR_NULL;
+  GompChainDev hc{};
+  if (chain_entry) {
+    for (int64_t b = 0; b < n_balls; b++)
+      if (balls[b].model == MI_GM_DH_CHAIN && !chain) { g_last_error = "ball " + std::to_string(b) + " is a chain ball and the scene has no chain"; return MI_OSQP_ERR_NULL; }
+    if (chain) {
+      const int nj = chain->n_joints;
+      if (nj < 1 || nj > MI_GOMP_MAXD) { g_last_error = "chain: n_joints must be 1 .. 8"; return MI_OSQP_ERR_INVALID_DATA; }
+      if (nj != dims) { g_last_error = "chain: n_joints differs from dims"; return MI_OSQP_ERR_INVALID_DATA; }
+      for (int i = 0; i < nj; i++)
+        if (!std::isfinite(chain->a[i]) || !std::isfinite(chain->d[i]) || !std::isfinite(chain->alpha[i]) || !std::isfinite(chain->theta0[i])) {
+          g_last_error = "chain: joint " + std::to_string(i) + " has a parameter that is not finite"; return MI_OSQP_ERR_INVALID_DATA;
+        }
+      for (int64_t b = 0; b < n_balls; b++) {
+        if (balls[b].model != MI_GM_DH_CHAIN) continue;
+        const double *pm = balls[b].param;
+        if (!std::isfinite(balls[b].radius) || !std::isfinite(pm[0]) || !std::isfinite(pm[1]) || !std::isfinite(pm[2]) || !std::isfinite(pm[3])) {
+          g_last_error = "chain ball " + std::to_string(b) + " has a parameter that is not finite"; return MI_OSQP_ERR_INVALID_DATA;
+        }
+        if (pm[0] != std::floor(pm[0]) || pm[0] < 1.0 || pm[0] > (double)nj) { g_last_error = "chain ball " + std::to_string(b) + ": param[0] must be a frame 1 .. n_joints"; return MI_OSQP_ERR_INVALID_DATA; }
+      }
+      hc.n_joints = nj;
+      for (int i = 0; i < nj; i++) { hc.a[i] = chain->a[i]; hc.d[i] = chain->d[i]; hc.ca[i] = std::cos(chain->alpha[i]); hc.sa[i] = std::sin(chain->alpha[i]); hc.theta0[i] = chain->theta0[i]; }
+      for (int i = nj; i < MI_GOMP_MAXD; i++) hc.ca[i] = 1.0;      // (never part of a result: identity joints)
+    }
+  }
+  if (!h) return MI_OSQP_ERR_NULL;
   const Analysis &an = (*h->anp);
   const int D = (int)dims, W = (int)waypoints;
   if (D < 1 || D > 8 || W < 2 || n_balls < 0 || n_lines < 0 || an.n != 2 * D * W) return MI_OSQP_ERR_INVALID_DATA;
@@ -3202,8 +3231,8 @@ int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, in
   const int row0 = (W - 1) * D + D * (W + W - 1 + W - 2);
   int rows3d = 0;
   for (int b = 0; b < (int)n_balls; b++) {
-    if (balls[b].model < MI_GM_UR5E_FLANGE || balls[b].model > MI_GM_TABLE) return MI_OSQP_ERR_INVALID_DATA;
-    if ((balls[b].model <= MI_GM_UR5E_ELBOW && D != 6) || (balls[b].model >= MI_GM_YAW_2LINK && D != 3)) return MI_OSQP_ERR_INVALID_DATA;
+    if (balls[b].model < MI_GM_UR5E_FLANGE || balls[b].model > (hc.n_joints ? MI_GM_DH_CHAIN : MI_GM_TABLE)) return MI_OSQP_ERR_INVALID_DATA;
+    if ((balls[b].model <= MI_GM_UR5E_ELBOW && D != 6) || ((balls[b].model == MI_GM_YAW_2LINK || balls[b].model == MI_GM_TABLE) && D != 3)) return MI_OSQP_ERR_INVALID_DATA;
     rows3d += W * ((balls[b].is_gripper ? 3 : 0) + (int)n_lines);
   }
   if (row0 + rows3d > an.m) return MI_OSQP_ERR_INVALID_DATA;
@@ -3212,6 +3241,7 @@ int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, in
   if (!sc) return MI_OSQP_ERR_ALLOC;
   std::unique_ptr<mi_gomp_scene> own(sc);
   sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->row0 = row0; sc->n_rows3d = rows3d;
+  sc->chain = hc;
   for (int k = 0; k < 3; k++) { sc->con_lo[k] = con_lo ? con_lo[k] : -1e30; sc->con_hi[k] = con_hi ? con_hi[k] : 1e30; }
   // where the entries of the 3-D rows sit in A's value array: row r of waypoint w holds D entries in the columns of q_w
   std::vector<int> aidx((size_t)rows3d * D, -1);
@@ -3247,6 +3277,17 @@ int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, in
   h->cont.keepA = sc->A.p; h->cont.keepl = sc->l.p; h->cont.keepu = sc->u.p;
   *out = own.release();
   return MI_OSQP_OK;
+}
+
+extern "C" {
+
+int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, int64_t n_balls, const mi_gomp_ball *balls,
+                         int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
+  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, con_lo, con_hi);
+}
+int mi_gomp_scene_create_chain(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
+                               int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
+  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, con_lo, con_hi);
 }
 
 void mi_gomp_scene_free(mi_gomp_scene *sc) {
