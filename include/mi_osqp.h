@@ -170,6 +170,20 @@ int mi_osqp_solve(mi_osqp_solver *h, mi_osqp_info *info);
  * when the exit code carries no solution. */
 int mi_osqp_get_primal(mi_osqp_solver *h, double *x_out);
 int mi_osqp_get_dual(mi_osqp_solver *h, double *y_out);
+/* Infeasibility certificates: what osqp_solve leaves in OSQPSolution::y / ::x of an infeasible problem (OSQP 0.6.2
+ * store_solution: prim_inf_cert = delta_y, dual_inf_cert = delta_x) and osqp-cpp returns from
+ * primal_infeasibility_certificate() / dual_infeasibility_certificate().
+ *   primal (status_val -3 or 3; m entries): delta_y of the exit iteration after the projection of the infeasibility test -
+ *     0 on rows without bounds, min(., 0) where only u is infinite, max(., 0) where only l is infinite -,
+ *   dual (status_val -4 or 4; n entries): delta_x of the exit iteration,
+ * multiplied by E / D when scaling != 0 and scaled_termination = 0 (else left in the scaled space, as upstream leaves it),
+ * then divided by its infinity norm: the largest entry is exactly +-1.  With any other status (kNonConvex included), before
+ * the first finished solve, and for the certificate of the other kind every entry reads NaN.  A certificate belongs to the
+ * last finished solve of its QP, like mi_osqp_info: updates and warm starts in between leave it, the next finished solve
+ * replaces it - with NaN when that solve ends with a solution.  x, y and info of an infeasible QP are what they were: NaN,
+ * NaN, obj_val = +-1e30.  m = 0: mi_osqp_get_prim_inf_cert writes nothing. */
+int mi_osqp_get_prim_inf_cert(mi_osqp_solver *h, double *dy_out /*[m]*/);
+int mi_osqp_get_dual_inf_cert(mi_osqp_solver *h, double *dx_out /*[n]*/);
 int mi_osqp_get_stats(mi_osqp_solver *h, mi_osqp_stats *st);
 /* Settings after setup (see "settings updates" below); a large single QP - one workgroup or the dataflow grid - included. */
 int mi_osqp_get_settings(mi_osqp_solver *h, mi_osqp_settings *out);
@@ -208,6 +222,10 @@ int mi_osqp_batch_solve(mi_osqp_batch *h);
 int mi_osqp_batch_get_primal(mi_osqp_batch *h, double *x_out /*[B][n]*/);
 int mi_osqp_batch_get_dual(mi_osqp_batch *h, double *y_out /*[B][m]*/);
 int mi_osqp_batch_get_info(mi_osqp_batch *h, mi_osqp_info *info /*[B]*/);
+/* Infeasibility certificates of every QP (see mi_osqp_get_prim_inf_cert): the rows of QPs without a certificate of that kind
+ * are NaN.  Like mi_osqp_batch_get_primal they end the continuous mode, and they work after mi_osqp_batch_solve_device. */
+int mi_osqp_batch_get_prim_inf_cert(mi_osqp_batch *h, double *dy_out /*[B][m]*/);
+int mi_osqp_batch_get_dual_inf_cert(mi_osqp_batch *h, double *dx_out /*[B][n]*/);
 int mi_osqp_batch_get_stats(mi_osqp_batch *h, mi_osqp_stats *st);
 /* the elimination order the analysis chose for the KKT matrix [[P + sigma I, A'], [A, -1/rho]]: kkt_perm[k] = natural index
  * (0 .. n-1 variables, n .. n+m-1 constraint rows) eliminated k-th; n + m entries.  (Lets a CPU checker factor the same
@@ -316,6 +334,7 @@ int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t
  *                                                              follows the launch in stream order
  *     poll(wait, ...)                                          which QPs finished in the oldest advance not polled yet
  *     get_primal_some / get_dual_some / get_info_some          results of finished QPs (host memory, no device access)
+ *     get_prim_inf_cert_some / get_dual_inf_cert_some          their infeasibility certificates (likewise)
  *     polish_some                                              polish finished kOptimal QPs on demand; reported once more
  *     update_rho_some                                          a new rho for QPs that are not iterating ("settings updates")
  *
@@ -344,6 +363,13 @@ int mi_osqp_batch_poll(mi_osqp_batch *h, int64_t wait, int64_t *n_finished, int6
 int mi_osqp_batch_get_primal_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, double *x_out /*[n_ids][n]*/);
 int mi_osqp_batch_get_dual_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, double *y_out /*[n_ids][m]*/);
 int mi_osqp_batch_get_info_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, mi_osqp_info *info /*[n_ids]*/);
+/* Infeasibility certificates (see mi_osqp_get_prim_inf_cert) of the listed QPs, by the status poll() last reported for each:
+ * NaN rows for QPs that have not finished a solve in this continuous phase or finished it otherwise.  Same id checks as
+ * get_primal_some, no device access; bit for bit what the whole-batch getters return for the same solves.  A QP reads NaN
+ * again from solve_begin_some (the solve in flight writes the row when it finishes) and from reinit_some (a new QP in the
+ * slot) on, before any poll(); the other per-QP updates and warm starts leave its certificate. */
+int mi_osqp_batch_get_prim_inf_cert_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, double *dy_out /*[n_ids][m]*/);
+int mi_osqp_batch_get_dual_inf_cert_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, double *dx_out /*[n_ids][n]*/);
 int64_t mi_osqp_batch_running(mi_osqp_batch *h);      /* QPs whose solve (or polish) has been begun and not been reported by poll() */
 /* Polish the listed QPs now (OSQP polish.c; settings polish_refine_iter and delta of the handle), without waiting for the
  * device and without disturbing the QPs that are iterating - in an SQP loop only the last, accepted QP of a trajectory is
@@ -458,6 +484,8 @@ int mi_osqp_multi_batch_wait(mi_osqp_multi *h);
 int mi_osqp_multi_batch_get_primal(mi_osqp_multi *h, double *x_out /*[B][n]*/);
 int mi_osqp_multi_batch_get_dual(mi_osqp_multi *h, double *y_out /*[B][m]*/);
 int mi_osqp_multi_batch_get_info(mi_osqp_multi *h, mi_osqp_info *info /*[B]*/);
+int mi_osqp_multi_batch_get_prim_inf_cert(mi_osqp_multi *h, double *dy_out /*[B][m]*/);      /* see mi_osqp_batch_get_prim_inf_cert */
+int mi_osqp_multi_batch_get_dual_inf_cert(mi_osqp_multi *h, double *dx_out /*[B][n]*/);
 /* shard k: its device, its QP range [begin, end) and its single-device handle (owned by the multi handle) */
 int64_t mi_osqp_multi_batch_shards(mi_osqp_multi *h);
 int mi_osqp_multi_batch_shard(mi_osqp_multi *h, int64_t k, int64_t *device, int64_t *begin, int64_t *end, mi_osqp_batch **handle);

@@ -19,6 +19,7 @@
 #include <atomic>
 #include <cassert>
 #include <iostream>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -88,7 +89,7 @@ class QPSolver {
     verbose_ = verbose;
     if (rc != MI_OSQP_OK) std::cerr << "QPSolver: setup failed: " << mi_osqp_error_name(rc) << " (" << mi_osqp_last_error() << ")" << std::endl;
     assert(rc == MI_OSQP_OK);                                              // [REF] :30 (assert only)
-    n_ = A.cols;
+    n_ = A.cols; m_ = A.rows;
   }
   ~QPSolver() { mi_osqp_free(h_); }
   // Not in the reference: the pattern analysis of a solver that will be constructed later for (c, P), computed now (blocking;
@@ -130,6 +131,20 @@ class QPSolver {
     return {static_cast<OsqpExitCode>(info.exit_code), x};
   }
 
+  // Not in the reference (osqp-cpp primal_infeasibility_certificate() / dual_infeasibility_certificate()): after a solve()
+  // that returned kPrimalInfeasible(Inaccurate) / kDualInfeasible(Inaccurate) the vector that proves it, delta_y (m entries) /
+  // delta_x (n entries) with unit infinity norm (mi_osqp.h mi_osqp_get_prim_inf_cert); NaN-filled after any other solve().
+  QPVector primalInfeasibilityCertificate() {
+    QPVector v((size_t)m_, std::numeric_limits<double>::quiet_NaN());
+    (void)mi_osqp_get_prim_inf_cert(h_, v.data());
+    return v;
+  }
+  QPVector dualInfeasibilityCertificate() {
+    QPVector v((size_t)n_, std::numeric_limits<double>::quiet_NaN());
+    (void)mi_osqp_get_dual_inf_cert(h_, v.data());
+    return v;
+  }
+
   // Not in the reference: settings after construction (mi_osqp.h "settings updates" - get, change fields, update).  Throws
   // std::invalid_argument, like update(), for a struct the core refuses; nothing has changed then.
   mi_osqp_settings settings() const { mi_osqp_settings s; mi_osqp_default_settings(&s); (void)mi_osqp_get_settings(h_, &s); return s; }
@@ -143,7 +158,7 @@ class QPSolver {
 
  private:
   mi_osqp_solver *h_ = nullptr;
-  long long n_ = 0;
+  long long n_ = 0, m_ = 0;
   int status_ = 0;
   bool verbose_ = true;
   mi_osqp_info last_{};
@@ -411,6 +426,19 @@ class ContinuousQPSolver {
       return {OsqpExitCode::kUnknown, x};
     last_ = info;
     return {static_cast<OsqpExitCode>(info.exit_code), x};
+  }
+  // the infeasibility certificates of a finished slot (QPSolver::primalInfeasibilityCertificate): host memory, no device access
+  QPVector primalInfeasibilityCertificate(long long id) {
+    const int64_t i = id;
+    QPVector v((size_t)m_, std::numeric_limits<double>::quiet_NaN());
+    (void)mi_osqp_batch_get_prim_inf_cert_some(h_, 1, &i, v.data());
+    return v;
+  }
+  QPVector dualInfeasibilityCertificate(long long id) {
+    const int64_t i = id;
+    QPVector v((size_t)n_, std::numeric_limits<double>::quiet_NaN());
+    (void)mi_osqp_batch_get_dual_inf_cert_some(h_, 1, &i, v.data());
+    return v;
   }
   long long running() const { return mi_osqp_batch_running(h_); }
   long long size() const { return K_; }

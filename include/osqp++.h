@@ -26,6 +26,10 @@
 // UpdateRho refactors the KKT matrix on the device; the others take effect at the next Solve.  UpdateTimeLimit validates
 // (>= 0) and stores the value, which is then ignored like the time_limit given to Init.
 //
+// primal_infeasibility_certificate() / dual_infeasibility_certificate() return, after a Solve() that ended kPrimalInfeasible(Inaccurate)
+// / kDualInfeasible(Inaccurate), the certificate with unit infinity norm (mi_osqp_get_prim_inf_cert / _dual_inf_cert; README
+// "Infeasibility certificates"); after any other Solve() - and before the first - every entry is NaN.
+//
 // polish, polish_refine_iter and delta map onto the core's solution polishing (mi_osqp_settings, README "Polishing").
 // Settings that the MI355X core does not implement are validated like upstream and otherwise ignored: time_limit,
 // adaptive_rho_fraction (the wall-clock rule; the deterministic interval 4 * check_termination stands in for "auto",
@@ -128,7 +132,7 @@ class OsqpSolver {
   OsqpSolver() = default;
   OsqpSolver(OsqpSolver &&o) noexcept { *this = std::move(o); }
   OsqpSolver &operator=(OsqpSolver &&o) noexcept {
-    if (this != &o) { reset(); h_ = o.h_; n_ = o.n_; m_ = o.m_; x_ = std::move(o.x_); y_ = std::move(o.y_); info_ = o.info_; time_limit_ = o.time_limit_; o.h_ = nullptr; }
+    if (this != &o) { reset(); h_ = o.h_; n_ = o.n_; m_ = o.m_; x_ = std::move(o.x_); y_ = std::move(o.y_); pcert_ = std::move(o.pcert_); dcert_ = std::move(o.dcert_); info_ = o.info_; time_limit_ = o.time_limit_; o.h_ = nullptr; }
     return *this;
   }
   OsqpSolver(const OsqpSolver &) = delete;
@@ -163,6 +167,7 @@ class OsqpSolver {
     if (rc != MI_OSQP_OK) { h_ = nullptr; return from_error(rc, "osqp_setup"); }
     n_ = n; m_ = m;
     x_.assign(static_cast<size_t>(n), 0.0); y_.assign(static_cast<size_t>(m), 0.0);
+    pcert_.assign(static_cast<size_t>(m), kNaN); dcert_.assign(static_cast<size_t>(n), kNaN);
     return MI_OSQP_SHIM_OK();
   }
   bool IsInitialized() const { return h_ != nullptr; }
@@ -170,6 +175,7 @@ class OsqpSolver {
   // osqp_solve + the copy-out of the solution; never throws ([REF] osqp-wrapper.h:51-54)
   OsqpExitCode Solve() {
     if (!h_) return OsqpExitCode::kUnknown;
+    pcert_.assign(static_cast<size_t>(m_), kNaN); dcert_.assign(static_cast<size_t>(n_), kNaN);      // (also where the solve fails)
     last_error_ = mi_osqp_solve(h_, &info_);
     if (last_error_ != MI_OSQP_OK) {
       // osqp-cpp turns a failing osqp_solve into kUnknown, which the reference's driver reads as "not converged, go on"
@@ -179,13 +185,20 @@ class OsqpSolver {
     }
     mi_osqp_get_primal(h_, x_.data());
     if (m_) mi_osqp_get_dual(h_, y_.data());
-    return static_cast<OsqpExitCode>(info_.exit_code);
+    // (the certificates are read only when there is one: an exit with a solution costs no further copy)
+    const OsqpExitCode code = static_cast<OsqpExitCode>(info_.exit_code);
+    if (code == OsqpExitCode::kPrimalInfeasible || code == OsqpExitCode::kPrimalInfeasibleInaccurate) mi_osqp_get_prim_inf_cert(h_, pcert_.data());
+    if (code == OsqpExitCode::kDualInfeasible || code == OsqpExitCode::kDualInfeasibleInaccurate) mi_osqp_get_dual_inf_cert(h_, dcert_.data());
+    return code;
   }
   int last_error() const { return last_error_; }        // mi_osqp_error of the last Solve() (not part of osqp-cpp)
   c_int iterations() const { return info_.iter; }
   double objective_value() const { return info_.obj_val; }
   Eigen::Map<const Eigen::VectorXd> primal_solution() const { return Eigen::Map<const Eigen::VectorXd>(x_.data(), n_); }
   Eigen::Map<const Eigen::VectorXd> dual_solution() const { return Eigen::Map<const Eigen::VectorXd>(y_.data(), m_); }
+  // delta_y / delta_x of the last Solve() with unit infinity norm, NaN where that Solve() proved no infeasibility of the kind
+  Eigen::Map<const Eigen::VectorXd> primal_infeasibility_certificate() const { return Eigen::Map<const Eigen::VectorXd>(pcert_.data(), m_); }
+  Eigen::Map<const Eigen::VectorXd> dual_infeasibility_certificate() const { return Eigen::Map<const Eigen::VectorXd>(dcert_.data(), n_); }
 
   absl::Status SetPrimalWarmStart(const Eigen::Ref<const Eigen::VectorXd> &primal_vector) {
     if (!h_) return not_initialized();
@@ -295,7 +308,8 @@ class OsqpSolver {
   }
   mi_osqp_solver *h_ = nullptr;
   c_int n_ = 0, m_ = 0;
-  std::vector<double> x_, y_;
+  static constexpr double kNaN = __builtin_nan("");
+  std::vector<double> x_, y_, pcert_, dcert_;
   mi_osqp_info info_{};
   int last_error_ = 0;
   double time_limit_ = 0.0;

@@ -121,6 +121,11 @@ def lib():
         L.mi_osqp_batch_get_primal.argtypes = [vp, dp]
         L.mi_osqp_batch_get_dual.argtypes = [vp, dp]
         L.mi_osqp_batch_get_info.argtypes = [vp, C.POINTER(Info)]
+        for f in ("mi_osqp_get_prim_inf_cert", "mi_osqp_get_dual_inf_cert", "mi_osqp_batch_get_prim_inf_cert",
+                  "mi_osqp_batch_get_dual_inf_cert", "mi_osqp_multi_batch_get_prim_inf_cert", "mi_osqp_multi_batch_get_dual_inf_cert"):
+            getattr(L, f).argtypes = [vp, dp]
+        L.mi_osqp_batch_get_prim_inf_cert_some.argtypes = [vp, C.c_int64, ip, dp]
+        L.mi_osqp_batch_get_dual_inf_cert_some.argtypes = [vp, C.c_int64, ip, dp]
         L.mi_osqp_batch_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.mi_osqp_batch_get_ordering.argtypes = [vp, ip]
         L.mi_osqp_batch_free.argtypes = [vp]; L.mi_osqp_batch_free.restype = None
@@ -350,6 +355,19 @@ class BatchSolver:
         _chk(lib().mi_osqp_batch_get_info(self._h, arr), "get_info")
         return list(arr)
 
+    # ---- infeasibility certificates (mi_osqp.h mi_osqp_get_prim_inf_cert): unit infinity norm, NaN rows where there is none
+    def prim_inf_cert(self):
+        """[B, m]: delta_y of every QP whose last solve ended primal infeasible (status -3 / 3), NaN rows elsewhere."""
+        v = np.empty((self.B, self.m))
+        _chk(lib().mi_osqp_batch_get_prim_inf_cert(self._h, _dp(v)), "get_prim_inf_cert")
+        return v
+
+    def dual_inf_cert(self):
+        """[B, n]: delta_x of every QP whose last solve ended dual infeasible (status -4 / 4), NaN rows elsewhere."""
+        v = np.empty((self.B, self.n))
+        _chk(lib().mi_osqp_batch_get_dual_inf_cert(self._h, _dp(v)), "get_dual_inf_cert")
+        return v
+
     def stats(self):
         s = Stats()
         _chk(lib().mi_osqp_batch_get_stats(self._h, C.byref(s)), "get_stats")
@@ -547,6 +565,16 @@ class BatchSolver:
         _chk(lib().mi_osqp_batch_get_info_some(self._h, len(ids), _ip(ids), arr), "get_info_some")
         return list(arr)
 
+    def prim_inf_cert_some(self, ids):
+        ids = _i64(ids); v = np.empty((len(ids), self.m))
+        _chk(lib().mi_osqp_batch_get_prim_inf_cert_some(self._h, len(ids), _ip(ids), _dp(v)), "get_prim_inf_cert_some")
+        return v
+
+    def dual_inf_cert_some(self, ids):
+        ids = _i64(ids); v = np.empty((len(ids), self.n))
+        _chk(lib().mi_osqp_batch_get_dual_inf_cert_some(self._h, len(ids), _ip(ids), _dp(v)), "get_dual_inf_cert_some")
+        return v
+
     # ---- device-resident variants (torch tensors on the solver's GPU)
     def solve_device(self, x_out=None, status=None, iters=None, stream=None):
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
@@ -655,6 +683,16 @@ class MultiBatchSolver:
         _chk(lib().mi_osqp_multi_batch_get_dual(self._h, _dp(y)), "multi get_dual")
         return y
 
+    def prim_inf_cert(self):
+        v = np.empty((self.B, self.m))
+        _chk(lib().mi_osqp_multi_batch_get_prim_inf_cert(self._h, _dp(v)), "multi get_prim_inf_cert")
+        return v
+
+    def dual_inf_cert(self):
+        v = np.empty((self.B, self.n))
+        _chk(lib().mi_osqp_multi_batch_get_dual_inf_cert(self._h, _dp(v)), "multi get_dual_inf_cert")
+        return v
+
     def update_A(self, Ax):
         Ax = _f64(Ax).reshape(self.B, -1)
         _chk(lib().mi_osqp_multi_batch_update_A(self._h, _ip(self._Ap), _ip(self._Ai), _dp(Ax)), "multi update_A")
@@ -732,6 +770,14 @@ class QPSolver:
 
     def dual(self):
         return self._b.dual()[0]
+
+    def prim_inf_cert(self):
+        """osqp-cpp primal_infeasibility_certificate(): [m], NaN unless the last solve ended primal infeasible."""
+        return self._b.prim_inf_cert()[0]
+
+    def dual_inf_cert(self):
+        """osqp-cpp dual_infeasibility_certificate(): [n], NaN unless the last solve ended dual infeasible."""
+        return self._b.dual_inf_cert()[0]
 
     def stats(self):
         return self._b.stats()

@@ -54,6 +54,10 @@ struct KernelArgs {
   double *dx, *dy, *out1, *out2, *dscal;
   int *iscal;
   double *x_out, *y_out;                // QP-major [B][n], [B][m]
+  // infeasibility certificate of every QP whose solve ended primal (delta_y, m entries) or dual infeasible (delta_x, n
+  // entries), unit infinity norm: QP-major [B][cert_stride], cert_stride = max(n, m, 1).  Other QPs' rows are not written.
+  double *cert_out;
+  int cert_stride;
   double *xs_global;                    // non-null: the solve vector lives here ([tile][xs_len][BT]) instead of LDS
   int xs_len;                           // length of the solve vector: Analysis::Next >= n + m
   int rs_off;                           // iterate / advance launches: LDS offset (in doubles) of the resident state (iterate_body RS), 0 = streamed

@@ -1363,6 +1363,26 @@ __device__ __forceinline__ int check_body(const KernelArgs &a, double *smem, int
       a.y_out[(size_t)qp * m + j] = has_sol ? (a.scaling ? p.Esc[e] * p.y[e] * cinv : p.y[e]) : nanv;
       if (!has_sol) { p.y[e] = 0.0; p.z[e] = 0.0; }
     }
+    // the certificate of an infeasible QP (OSQP 0.6.2 store_solution): the vector the test above accepted - delta_y projected
+    // by bound type / delta_x, in the space the test ran in - over its infinity norm mi[0] / mi[1] (a true division: the
+    // largest entry is exactly +-1).  QPs that end with a solution store nothing here.
+    if (status == -3 || status == 3) {
+      double *cert = a.cert_out + (size_t)qp * a.cert_stride;
+      for (int e = tid; e < m * BT; e += nthr) {
+        double d = p.dy[e];
+        const double lo = p.l[e], up = p.u[e];
+        if (up > MI_INFTY * MI_MIN_SCALING) {
+          if (lo < -MI_INFTY * MI_MIN_SCALING) d = 0.0; else d = fmin(d, 0.0);
+        } else if (lo < -MI_INFTY * MI_MIN_SCALING) d = fmax(d, 0.0);
+        cert[e / BT] = (unscale ? p.Esc[e] * d : d) / norm_dy;
+      }
+    } else if (status == -4 || status == 4) {
+      double *cert = a.cert_out + (size_t)qp * a.cert_stride;
+      for (int e = tid; e < n * BT; e += nthr) {
+        const double d = p.dx[e];
+        cert[e / BT] = (unscale ? p.Dsc[e] * d : d) / norm_dx;
+      }
+    }
   }
   sync();
   const bool was_done = done && !just_done;          // idle before this check: its flags (a failed factor's -1) stay

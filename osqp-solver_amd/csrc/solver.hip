@@ -15,6 +15,7 @@
 #include <cmath>
 #include <condition_variable>
 #include <functional>
+#include <limits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -286,6 +287,7 @@ struct mi_osqp_batch {
   DevBuf<uint32_t> pinv, xloc;
   DevBuf<double> fwd_val, bwd_val, chk_val, dinv, x, z, y, q, l, u, rho_vec, rho_inv, Dsc, Dsc_inv, Esc, Esc_inv;
   DevBuf<double> dx, dy, out1, out2, dscal, x_out, y_out, xs_global;
+  DevBuf<double> cert_out;                    // infeasibility certificates, [B][max(n, m, 1)] (KernelArgs::cert_out)
   bool global_xs = false;
   int mw_groups = 0, mw_threads = 0;    // > 0: dataflow form of the solves (Analysis::df): mw_groups workgroups of mw_threads threads share the ONE QP of the handle
   DevBuf<uint32_t> mw_bar;              // their grid barrier: arrival count, generation, error word
@@ -367,6 +369,10 @@ struct mi_osqp_batch {
     hipEvent_t ev[2] = {nullptr, nullptr}; int64_t seq_of[2] = {0, 0};
     // solutions of finished QPs land in pinned host memory straight from check_kernel ([B][n], [B][m])
     double *xh = nullptr, *yh = nullptr; size_t xh_cap = 0, yh_cap = 0;
+    double *ch = nullptr; size_t ch_cap = 0;      // and the infeasibility certificates ([B][max(n, m, 1)], KernelArgs::cert_out)
+    // per QP: the status under which get_*_inf_cert_some read its row of ch - what poll() reported for its last finished solve,
+    // 0 (no certificate) from the begin of its next solve or a reinit on; cont.info keeps the last report meanwhile
+    std::vector<int> cert_status;
     // staging ring of the per-QP calls: regions are handed out once per call and recycled when the ring wraps (after a
     // synchronisation), so a call never waits for an earlier call's copy
     char *ring_h = nullptr; size_t ring_cap = 0, ring_h_cap = 0, ring_head = 0;
@@ -394,7 +400,7 @@ struct mi_osqp_batch {
     DevGuard guard(device);
     if (stream) (void)hipStreamSynchronize(stream);      // (the buffers go back to their pools right after: DevBuf remembers its device)
     for (int k = 0; k < 2; k++) { hostpool::give(cont.h_is[k], cont.h_is_cap[k]); hostpool::give(cont.h_ds[k], cont.h_ds_cap[k]); if (cont.ev[k]) (void)hipEventDestroy(cont.ev[k]); }
-    hostpool::give(cont.xh, cont.xh_cap); hostpool::give(cont.yh, cont.yh_cap); hostpool::give(cont.ring_h, cont.ring_h_cap);
+    hostpool::give(cont.xh, cont.xh_cap); hostpool::give(cont.yh, cont.yh_cap); hostpool::give(cont.ch, cont.ch_cap); hostpool::give(cont.ring_h, cont.ring_h_cap);
     if (cont.ev_adv) (void)hipEventDestroy(cont.ev_adv);
     if (evp0) (void)hipEventDestroy(evp0);
     if (evp1) (void)hipEventDestroy(evp1);
@@ -454,6 +460,7 @@ static KernelArgs make_args(mi_osqp_batch *h) {
   a.Esc = h->Esc.p; a.Esc_inv = h->Esc_inv.p; a.dx = h->dx.p; a.dy = h->dy.p; a.out1 = h->out1.p; a.out2 = h->out2.p;
   a.dscal = h->dscal.p; a.iscal = h->iscal.p;
   a.x_out = h->x_out.p; a.y_out = h->y_out.p;
+  a.cert_out = h->cert_out.p; a.cert_stride = (int)std::max<int64_t>(std::max<int64_t>(a.n, a.m), 1);
   a.xs_global = h->global_xs ? h->xs_global.p : nullptr; a.xs_len = (*h->anp).xs_total; a.wide = (*h->anp).wide ? 1 : 0;
   a.rs_off = h->rs_off; a.rf_off = h->rf_off;
   a.mw_groups = h->mw_groups; a.mw_bar = h->mw_bar.p; a.mw_scratch = h->mw_scratch.p;
@@ -1037,8 +1044,9 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
     }
   }
   if ((rc = h->x_out.alloc((size_t)B * n)) || (rc = h->y_out.alloc((size_t)B * std::max<int64_t>(m, 1)))) return rc;
+  if ((rc = h->cert_out.alloc((size_t)B * std::max<int64_t>(std::max<int64_t>(n, m), 1)))) return rc;
   if ((rc = h->rawP.alloc((size_t)B * std::max(an.Pp[n], 1))) || (rc = h->rawq.alloc((size_t)B * n))) return rc;
-  if ((rc = h->x_out.zero(h->stream)) || (rc = h->y_out.zero(h->stream))) return rc;
+  if ((rc = h->x_out.zero(h->stream)) || (rc = h->y_out.zero(h->stream)) || (rc = h->cert_out.zero(h->stream))) return rc;
   HIPCHK(hostpool::alloc((void **)&h->h_iscal, (size_t)IS_COUNT * T * sizeof(int), &h->h_iscal_cap));
   HIPCHK(hostpool::alloc((void **)&h->h_dscal, (size_t)DS_COUNT * T * sizeof(double), &h->h_dscal_cap));
   if ((rc = ensure_pin(h, std::max((size_t)2 * B * m, (size_t)B * n)))) return rc;      // (host update paths: bounds, warm starts)
@@ -1701,6 +1709,41 @@ int mi_osqp_batch_get_dual(mi_osqp_batch *h, double *y) {
   if ((*h->anp).m) HIPCHK(hipMemcpy(y, h->y_out.p, (size_t)h->B * (*h->anp).m * sizeof(double), hipMemcpyDeviceToHost));
   return MI_OSQP_OK;
 }
+
+// Infeasibility certificates (mi_osqp.h).  check_body stores the certificate of a QP whose solve ends infeasible into its
+// row of cert_out and nothing for any other QP; which rows hold a certificate of the asked kind is read from the exit codes
+// of the last finished solves, and every other row of the answer is NaN-filled here, on the host.
+static bool cert_status(int64_t status, bool primal) { return primal ? (status == -3 || status == 3) : (status == -4 || status == 4); }
+static void cert_row(double *dst, const double *src, size_t len, bool valid) {
+  if (valid) memcpy(dst, src, len * sizeof(double));
+  else std::fill(dst, dst + len, std::numeric_limits<double>::quiet_NaN());
+}
+static int get_cert(mi_osqp_batch *h, double *out, bool primal) {
+  CallTimer timer_(primal ? "batch_get_prim_inf_cert" : "batch_get_dual_inf_cert");
+  if (!h || !out) return MI_OSQP_ERR_NULL;
+  const size_t n = (size_t)(*h->anp).n, m = (size_t)(*h->anp).m, len = primal ? m : n, stride = std::max(std::max(n, m), (size_t)1);
+  if (!len) return MI_OSQP_OK;
+  DevGuard guard(h->device);
+  { const int rc_ = cont_leave(h); if (rc_) return rc_; }
+  const int BT = h->BT;
+  HIPCHK(hipMemcpy(h->h_iscal, h->iscal.p, (size_t)h->ntiles * IS_COUNT * BT * sizeof(int), hipMemcpyDeviceToHost));
+  auto status = [&](int q) { return h->h_iscal[(size_t)(q / BT) * IS_COUNT * BT + IS_STATUS * BT + q % BT]; };
+  // the buffer is fetched only when a QP holds a certificate of this kind (the usual batch has none: NaN rows, no copy)
+  bool any = false;
+  for (int q = 0; q < h->B && !any; q++) any = cert_status(status(q), primal);
+  std::vector<double> rows;
+  if (any) {
+    rows.resize((size_t)h->B * stride);
+    HIPCHK(hipMemcpy(rows.data(), h->cert_out.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  for (int q = 0; q < h->B; q++) {
+    const bool valid = any && cert_status(status(q), primal);
+    cert_row(out + (size_t)q * len, valid ? rows.data() + (size_t)q * stride : nullptr, len, valid);
+  }
+  return MI_OSQP_OK;
+}
+int mi_osqp_batch_get_prim_inf_cert(mi_osqp_batch *h, double *dy_out) { return get_cert(h, dy_out, true); }
+int mi_osqp_batch_get_dual_inf_cert(mi_osqp_batch *h, double *dx_out) { return get_cert(h, dx_out, false); }
 
 int mi_osqp_batch_get_info(mi_osqp_batch *h, mi_osqp_info *info) {
   CallTimer timer_("batch_get_info");
@@ -2439,6 +2482,15 @@ static int ensure_advance_buffers(mi_osqp_batch *h) {
   if (!c.h_done) { HIPCHK(hostpool::alloc((void **)&c.h_done, 64, &c.h_done_cap)); c.h_done[0] = c.h_done[1] = 0; }
   return MI_OSQP_OK;
 }
+// a QP of the flags in h_iscal ended its last solve with an infeasibility certificate
+static bool any_cert_status(const mi_osqp_batch *h) {
+  const int BT = h->BT;
+  for (int q = 0; q < h->B; q++) {
+    const int st = h->h_iscal[(size_t)(q / BT) * IS_COUNT * BT + IS_STATUS * BT + q % BT];
+    if (st == -3 || st == 3 || st == -4 || st == 4) return true;
+  }
+  return false;
+}
 static int cont_enter(mi_osqp_batch *h) {
   mi_osqp_batch::Cont &c = h->cont;
   if (c.on) return MI_OSQP_OK;
@@ -2448,6 +2500,7 @@ static int cont_enter(mi_osqp_batch *h) {
   c.L = segment_length(h->st);
   c.running.assign((size_t)B, 0); c.clear_rho.assign((size_t)B, 0); c.epoch.assign((size_t)B, 0);
   c.info.assign((size_t)B, mi_osqp_info{});
+  c.cert_status.assign((size_t)B, 0);
   c.polishable.assign((size_t)B, 0); c.polishing.assign((size_t)B, 0);
   c.pol_status.assign((size_t)B, 0);
   if (!h->st.polish && h->pol_status.size() == (size_t)B) c.pol_status = h->pol_status;      // (an earlier continuous phase polished)
@@ -2460,6 +2513,8 @@ static int cont_enter(mi_osqp_batch *h) {
   }
   if (!c.xh) HIPCHK(hostpool::alloc((void **)&c.xh, (size_t)B * n * sizeof(double), &c.xh_cap));
   if (!c.yh) HIPCHK(hostpool::alloc((void **)&c.yh, (size_t)B * std::max(m, 1) * sizeof(double), &c.yh_cap));
+  const size_t cert_bytes = (size_t)B * std::max(std::max(n, m), 1) * sizeof(double);
+  if (!c.ch) HIPCHK(hostpool::alloc((void **)&c.ch, cert_bytes, &c.ch_cap));
   if (!c.ring_h) {
     // a few rounds of per-QP calls: (A values + bounds + a warm start) of every QP, twice
     const size_t per_qp = ((size_t)an.Ap[n] + (size_t)an.Pp[n] + 2 * (size_t)m + (size_t)n + 16) * sizeof(double);      // (a whole call - ids, rows in, scaled values out - fits one lap)
@@ -2485,6 +2540,8 @@ static int cont_enter(mi_osqp_batch *h) {
   c.h_done[0] = c.h_done[1] = 0;
   // the state of the last blocking solve, if any, stays valid; every slot is idle until its solve is begun
   HIPCHK(hipMemcpy(h->h_iscal, h->iscal.p, icnt * sizeof(int), hipMemcpyDeviceToHost));
+  // (the certificates of the last blocking solve stay with their QPs - cont_leave hands the image back; most batches have none)
+  if (any_cert_status(h)) HIPCHK(hipMemcpy(c.ch, h->cert_out.p, cert_bytes, hipMemcpyDeviceToHost));
   for (int t = 0; t < h->ntiles; t++)
     for (int b = 0; b < BT; b++) {
       int *p = h->h_iscal + (size_t)t * IS_COUNT * BT;
@@ -2516,6 +2573,8 @@ static int cont_leave(mi_osqp_batch *h) {
   // the solutions of the finished QPs, for the whole-batch getters
   HIPCHK(hipMemcpy(h->x_out.p, c.xh, (size_t)h->B * (*h->anp).n * sizeof(double), hipMemcpyHostToDevice));
   if ((*h->anp).m) HIPCHK(hipMemcpy(h->y_out.p, c.yh, (size_t)h->B * (*h->anp).m * sizeof(double), hipMemcpyHostToDevice));
+  if (any_cert_status(h))       // (a row is read under a status that wrote it: without such a status there is nothing to hand back)
+    HIPCHK(hipMemcpy(h->cert_out.p, c.ch, (size_t)h->B * std::max(std::max((*h->anp).n, (*h->anp).m), 1) * sizeof(double), hipMemcpyHostToDevice));
   // every enqueued polish has run: those not reported yet have their result in the pinned image
   if (!h->st.polish) {
     bool any = !h->pol_status.empty();
@@ -2675,6 +2734,7 @@ static int cont_new_data(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, co
   if ((rc = enqueue_refactor_list(h, d_ids, nq))) return rc;
   if ((rc = snapshot_some(h, d_ids, nq, us))) return rc;
   for (int64_t j = 0; j < n_ids; j++) { h->cont.clear_rho[(size_t)ids[j]] = 1; h->failed[(size_t)ids[j]] = 0; h->cont.polishable[(size_t)ids[j]] = 0; }
+  if (fresh) for (int64_t j = 0; j < n_ids; j++) h->cont.cert_status[(size_t)ids[j]] = 0;      // (a new QP in the slot: it has not finished a solve)
   h->host_scaling_stale = true; h->host_bounds_stale = true; h->host_rho_stale = true;
   return MI_OSQP_OK;
 }
@@ -2788,7 +2848,7 @@ int mi_osqp_batch_solve_begin_some(mi_osqp_batch *h, int64_t n_ids, const int64_
   }
   if ((rc = ring_upload(h, sp, 2 * (size_t)n_ids * sizeof(int)))) return rc;
   KernelArgs a = make_args(h);
-  a.x_out = c.xh; a.y_out = c.yh;
+  a.x_out = c.xh; a.y_out = c.yh; a.cert_out = c.ch;
   // (a QP whose last refactorisation lost the inertia carries flag -1 on the device: start_slots_kernel ends it as kNonConvex)
   HIPCHK(launch_start_slots(a, (const int *)sp.dev, (const int *)sp.dev + n_ids, (int)n_ids, h->BT, h->st.warm_start ? 0 : 1, h->stream));
   for (int64_t j = 0; j < n_ids; j++) {
@@ -2796,6 +2856,7 @@ int mi_osqp_batch_solve_begin_some(mi_osqp_batch *h, int64_t n_ids, const int64_
     if (!c.running[q]) { c.running[q] = 1; c.n_running++; }
     c.epoch[q]++;
     c.polishable[q] = 0; c.pol_status[q] = 0;
+    c.cert_status[q] = 0;                 // (the solve in flight writes the QP's certificate row when it finishes)
   }
   return MI_OSQP_OK;
 }
@@ -2841,7 +2902,7 @@ int mi_osqp_batch_polish_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *id
   int *d_ids = nullptr;
   if ((rc = cont_stage_ids(h, n_ids, ids, &d_ids, nullptr))) return rc;
   KernelArgs a = make_args(h);
-  a.x_out = c.xh; a.y_out = c.yh;
+  a.x_out = c.xh; a.y_out = c.yh; a.cert_out = c.ch;
   PolishArgs pa{h->pol_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter};
   HIPCHK(launch_polish_active_list(a, pa, d_ids, nq, BT, h->stream));
   if ((rc = enqueue_refactor_list(h, d_ids, nq, &pa))) return rc;
@@ -2869,7 +2930,7 @@ int mi_osqp_batch_advance(mi_osqp_batch *h, int64_t n_segments) {
   if (c.adv_seq - c.polled_seq >= 2) { g_last_error = "advance: two advances are waiting for poll()"; return MI_OSQP_ERR_INVALID_DATA; }
   const int BT = h->BT, nslots = h->ntiles * BT;
   KernelArgs a = make_args(h);
-  a.x_out = c.xh; a.y_out = c.yh;
+  a.x_out = c.xh; a.y_out = c.yh; a.cert_out = c.ch;
   // ONE launch: every tile runs up to n_segments segments (L iterations + check each) and publishes its flags and the
   // solutions of finished QPs in pinned host memory; with several segments the launch ends early for everybody once a QP
   // has finished (the caller wants to react to it), and for a tile whose QP asks for a refactorisation
@@ -2936,6 +2997,7 @@ int mi_osqp_batch_poll(mi_osqp_batch *h, int64_t wait, int64_t *n_finished, int6
     I.obj_val = td[DS_OBJ * BT + b]; I.pri_res = td[DS_PRI_RES * BT + b]; I.dua_res = td[DS_DUA_RES * BT + b];
     I.rho_updates = ti[IS_RHO_UPDATES * BT + b]; I.rho_estimate = td[DS_RHO_EST * BT + b]; I.rho = td[DS_RHO * BT + b];
     if (ti[IS_NEED_REFACTOR * BT + b] < 0) h->failed[(size_t)q] = 1;
+    c.cert_status[(size_t)q] = (int)I.status_val;
     if (c.polishing[(size_t)q]) {      // the second report of a polished QP: (the image is valid: the epoch moved after it was written)
       c.polishing[(size_t)q] = 0;
       c.pol_status[(size_t)q] = c.h_pstat[q];
@@ -2982,6 +3044,24 @@ int mi_osqp_batch_get_info_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *
     info[j] = h->cont.info[(size_t)ids[j]];
   }
   return MI_OSQP_OK;
+}
+// (the status is the one poll() reported for the QP's last finished solve, until its next solve begins or the slot is
+//  reinitialised: Cont::cert_status; no device is touched)
+static int get_cert_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, double *out, bool primal) {
+  if (!h || (n_ids > 0 && (!ids || !out))) return MI_OSQP_ERR_NULL;
+  if (!h->cont.on) return MI_OSQP_ERR_INVALID_DATA;
+  const size_t n = (size_t)(*h->anp).n, m = (size_t)(*h->anp).m, len = primal ? m : n, stride = std::max(std::max(n, m), (size_t)1);
+  for (int64_t j = 0; j < n_ids; j++) {
+    if (ids[j] < 0 || ids[j] >= h->B) return MI_OSQP_ERR_INVALID_DATA;
+    cert_row(out + (size_t)j * len, h->cont.ch + (size_t)ids[j] * stride, len, cert_status(h->cont.cert_status[(size_t)ids[j]], primal));
+  }
+  return MI_OSQP_OK;
+}
+int mi_osqp_batch_get_prim_inf_cert_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, double *dy_out) {
+  return get_cert_some(h, n_ids, ids, dy_out, true);
+}
+int mi_osqp_batch_get_dual_inf_cert_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, double *dx_out) {
+  return get_cert_some(h, n_ids, ids, dx_out, false);
 }
 int64_t mi_osqp_batch_running(mi_osqp_batch *h) { return h && h->cont.on ? h->cont.n_running : 0; }
 int64_t mi_osqp_batch_ring_wraps(mi_osqp_batch *h) { return h ? h->cont.ring_wraps : 0; }
@@ -3407,6 +3487,8 @@ int mi_osqp_solve(mi_osqp_solver *h, mi_osqp_info *info) {
 }
 int mi_osqp_get_primal(mi_osqp_solver *h, double *x) { return h ? mi_osqp_batch_get_primal(h->b, x) : MI_OSQP_ERR_NULL; }
 int mi_osqp_get_dual(mi_osqp_solver *h, double *y) { return h ? mi_osqp_batch_get_dual(h->b, y) : MI_OSQP_ERR_NULL; }
+int mi_osqp_get_prim_inf_cert(mi_osqp_solver *h, double *dy_out) { return h ? mi_osqp_batch_get_prim_inf_cert(h->b, dy_out) : MI_OSQP_ERR_NULL; }
+int mi_osqp_get_dual_inf_cert(mi_osqp_solver *h, double *dx_out) { return h ? mi_osqp_batch_get_dual_inf_cert(h->b, dx_out) : MI_OSQP_ERR_NULL; }
 int mi_osqp_debug_refactor_chunks(int64_t n_flagged, const int64_t *flagged, int64_t n_active, const int64_t *active, int64_t tile,
                                   int64_t chunk_qps, int64_t max_chunks, int64_t *n_chunks, int64_t *work_begin, int64_t *tiles,
                                   int64_t *tile_begin) {
@@ -3652,6 +3734,14 @@ int mi_osqp_multi_batch_get_primal(mi_osqp_multi *h, double *x) {
 int mi_osqp_multi_batch_get_dual(mi_osqp_multi *h, double *y) {
   if (!h || !y) return MI_OSQP_ERR_NULL;
   return multi_fan_out(h, [&](size_t k) { return mi_osqp_batch_get_dual(h->shard[k], y + h->begin[k] * h->m); });
+}
+int mi_osqp_multi_batch_get_prim_inf_cert(mi_osqp_multi *h, double *dy_out) {
+  if (!h || !dy_out) return MI_OSQP_ERR_NULL;
+  return multi_fan_out(h, [&](size_t k) { return mi_osqp_batch_get_prim_inf_cert(h->shard[k], dy_out + h->begin[k] * h->m); });
+}
+int mi_osqp_multi_batch_get_dual_inf_cert(mi_osqp_multi *h, double *dx_out) {
+  if (!h || !dx_out) return MI_OSQP_ERR_NULL;
+  return multi_fan_out(h, [&](size_t k) { return mi_osqp_batch_get_dual_inf_cert(h->shard[k], dx_out + h->begin[k] * h->n); });
 }
 int mi_osqp_multi_batch_get_info(mi_osqp_multi *h, mi_osqp_info *info) {
   if (!h || !info) return MI_OSQP_ERR_NULL;
