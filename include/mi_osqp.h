@@ -184,6 +184,11 @@ int mi_osqp_get_dual(mi_osqp_solver *h, double *y_out);
  * NaN, obj_val = +-1e30.  m = 0: mi_osqp_get_prim_inf_cert writes nothing. */
 int mi_osqp_get_prim_inf_cert(mi_osqp_solver *h, double *dy_out /*[m]*/);
 int mi_osqp_get_dual_inf_cert(mi_osqp_solver *h, double *dx_out /*[n]*/);
+/* Adjoint derivative of the solution (OSQP 1.0 osqp_adjoint_derivative_compute / _get_mat / _get_vec; see
+ * mi_osqp_batch_adjoint_device below for the mathematics, the layouts and the status): one QP, a large one in the dataflow
+ * form included.  dx, dq [n]; dy, dl, du [m]; dP [nnz of triu(P)]; dA [nnzA]; status [1].  dy and every output may be NULL. */
+int mi_osqp_adjoint(mi_osqp_solver *h, const double *dx, const double *dy, double *dq, double *dP, double *dA, double *dl, double *du,
+                    int32_t *status);
 int mi_osqp_get_stats(mi_osqp_solver *h, mi_osqp_stats *st);
 /* Settings after setup (see "settings updates" below); a large single QP - one workgroup or the dataflow grid - included. */
 int mi_osqp_get_settings(mi_osqp_solver *h, mi_osqp_settings *out);
@@ -279,6 +284,36 @@ int mi_osqp_batch_last_polish_stats(mi_osqp_batch *h, int64_t *polished, int64_t
  * polish; in the continuous mode the call waits for the work enqueued on the handle (polishes included) and does not end
  * the mode. */
 int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act);
+
+/* -------------------------------------------------------- adjoint derivative
+ * OSQP 1.0 osqp_adjoint_derivative_compute + osqp_adjoint_derivative_get_mat + osqp_adjoint_derivative_get_vec in one call
+ * (README "Adjoint derivative").  Given dx = dL/dx [B][n] and dy = dL/dy [B][m] (NULL = zero; read on
+ * active rows only, y is 0 on the others) of a loss L(x, y) at the solutions of the last solve, the call returns the gradient
+ * of L with respect to the problem data, per QP:
+ *   dq [B][n], dl [B][m], du [B][m],
+ *   dA [B][nnzA]  in the CSC order of A,
+ *   dP [B][nnzP]  on the pattern and CSC order of the UPPER triangle of P (the upper form mi_osqp_batch_update_P takes),
+ *                 whichever form P had at setup: the derivative with respect to the stored value, which stands for (i, j)
+ *                 and (j, i).
+ * It is the derivative of the active-set solution map: the active set is taken from the current iterate by the polish rule,
+ * K = [[P, A_a'], [A_a, 0]] is factored by the polish machinery (settings delta, polish_refine_iter) and K r = [dx; dy_a] is
+ * solved; dq = -r_x, dl_i / du_i = r_y,i on the side the row is active at (an equality row: the side the rule marked),
+ * dA_k = -(y_i r_x,j + r_y,i x_j), dP_k = -(r_x,i x_j + r_x,j x_i) (diagonal: -(r_x,i x_i)).  Where strict complementarity
+ * fails (a weakly active row) the true map is not differentiable and the call returns the derivative for the marked set.
+ * The result is exact for the exact solution of the active set: solve with polish = 1 or tight tolerances for accurate
+ * gradients.  Call it after a solve and before the next update or warm start: it differentiates the data in force.
+ * status [B] (may be NULL): 1 computed; 0 the QP's last solve did not end kOptimal, or none has finished; -1 its reduced
+ * factor failed the inertia test.  The outputs of a QP whose status is not 1 read NaN.  Any output may be NULL: it is not
+ * computed.  dx is required (MI_OSQP_ERR_NULL); an output that aliases dx or dy is MI_OSQP_ERR_INVALID_DATA; a refused call
+ * has enqueued nothing.  The call changes nothing else - x, y, the iterates, rho, the ADMM factor, the infos (status_polish
+ * included) and the certificates stay bit for bit, and the next solve is the one that would have run without it - except that
+ * mi_osqp_batch_get_polish_active afterwards returns the active set the adjoint used.  Like the other whole-batch calls it
+ * ends the continuous mode.  _device: every pointer is device memory, the work is ordered on `stream` (NULL: the handle's)
+ * and finished when the call returns. */
+int mi_osqp_batch_adjoint_device(mi_osqp_batch *h, const double *d_dx, const double *d_dy, double *d_dq, double *d_dP, double *d_dA,
+                                 double *d_dl, double *d_du, int32_t *d_status, void *stream);
+int mi_osqp_batch_adjoint(mi_osqp_batch *h, const double *dx, const double *dy, double *dq, double *dP, double *dA, double *dl,
+                          double *du, int32_t *status);
 
 /* ---------------------------------------------------------- settings updates
  * OSQP 0.6.x osqp_update_* (README "Settings updates").  update_settings takes a whole struct - get, change fields, update:

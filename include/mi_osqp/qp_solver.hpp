@@ -66,6 +66,13 @@ inline QPMatrixSparse from_eigen(const EigenSparse &M_) {
 }
 #endif
 
+// QPSolver::adjointDerivative: the gradient of a loss with respect to the problem data (mi_osqp.h "adjoint derivative")
+struct QPAdjoint {
+  int status = 0;                  // 1 computed; 0 the last solve did not end kOptimal; -1 the reduced factor failed (NaN entries then)
+  QPVector dq, dl, du;             // n, m, m entries
+  std::vector<double> dP, dA;      // values on the upper triangle of P / on A, CSC order
+};
+
 class QPSolver {
  public:
   // `verbose` mirrors settings.verbose = true of the reference (log lines only).
@@ -143,6 +150,24 @@ class QPSolver {
     QPVector v((size_t)n_, std::numeric_limits<double>::quiet_NaN());
     (void)mi_osqp_get_dual_inf_cert(h_, v.data());
     return v;
+  }
+
+  // Not in the reference (OSQP 1.0 osqp_adjoint_derivative_compute / _get_mat / _get_vec): from dL/dx (n entries) and dL/dy
+  // (m entries, or empty = zero) at the solution of the last solve(), dL/d(q, P, A, l, u) of the active-set solution map
+  // (mi_osqp_adjoint).  Throws std::invalid_argument for a wrong length.
+  QPAdjoint adjointDerivative(const QPVector &dx, const QPVector &dy = {}) {
+    if ((long long)dx.size() != n_ || (!dy.empty() && (long long)dy.size() != m_)) throw std::invalid_argument(mi_osqp_error_name(MI_OSQP_ERR_INVALID_DATA));
+    mi_osqp_stats st{};
+    (void)mi_osqp_get_stats(h_, &st);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    QPAdjoint g;
+    g.dq.assign((size_t)n_, nan); g.dl.assign((size_t)m_, nan); g.du.assign((size_t)m_, nan);
+    g.dP.assign((size_t)st.nnz_P_triu, nan); g.dA.assign((size_t)st.nnz_A, nan);
+    int32_t status = 0;
+    const int rc = mi_osqp_adjoint(h_, dx.data(), dy.empty() ? nullptr : dy.data(), g.dq.data(), g.dP.data(), g.dA.data(), g.dl.data(), g.du.data(), &status);
+    if (rc != MI_OSQP_OK) throw std::invalid_argument(std::string(mi_osqp_error_name(rc)) + " (" + mi_osqp_last_error() + ")");
+    g.status = status;
+    return g;
   }
 
   // Not in the reference: settings after construction (mi_osqp.h "settings updates" - get, change fields, update).  Throws

@@ -137,6 +137,9 @@ def lib():
         L.mi_osqp_batch_last_solve_stats.argtypes = [vp, ip, ip, dp, dp, ip, dp]
         L.mi_osqp_batch_last_polish_stats.argtypes = [vp, ip, ip, dp]
         L.mi_osqp_batch_get_polish_active.argtypes = [vp, C.POINTER(C.c_int8)]
+        L.mi_osqp_batch_adjoint.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
+        L.mi_osqp_adjoint.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
+        L.mi_osqp_batch_adjoint_device.argtypes = [vp] * 10
         L.mi_osqp_batch_get_scaling.argtypes = [vp, dp, dp, dp]
         L.mi_osqp_batch_spmv.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.mi_osqp_batch_kkt_solve.argtypes = [vp, vp, vp, vp]
@@ -477,6 +480,26 @@ class BatchSolver:
         _chk(lib().mi_osqp_batch_get_polish_active(self._h, act.ctypes.data_as(C.POINTER(C.c_int8))), "get_polish_active")
         return act
 
+    # ---- adjoint derivative (OSQP 1.0 osqp_adjoint_derivative_compute / _get_mat / _get_vec; mi_osqp.h "adjoint derivative")
+    def adjoint(self, dx, dy=None):
+        """Gradient of a loss with respect to the problem data from its gradient dx [B, n] (and dy [B, m], None = 0) with
+        respect to the solutions of the last solve: dict(dq [B, n], dP [B, nnz triu(P)] (upper triangle, CSC order), dA
+        [B, nnzA], dl, du [B, m], status int32 [B]: 1 computed, 0 not kOptimal, -1 factor failed; NaN rows where not 1)."""
+        dx = _f64(dx).reshape(self.B, self.n)
+        dy = None if dy is None else _f64(dy).reshape(self.B, self.m)
+        st = self.stats()
+        out = dict(dq=np.empty((self.B, self.n)), dP=np.empty((self.B, st["nnz_P_triu"])), dA=np.empty((self.B, st["nnz_A"])),
+                   dl=np.empty((self.B, self.m)), du=np.empty((self.B, self.m)), status=np.zeros(self.B, dtype=np.int32))
+        _chk(lib().mi_osqp_batch_adjoint(self._h, _dp(dx), _dp(dy), _dp(out["dq"]), _dp(out["dP"]), _dp(out["dA"]), _dp(out["dl"]),
+                                         _dp(out["du"]), out["status"].ctypes.data_as(C.POINTER(C.c_int32))), "adjoint")
+        return out
+
+    def adjoint_device(self, dx, dy, dq=None, dP=None, dA=None, dl=None, du=None, status=None, stream=None):
+        """adjoint() on torch CUDA tensors (float64, contiguous; status int32 [B]); dy and every output may be None."""
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _chk(lib().mi_osqp_batch_adjoint_device(self._h, p(dx), p(dy), p(dq), p(dP), p(dA), p(dl), p(du), p(status),
+                                                None if stream is None else C.c_void_p(stream)), "adjoint_device")
+
     def scaling(self):
         """Ruiz scaling in force, read from the device: (D [B, n], E [B, m], c [B]); all ones with scaling = 0."""
         D, E, c = np.empty((self.B, self.n)), np.empty((self.B, self.m)), np.empty(self.B)
@@ -778,6 +801,11 @@ class QPSolver:
     def dual_inf_cert(self):
         """osqp-cpp dual_infeasibility_certificate(): [n], NaN unless the last solve ended dual infeasible."""
         return self._b.dual_inf_cert()[0]
+
+    def adjoint(self, dx, dy=None):
+        """OSQP 1.0 adjoint derivative of the last solve (BatchSolver.adjoint without the batch axis; status is an int)."""
+        out = self._b.adjoint(dx, dy)
+        return {k: (int(v[0]) if k == "status" else v[0]) for k, v in out.items()}
 
     def stats(self):
         return self._b.stats()

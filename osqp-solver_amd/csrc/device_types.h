@@ -156,6 +156,17 @@ hipError_t launch_polish_active_list(const KernelArgs &a, const PolishArgs &p, c
 hipError_t launch_polish_publish(const KernelArgs &a, const PolishArgs &p, const int *slots, int nslots, int *host_stat, int BT, hipStream_t st);
 // a = the handle's arguments with the polish factor's streams / dinv / dense-tail stream (use_work null)
 hipError_t launch_polish(const KernelArgs &a, const PolishArgs &p, int BT, int tiles, int threads, size_t lds, int n_cus, hipStream_t st);
+// adjoint derivative of the active-set solution map (adjoint_kernel; solver.hip "adjoint")
+struct AdjointArgs {
+  const double *gx, *gy;                      // dL/dx [B][n], dL/dy [B][m] (null: zero), QP-major
+  double *dq, *dP, *dA, *dl, *du;             // [B][n], [B][nnzP] (triu(P), CSC order), [B][nnzA], [B][m], [B][m]; null: not written
+  const int32_t *prow, *pcol, *arow, *acol;   // per entry of triu(P) / A: row, column
+  int nnzP, nnzA;
+};
+// a = the handle's arguments with the polish factor's streams (as launch_polish); p.stat[slot] = 1 marks the QPs to differentiate
+hipError_t launch_adjoint(const KernelArgs &a, const PolishArgs &p, const AdjointArgs &g, int BT, int tiles, int threads, size_t lds, int n_cus, hipStream_t st);
+// behind adjoint_kernel: status[slot] = stat[slot] (1 computed, 0 not kOptimal, -1 factor failed); NaN outputs where it is not 1
+hipError_t launch_adjoint_finish(const int *stat, const AdjointArgs &g, int32_t *status, int B, int n, int m, hipStream_t st);
 hipError_t launch_factor(const FactorArgs &a, int BT, int tiles, int threads, hipStream_t st);
 size_t factor_lds_bytes(int BT, int threads);
 bool factor_fits_lds(const FactorArgs &a, int threads);      // the LDS-resident form of factor_kernel<1> applies (one QP per workgroup, no group sharing)

@@ -1904,6 +1904,155 @@ __global__ __launch_bounds__(NT) void polish_kernel(KernelArgs a, PolishArgs pa)
   }
 }
 
+// Adjoint derivative of the active-set solution map (OSQP 1.0 osqp_adjoint_derivative_compute; solver.hip "adjoint", DESIGN.md
+// section 8).  After the polish factor of the marked QPs (pa.stat[slot] = 1), as polish_kernel: same forms, threads, barriers
+// and LDS; the solve-and-refine loop is polish_kernel's with another right-hand side (a copy on purpose: polish_kernel's
+// results are pinned bit for bit).  With T = diag(c D, E_a) the scaled reduced matrix is K~ = (1/c) T K T, so
+//   g~ = [c D g_x; E g_y (active rows)],   K~ r~ = g~,   r_x = D r~_x,   r_y = E r~_y / c (0 on inactive rows)
+// and, with the caller-space solution (x, y) = (x_out, y_out):
+//   dq = -r_x,  dl_i = r_y,i (lower-active),  du_i = r_y,i (upper-active),  dA_k = -(y_i r_x,j + r_y,i x_j) at (i, j),
+//   dP_k = -(r_x,i x_i) on the diagonal, -(r_x,i x_j + r_x,j x_i) off it (stored value of triu(P): it stands for both halves)
+// g~ is written once into the tile's out2 scratch, so the loop holds across a solve what polish_kernel's holds (with g_x, g_y,
+// c, D and E read inside the loop the two-QP instances lose a wave per SIMD).  The unscaled r replaces the refinement iterate
+// in pa.sol; every thread of the tile (of the grid in the dataflow form) then takes part in the loops over the stored
+// entries.  Outputs whose pointer is null are not written; QPs not marked are left to adjoint_finish_kernel.
+template <int BT, int NT, bool GX, bool WIDE = false>
+__global__ __launch_bounds__(NT) void adjoint_kernel(KernelArgs a, PolishArgs pa, AdjointArgs ga) {
+  extern __shared__ double smem[];
+  bool df = false, dfm = false;
+  if constexpr (GX && BT == 1 && WIDE) { df = a.df != 0; dfm = df && a.mw_groups > 1; }
+  const Mw mw{a.mw_bar, dfm ? (unsigned)a.mw_groups : 1u};
+  const int tile = dfm ? 0 : blockIdx.x;
+  const int tid = dfm ? blockIdx.x * blockDim.x + threadIdx.x : threadIdx.x, nthr = dfm ? blockDim.x * mw.G : blockDim.x;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nthr >> 6;
+  const int b = tid % BT;
+  auto sync = [&]() { if constexpr (GX && BT == 1 && WIDE) wg_or_grid_barrier(mw); else __syncthreads(); };
+  const int n = a.n, m = a.m, N = a.N;
+  const uint32_t sh = a.df_shadow;
+  double *red;
+  double *xs = solve_vector<BT, GX>(a, smem, tile, red);
+  TilePtrs<BT> p = tile_ptrs<BT>(a, tile);
+  p.act = 0;
+#pragma unroll
+  for (int bb = 0; bb < BT; bb++) {       // QPs not marked stream nothing (same for every thread: wave-uniform)
+    const int sl = tile * BT + bb;
+    if (sl < a.B && pa.stat[sl] == 1) { p.act |= 1 << bb; continue; }
+    p.vfwd.vals[bb] = make_rsrc(nullptr, 0u); p.vbwd.vals[bb] = make_rsrc(nullptr, 0u);
+    p.vchk.vals[bb] = make_rsrc(nullptr, 0u); p.vdt[bb] = make_rsrc(nullptr, 0u);
+  }
+  if (!p.act) return;
+  const int slot = tile * BT + b;
+  const bool on = (p.act >> b) & 1;
+  const size_t so = on ? slot : 0;             // (a QP that is not marked reads the rows of QP 0: in bounds, unused)
+  const signed char *act = pa.act + so * m;
+  double *s = pa.sol + (size_t)tile * N * BT;
+  auto put_rhs = [&](int e, double v) {        // natural entry e / BT of the right-hand side -> the solve vector
+    const uint32_t pe = a.pinv[e / BT];
+    if (df) { st_sc1(xs + pe, v); df_arm_fwd(xs, pe, a.rflag[pe], a.xloc[pe], sh); }
+    else xs[(size_t)pe * BT + b] = v;
+  };
+  auto get_sol = [&](int e) -> double {
+    const uint32_t pe = a.pinv[e / BT];
+    return df ? ld_sc1(xs + df_bloc(pe, a.rflag[pe], sh)) : xs[(size_t)pe * BT + b];
+  };
+  const size_t nB = (size_t)n * BT;
+  {    // g~ once, into out2 (scratch of the polish as well): the loop below then reads one array, as polish_kernel reads q, l, u
+    const double cs = a.scaling ? p.dscal[DS_C * BT + b] : 1.0;
+    for (int e = tid; e < N * BT; e += nthr) {
+      double v = 0.0;
+      if (on) {
+        const int i = e / BT;
+        if (i < n) {
+          v = ga.gx[so * n + i];
+          if (a.scaling) v *= cs * p.Dsc[e];
+        } else if (act[i - n] && ga.gy) {
+          v = ga.gy[so * m + (i - n)];
+          if (a.scaling) v *= p.Esc[e - (int)nB];
+        }
+      }
+      p.out2[e] = v;
+    }
+  }
+  for (int r = 0; r <= pa.refine_iter; r++) {
+    if (r > 0) {
+      for (int e = tid; e < N * BT; e += nthr) xs[e] = s[e];
+      sync();
+      run_spmv<BT, MI_PFV, WIDE>(a.chk, p.vchk, xs, p.out1, wave, lane, 0, 3, nw);
+      sync();
+    }
+    for (int e = tid; e < N * BT; e += nthr) {
+      double v = p.out2[e];
+      if (on && r > 0) {
+        const int i = e / BT;
+        if (i < n) v -= p.out1[e] + p.out1[nB + e];
+        else if (act[i - n]) v -= p.out1[2 * nB + (e - (int)nB)];
+      }
+      put_rhs(e, v);
+    }
+    if (df && tid == 0) st_sc1(xs + 2 * (size_t)sh, 0.0);
+    sync();
+    kkt_solve_lds<BT, MI_PFV_NT(NT, GX), GX, WIDE>(a, p, xs, tid, nthr, wave, nw, lane, mw);
+    for (int e = tid; e < N * BT; e += nthr) {
+      const int i = e / BT;
+      double d = get_sol(e);
+      if (i >= n && !act[i - n]) d = 0.0;
+      s[e] = r ? s[e] + d : d;
+    }
+    sync();
+  }
+  // r = T r~ / c in place of the refinement iterate; dq, dl, du
+  const double cinv = a.scaling ? p.dscal[DS_CINV * BT + b] : 1.0;
+  for (int e = tid; e < N * BT; e += nthr) {
+    const int i = e / BT;
+    double v = s[e];
+    if (a.scaling) v *= i < n ? p.Dsc[e] : p.Esc[e - (int)nB] * cinv;
+    s[e] = v;
+    if (!on) continue;
+    if (i < n) {
+      if (ga.dq) ga.dq[(size_t)slot * n + i] = -v;
+    } else {
+      const signed char c = act[i - n];
+      if (ga.dl) ga.dl[(size_t)slot * m + (i - n)] = c < 0 ? v : 0.0;
+      if (ga.du) ga.du[(size_t)slot * m + (i - n)] = c > 0 ? v : 0.0;
+    }
+  }
+  sync();
+  // the stored values of triu(P) and A, natural CSC order: every thread of the tile serves every marked QP of it
+#pragma unroll
+  for (int bb = 0; bb < BT; bb++) {
+    if (!((p.act >> bb) & 1)) continue;
+    const size_t sl = (size_t)tile * BT + bb;
+    const double *xo = a.x_out + sl * n, *yo = a.y_out + sl * m;
+    if (ga.dP) {
+      double *dP = ga.dP + sl * ga.nnzP;
+      for (int k = tid; k < ga.nnzP; k += nthr) {
+        const int i = ga.prow[k], j = ga.pcol[k];
+        const double ri = s[(size_t)i * BT + bb], rj = s[(size_t)j * BT + bb];
+        dP[k] = i == j ? -(ri * xo[i]) : -(ri * xo[j] + rj * xo[i]);
+      }
+    }
+    if (ga.dA) {
+      double *dA = ga.dA + sl * ga.nnzA;
+      for (int k = tid; k < ga.nnzA; k += nthr) {
+        const int i = ga.arow[k], j = ga.acol[k];
+        dA[k] = -(yo[i] * s[(size_t)j * BT + bb] + s[nB + (size_t)i * BT + bb] * xo[j]);
+      }
+    }
+  }
+}
+// Behind adjoint_kernel, one workgroup per QP: the per-QP status, and NaN in every requested output of a QP that has none
+// (its last solve did not end kOptimal, or its reduced factor failed the inertia test) - the convention of the certificates.
+__global__ void adjoint_finish_kernel(const int *__restrict__ stat, AdjointArgs ga, int32_t *status, int n, int m) {
+  const int slot = blockIdx.x, st = stat[slot];
+  if (status && threadIdx.x == 0) status[slot] = st;
+  if (st == 1) return;
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  auto fill = [&](double *dst, int len) {
+    if (dst) for (int i = threadIdx.x; i < len; i += blockDim.x) dst[(size_t)slot * len + i] = nan;
+  };
+  fill(ga.dq, n); fill(ga.dP, ga.nnzP); fill(ga.dA, ga.nnzA); fill(ga.dl, m); fill(ga.du, m);
+}
+
 // Debug twin of kkt_solve_kernel<2, 512, false> (MI_OSQP trace entry point, scripts/trace_phases.py): same
 // solve, plus per-phase / per-wave shader-clock stamps of tiles {0, gridDim/2} copied to trace[2][words].
 // Layout of one tile's words: [0..3] = memtime / memrealtime at start and end (low words), [4..5] = memtime before / after
@@ -3919,6 +4068,22 @@ hipError_t launch_polish(const KernelArgs &a, const PolishArgs &p, int BT, int t
     tiles = a.mw_groups;
   }
   MI_DISPATCH(polish_kernel, a, p);
+}
+hipError_t launch_adjoint(const KernelArgs &a, const PolishArgs &p, const AdjointArgs &g, int BT, int tiles, int threads, size_t lds, int n_cus, hipStream_t st) {
+  if (a.df && a.mw_groups > 1) {
+    // the grid spins on its barriers: every workgroup must be resident at once
+    if (tiles != 1 || BT != 1 || !a.xs_global || !a.wide || !a.mw_bar) return hipErrorInvalidValue;
+    int nb = 0;
+    const void *k = reinterpret_cast<const void *>(&adjoint_kernel<1, 512, true, true>);
+    if (ensure_dynamic_lds(k, lds) != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds) != hipSuccess ||
+        nb * n_cus < a.mw_groups) return hipErrorInvalidValue;
+    tiles = a.mw_groups;
+  }
+  MI_DISPATCH(adjoint_kernel, a, p, g);
+}
+hipError_t launch_adjoint_finish(const int *stat, const AdjointArgs &g, int32_t *status, int B, int n, int m, hipStream_t st) {
+  hipLaunchKernelGGL(adjoint_finish_kernel, dim3(B), dim3(256), 0, st, stat, g, status, n, m);
+  return hipGetLastError();
 }
 hipError_t launch_kkt_trace(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st,
                             const double *rhs, double *sol, uint32_t *trace, uint32_t words) {

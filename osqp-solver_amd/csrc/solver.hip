@@ -337,7 +337,7 @@ struct mi_osqp_batch {
   int64_t last_total_iters = 0, last_launches = 0, last_refactors = 0;
   double last_device_s = 0.0, last_refactor_s = 0.0, kernel_ms_sum = 0.0;
   int64_t kernel_launches = 0, kernel_qp_iters = 0;
-  bool solved_once = false;
+  bool solved_once = false;             // the status words of iscal are valid: a blocking solve has finished, or the continuous mode was entered
   // per-QP failure isolation: QPs whose KKT factor lost its inertia (at setup, in an update or in a rho update).  They
   // report kNonConvex with a NaN solution on every solve until a later refactorisation of theirs succeeds; the rest
   // of the batch is unaffected ([REF] src/osqp-wrapper.h:51-54: solve() never throws, one exit code per solver).
@@ -354,6 +354,7 @@ struct mi_osqp_batch {
   int64_t pol_count = 0, pol_accepted = 0;
   double pol_seconds = 0.0;
   hipEvent_t evp0 = nullptr, evp1 = nullptr;
+  DevBuf<int> adj_stat;                 // adjoint derivative (section "adjoint"): its own per-QP marks / results (pol_stat belongs to the polish)
   // ---- continuous batching (the per-QP entry points + advance / poll; section "continuous" below)
   struct Cont {
     bool on = false;
@@ -1369,6 +1370,49 @@ static int polish_impl(mi_osqp_batch *h, const KernelArgs &a) {
   return MI_OSQP_OK;
 }
 
+// ------------------------------------------------------------------- adjoint
+// Adjoint derivative of the solution (mi_osqp.h mi_osqp_batch_adjoint_device; DESIGN.md section 8, "Adjoint derivative"): the
+// polish chain with another last kernel.  The active set of every QP whose last solve ended kOptimal from its current iterate
+// (polish_active_kernel - after an accepted polish that is the polished set), the reduced KKT matrix of those QPs factored
+// into the polish buffers (device_refactor_slots in polish mode), adjoint_kernel, adjoint_finish_kernel (statuses, NaN rows).
+// The marks live in adj_stat, not pol_stat, and nothing a solve reads is written: the iterates, rho, the ADMM factor, the
+// infos and the certificates stay as they are (out1 / pol_sol / the polish buffers are scratch of the polish as well).
+static int adjoint_impl(mi_osqp_batch *h, const AdjointArgs &ga, int32_t *d_status, hipStream_t user_stream) {
+  hipStream_t keep = h->stream;
+  struct Restore { mi_osqp_batch *h; hipStream_t s; ~Restore() { h->stream = s; } } restore{h, keep};
+  if (user_stream) h->stream = user_stream;
+  const Analysis &an = (*h->anp);
+  const int BT = h->BT, ntl = h->ntiles;
+  int rc;
+  if ((rc = ensure_polish_buffers(h))) return rc;
+  if (!h->adj_stat.p && ((rc = h->adj_stat.alloc((size_t)ntl * BT)))) return rc;
+  if ((rc = h->adj_stat.zero(h->stream))) return rc;
+  std::vector<int> work;                // the QPs whose last solve ended kOptimal
+  if (h->solved_once) {                 // (before that the status words are not initialised; the continuous mode sets it too)
+    HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)ntl * IS_COUNT * BT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int q = 0; q < h->B; q++)
+      if (h->h_iscal[(size_t)(q / BT) * IS_COUNT * BT + IS_STATUS * BT + q % BT] == 1) work.push_back(q);
+  }
+  if (!work.empty()) {
+    const KernelArgs a = make_args(h);
+    PolishArgs pa{h->adj_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter};
+    HIPCHK(launch_polish_active(a, pa, BT, h->stream));
+    if ((rc = device_refactor_slots(h, std::move(work), nullptr, &pa))) return rc;
+    KernelArgs ap = a;
+    ap.fwd_val = h->pol_fwd.p; ap.bwd_val = h->pol_bwd.p; ap.dinv = h->pol_dinv.p; ap.dt_val = h->pol_dt.p; ap.use_work = nullptr;
+    std::unique_lock<std::mutex> spin_lock(spin_mutex(h->device), std::defer_lock);
+    if (h->mw_groups > 0) { spin_lock.lock(); HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), h->stream)); }
+    HIPCHK(launch_adjoint(ap, pa, ga, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds, h->n_cus, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (spin_lock.owns_lock()) spin_lock.unlock();
+    if ((rc = mw_barrier_ok(h))) return rc;
+  }
+  HIPCHK(launch_adjoint_finish(h->adj_stat.p, ga, d_status, h->B, an.n, an.m, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return MI_OSQP_OK;
+}
+
 // ------------------------------------------------ pipelined refactorisation
 // A long work list at a rho-update point ("Pipelined refactorisation"): no tile shares anything with
 // another, so a tile may start the next segment as soon as the factors of its own QPs are written.  The work list is cut into
@@ -1782,6 +1826,54 @@ int mi_osqp_batch_get_polish_active(mi_osqp_batch *h, int8_t *act) {
   DevGuard guard(h->device);
   if (h->cont.on) HIPCHK(hipStreamSynchronize(h->stream));      // (polish_some only enqueues; the continuous mode goes on)
   if (cnt) HIPCHK(hipMemcpy(act, h->pol_act.p, cnt, hipMemcpyDeviceToHost));
+  return MI_OSQP_OK;
+}
+
+// Adjoint derivative (mi_osqp.h; section "adjoint" above).  Refusals come before anything is enqueued.
+static AdjointArgs adjoint_args(mi_osqp_batch *h, const double *d_dx, const double *d_dy, double *d_dq, double *d_dP, double *d_dA,
+                                double *d_dl, double *d_du) {
+  const Analysis &an = (*h->anp);
+  AdjointArgs ga{};
+  ga.gx = d_dx; ga.gy = d_dy; ga.dq = d_dq; ga.dP = d_dP; ga.dA = d_dA; ga.dl = d_dl; ga.du = d_du;
+  ga.prow = h->rz_prow.p; ga.pcol = h->rz_pcol.p; ga.arow = h->rz_arow.p; ga.acol = h->rz_acol.p;
+  ga.nnzP = (int)an.Pp[an.n]; ga.nnzA = (int)an.Ap[an.n];
+  return ga;
+}
+int mi_osqp_batch_adjoint_device(mi_osqp_batch *h, const double *d_dx, const double *d_dy, double *d_dq, double *d_dP, double *d_dA,
+                                 double *d_dl, double *d_du, int32_t *d_status, void *stream) {
+  CallTimer timer_("batch_adjoint_device");
+  if (!h) return MI_OSQP_ERR_NULL;
+  if (!d_dx) { g_last_error = "adjoint: dx is null (dL/dx is required; only dy may be null)"; return MI_OSQP_ERR_NULL; }
+  for (const double *o : {(const double *)d_dq, (const double *)d_dP, (const double *)d_dA, (const double *)d_dl, (const double *)d_du})
+    if (o && (o == d_dx || o == d_dy)) { g_last_error = "adjoint: an output aliases dx or dy"; return MI_OSQP_ERR_INVALID_DATA; }
+  DevGuard guard(h->device);
+  { const int rc_ = cont_leave(h); if (rc_) return rc_; }
+  return adjoint_impl(h, adjoint_args(h, d_dx, d_dy, d_dq, d_dP, d_dA, d_dl, d_du), d_status, (hipStream_t)stream);
+}
+int mi_osqp_batch_adjoint(mi_osqp_batch *h, const double *dx, const double *dy, double *dq, double *dP, double *dA, double *dl,
+                          double *du, int32_t *status) {
+  CallTimer timer_("batch_adjoint");
+  if (!h) return MI_OSQP_ERR_NULL;
+  if (!dx) { g_last_error = "adjoint: dx is null (dL/dx is required; only dy may be null)"; return MI_OSQP_ERR_NULL; }
+  DevGuard guard(h->device);
+  { const int rc_ = cont_leave(h); if (rc_) return rc_; }
+  const Analysis &an = (*h->anp);
+  const size_t B = (size_t)h->B, n = (size_t)an.n, m = (size_t)an.m, nnzP = (size_t)an.Pp[an.n], nnzA = (size_t)an.Ap[an.n];
+  // one device block: dx, dy, then the requested outputs
+  const size_t len[7] = {B * n, dy ? B * m : 0, dq ? B * n : 0, dP ? B * nnzP : 0, dA ? B * nnzA : 0, dl ? B * m : 0, du ? B * m : 0};
+  size_t off[8] = {0};
+  for (int k = 0; k < 7; k++) off[k + 1] = off[k] + len[k];
+  DevBuf<double> buf;
+  DevBuf<int> stat;
+  int rc;
+  if ((rc = buf.alloc(off[7])) || (rc = stat.alloc(B))) return rc;
+  auto at = [&](int k) -> double * { return len[k] ? buf.p + off[k] : nullptr; };
+  HIPCHK(hipMemcpy(at(0), dx, len[0] * sizeof(double), hipMemcpyHostToDevice));
+  if (len[1]) HIPCHK(hipMemcpy(at(1), dy, len[1] * sizeof(double), hipMemcpyHostToDevice));
+  if ((rc = adjoint_impl(h, adjoint_args(h, at(0), at(1), at(2), at(3), at(4), at(5), at(6)), stat.p, nullptr))) return rc;
+  double *out[7] = {nullptr, nullptr, dq, dP, dA, dl, du};
+  for (int k = 2; k < 7; k++) if (len[k]) HIPCHK(hipMemcpy(out[k], at(k), len[k] * sizeof(double), hipMemcpyDeviceToHost));
+  if (status) HIPCHK(hipMemcpy(status, stat.p, B * sizeof(int32_t), hipMemcpyDeviceToHost));
   return MI_OSQP_OK;
 }
 
@@ -2546,10 +2638,12 @@ static int cont_enter(mi_osqp_batch *h) {
     for (int b = 0; b < BT; b++) {
       int *p = h->h_iscal + (size_t)t * IS_COUNT * BT;
       p[IS_DONE * BT + b] = 1; p[IS_CUR * BT + b] = 0; p[IS_PENDING * BT + b] = 0; p[IS_EPOCH * BT + b] = 0;
+      if (!h->solved_once) p[IS_STATUS * BT + b] = 0;      // (no solve yet: the word is not initialised, and the adjoint reads it)
       if (h->clear_rho_updates) p[IS_RHO_UPDATES * BT + b] = 0;
       if (t * BT + b < B && h->failed[(size_t)t * BT + b]) p[IS_NEED_REFACTOR * BT + b] = -1;
     }
   h->clear_rho_updates = false;
+  h->solved_once = true;               // (from here on every status word is either 0 or what a finished solve left)
   HIPCHK(hipMemcpyAsync(h->iscal.p, h->h_iscal, icnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
   memcpy(c.h_is[0], h->h_iscal, icnt * sizeof(int)); memcpy(c.h_is[1], h->h_iscal, icnt * sizeof(int));      // the host images advance_kernel writes
   if (!c.stop.p && (rc = c.stop.alloc(4))) return rc;
@@ -3489,6 +3583,10 @@ int mi_osqp_get_primal(mi_osqp_solver *h, double *x) { return h ? mi_osqp_batch_
 int mi_osqp_get_dual(mi_osqp_solver *h, double *y) { return h ? mi_osqp_batch_get_dual(h->b, y) : MI_OSQP_ERR_NULL; }
 int mi_osqp_get_prim_inf_cert(mi_osqp_solver *h, double *dy_out) { return h ? mi_osqp_batch_get_prim_inf_cert(h->b, dy_out) : MI_OSQP_ERR_NULL; }
 int mi_osqp_get_dual_inf_cert(mi_osqp_solver *h, double *dx_out) { return h ? mi_osqp_batch_get_dual_inf_cert(h->b, dx_out) : MI_OSQP_ERR_NULL; }
+int mi_osqp_adjoint(mi_osqp_solver *h, const double *dx, const double *dy, double *dq, double *dP, double *dA, double *dl, double *du,
+                    int32_t *status) {
+  return h ? mi_osqp_batch_adjoint(h->b, dx, dy, dq, dP, dA, dl, du, status) : MI_OSQP_ERR_NULL;
+}
 int mi_osqp_debug_refactor_chunks(int64_t n_flagged, const int64_t *flagged, int64_t n_active, const int64_t *active, int64_t tile,
                                   int64_t chunk_qps, int64_t max_chunks, int64_t *n_chunks, int64_t *work_begin, int64_t *tiles,
                                   int64_t *tile_begin) {
