@@ -1707,6 +1707,12 @@ __global__ __launch_bounds__(NT) void kkt_solve_kernel(KernelArgs a, const doubl
 // ---- solution polishing (OSQP polish.c on the scaled data; solver.hip "polish") ----------------------------------------
 // Before the polish factor: the active set of every kOptimal QP from its final iterate (z, y):
 //   lower-active  z_j - l_j < -y_j,   upper-active  u_j - z_j < y_j   (l <= u: never both)
+__device__ __forceinline__ signed char active_row(const KernelArgs &a, size_t k) {      // k = (tile * m + row) * BT + b
+  const double z = a.z[k], y = a.y[k];
+  if (z - a.l[k] < -y) return -1;
+  if (a.u[k] - z < y) return 1;
+  return 0;
+}
 // one thread per (QP, row); the thread of row m marks the QP as one to polish.
 __global__ void polish_active_kernel(KernelArgs a, PolishArgs pa, int BT) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x, per = (size_t)a.m + 1;
@@ -1715,14 +1721,7 @@ __global__ void polish_active_kernel(KernelArgs a, PolishArgs pa, int BT) {
   const size_t t = (size_t)slot / BT, b = (size_t)slot % BT;
   const bool cand = a.iscal[(t * IS_COUNT + IS_STATUS) * BT + b] == 1;
   if (j == m) { pa.stat[slot] = cand ? 1 : 0; return; }
-  signed char s = 0;
-  if (cand) {
-    const size_t k = (t * m + j) * BT + b;
-    const double z = a.z[k], y = a.y[k];
-    if (z - a.l[k] < -y) s = -1;
-    else if (a.u[k] - z < y) s = 1;
-  }
-  pa.act[(size_t)slot * m + j] = s;
+  pa.act[(size_t)slot * m + j] = cand ? active_row(a, (t * m + j) * BT + b) : 0;
 }
 // The same for a list of slots (continuous mode, mi_osqp_batch_polish_some): one workgroup per listed slot, the other slots'
 // active sets and marks are left alone (an earlier call's QPs may be waiting for their report).
@@ -1731,16 +1730,7 @@ __global__ void polish_active_list_kernel(KernelArgs a, PolishArgs pa, const int
   if (slot < 0 || slot >= a.B) return;
   const size_t t = (size_t)slot / BT, b = (size_t)slot % BT;
   const bool cand = a.iscal[(t * IS_COUNT + IS_STATUS) * BT + b] == 1;
-  for (int j = threadIdx.x; j < m; j += blockDim.x) {
-    signed char s = 0;
-    if (cand) {
-      const size_t k = (t * m + j) * BT + b;
-      const double z = a.z[k], y = a.y[k];
-      if (z - a.l[k] < -y) s = -1;
-      else if (a.u[k] - z < y) s = 1;
-    }
-    pa.act[(size_t)slot * m + j] = s;
-  }
+  for (int j = threadIdx.x; j < m; j += blockDim.x) pa.act[(size_t)slot * m + j] = cand ? active_row(a, (t * m + j) * BT + b) : 0;
   if (threadIdx.x == 0) pa.stat[slot] = cand ? 1 : 0;
 }
 // End of a polish_some chain, after polish_kernel: the listed slots' results go to the pinned image poll() reads and their
@@ -1757,107 +1747,140 @@ __global__ void polish_publish_kernel(KernelArgs a, PolishArgs pa, const int *__
   a.iscal[((size_t)(slot / BT) * IS_COUNT + IS_EPOCH) * BT + slot % BT] += 1;
 }
 
-// After the polish factor (a's streams / dinv / dense-tail stream are the polish factor's): for the QPs marked 1
-//   s = K_d^-1 b, then refine_iter rounds of  s += K_d^-1 (b - K s)      K_d = [[P + d I, A~'], [A~, -d I]], K: d = 0
-//   b = [-q; l_j (lower-active) | u_j (upper-active) | 0 (inactive)],  A~ = A without its inactive rows
-// then x = s_x, z = A x, y = s_y (0 on inactive rows), the projection t = z + y, z = clip(t, l, u), y = t - z, the
-// residuals and the objective exactly as check_kernel computes them, and the acceptance test against the residuals of the
-// termination check.  Accepted: the polished point becomes the iterate, the solution and the info of the QP.
-// K s runs through the check schedule (P x / A'y / A x): A~'s_y = A's_y (s_y is 0 on inactive rows), A~ s_x = A s_x
-// masked.  Thread / barrier structure as check_body (one QP shared by the grid in the dataflow form).
-template <int BT, int NT, bool GX, bool WIDE = false>
-__global__ __launch_bounds__(NT) void polish_kernel(KernelArgs a, PolishArgs pa) {
-  extern __shared__ double smem[];
-  bool df = false, dfm = false;
-  if constexpr (GX && BT == 1 && WIDE) { df = a.df != 0; dfm = df && a.mw_groups > 1; }
-  const Mw mw{a.mw_bar, dfm ? (unsigned)a.mw_groups : 1u};
-  const int tile = dfm ? 0 : blockIdx.x;
-  const int ltid = threadIdx.x, lwave = __builtin_amdgcn_readfirstlane(ltid >> 6), lnw = blockDim.x >> 6;
-  const int tid = dfm ? blockIdx.x * blockDim.x + threadIdx.x : threadIdx.x, nthr = dfm ? blockDim.x * mw.G : blockDim.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nthr >> 6;
-  const int b = tid % BT;
-  auto sync = [&]() { if constexpr (GX && BT == 1 && WIDE) wg_or_grid_barrier(mw); else __syncthreads(); };
-  auto gscratch = [&](int slot) { return a.mw_scratch + (size_t)slot * 256 * 16; };
-  const int n = a.n, m = a.m, N = a.N;
-  const uint32_t sh = a.df_shadow;
-  double *red;
-  double *xs = solve_vector<BT, GX>(a, smem, tile, red);
-  TilePtrs<BT> p = tile_ptrs<BT>(a, tile);
-  p.act = 0;
+// ---- the reduced KKT solve polish_kernel and adjoint_kernel share --------------------------------------------------------
+// Both run after the polish factor (a's streams / dinv / dense-tail stream are the polish factor's) on the QPs marked
+// pa.stat[slot] = 1, with the thread / barrier structure of check_body (one QP shared by the grid in the dataflow form).
+// ReducedTile is what a thread knows of its tile: who it is, the solve vector, the tile's arrays with the marks folded into
+// p.act (QPs not marked stream nothing), its QP's active set and the refinement iterate s.
+template <int BT, bool GX, bool WIDE>
+struct ReducedTile {
+  const KernelArgs &a;
+  bool df = false, dfm = false;      // dataflow sweeps; the grid of workgroups that shares the one QP
+  Mw mw;
+  int tile, ltid, lwave, lnw;        // (l*: within the workgroup, for its reductions)
+  int tid, nthr, lane, wave, nw, b;  // within the tile: the workgroup, or the whole grid when dfm
+  double *xs, *red;
+  TilePtrs<BT> p;
+  int slot;                          // the QP of lane class b,
+  bool on;                           // whether it is marked,
+  const signed char *act;            // its active set (a QP that is not marked reads the rows of QP 0: in bounds, unused)
+  double *s;                         // the tile's refinement iterate [x; y_red], natural order
+
+  __device__ __forceinline__ ReducedTile(const KernelArgs &a_, const PolishArgs &pa, double *smem) : a(a_) {
+    if constexpr (GX && BT == 1 && WIDE) { df = a.df != 0; dfm = df && a.mw_groups > 1; }
+    mw = Mw{a.mw_bar, dfm ? (unsigned)a.mw_groups : 1u};
+    tile = dfm ? 0 : blockIdx.x;
+    ltid = threadIdx.x; lwave = __builtin_amdgcn_readfirstlane(ltid >> 6); lnw = blockDim.x >> 6;
+    tid = dfm ? blockIdx.x * blockDim.x + threadIdx.x : threadIdx.x; nthr = dfm ? blockDim.x * mw.G : blockDim.x;
+    lane = tid & 63; wave = __builtin_amdgcn_readfirstlane(tid >> 6); nw = nthr >> 6;
+    b = tid % BT;
+    xs = solve_vector<BT, GX>(a, smem, tile, red);
+    p = tile_ptrs<BT>(a, tile);
+    p.act = 0;
 #pragma unroll
-  for (int bb = 0; bb < BT; bb++) {       // QPs not polished stream nothing (same for every thread: wave-uniform)
-    const int sl = tile * BT + bb;
-    if (sl < a.B && pa.stat[sl] == 1) { p.act |= 1 << bb; continue; }
-    p.vfwd.vals[bb] = make_rsrc(nullptr, 0u); p.vbwd.vals[bb] = make_rsrc(nullptr, 0u);
-    p.vchk.vals[bb] = make_rsrc(nullptr, 0u); p.vdt[bb] = make_rsrc(nullptr, 0u);
+    for (int bb = 0; bb < BT; bb++) {       // QPs not marked stream nothing (same for every thread: wave-uniform)
+      const int sl = tile * BT + bb;
+      if (sl < a.B && pa.stat[sl] == 1) { p.act |= 1 << bb; continue; }
+      p.vfwd.vals[bb] = make_rsrc(nullptr, 0u); p.vbwd.vals[bb] = make_rsrc(nullptr, 0u);
+      p.vchk.vals[bb] = make_rsrc(nullptr, 0u); p.vdt[bb] = make_rsrc(nullptr, 0u);
+    }
+    slot = tile * BT + b;
+    on = (p.act >> b) & 1;
+    act = pa.act + (size_t)(on ? slot : 0) * a.m;
+    s = pa.sol + (size_t)tile * a.N * BT;
   }
-  if (!p.act) return;
-  const int slot = tile * BT + b;
-  const bool on = (p.act >> b) & 1;
-  const signed char *act = pa.act + (size_t)(on ? slot : 0) * m;
-  double *s = pa.sol + (size_t)tile * N * BT;
-  auto put_rhs = [&](int e, double v) {        // natural entry e / BT of the right-hand side -> the solve vector
-    const uint32_t pe = a.pinv[e / BT];
+  __device__ __forceinline__ void sync() const { if constexpr (GX && BT == 1 && WIDE) wg_or_grid_barrier(mw); else __syncthreads(); }
+  __device__ __forceinline__ void put_rhs(int e, double v) const {      // natural entry e / BT of the right-hand side -> the solve vector
+    const uint32_t pe = a.pinv[e / BT], sh = a.df_shadow;
     if (df) { st_sc1(xs + pe, v); df_arm_fwd(xs, pe, a.rflag[pe], a.xloc[pe], sh); }
     else xs[(size_t)pe * BT + b] = v;
-  };
-  auto get_sol = [&](int e) -> double {
+  }
+  __device__ __forceinline__ double get_sol(int e) const {
     const uint32_t pe = a.pinv[e / BT];
-    return df ? ld_sc1(xs + df_bloc(pe, a.rflag[pe], sh)) : xs[(size_t)pe * BT + b];
-  };
-  const size_t nB = (size_t)n * BT, mB = (size_t)m * BT;
-  auto spmv = [&]() {                           // natural [x; y] in xs -> P x, A'y, A x in out1
+    return df ? ld_sc1(xs + df_bloc(pe, a.rflag[pe], a.df_shadow)) : xs[(size_t)pe * BT + b];
+  }
+  __device__ __forceinline__ void spmv() const {        // natural [x; y] in xs -> P x, A'y, A x in out1
     sync();
     run_spmv<BT, MI_PFV, WIDE>(a.chk, p.vchk, xs, p.out1, wave, lane, 0, 3, nw);
     sync();
-  };
-  for (int r = 0; r <= pa.refine_iter; r++) {
+  }
+};
+// s = K_d^-1 b, then refine_iter rounds of  s += K_d^-1 (b - K s)      K_d = [[P + d I, A~'], [A~, -d I]], K: d = 0,
+// A~ = A without its inactive rows.  rhs0(e) = entry e of b in natural order (0 on inactive rows and for a QP not marked).
+// K s runs through the check schedule (P x / A'y / A x): A~'s_y = A's_y (s_y is 0 on inactive rows), A~ s_x = A s_x masked.
+template <int BT, int NT, bool GX, bool WIDE, class Rhs0>
+__device__ __forceinline__ void reduced_solve_refine(const ReducedTile<BT, GX, WIDE> &c, int refine_iter, Rhs0 rhs0) {
+  const KernelArgs &a = c.a;
+  const int n = a.n, N = a.N, tid = c.tid, nthr = c.nthr;
+  const size_t nB = (size_t)n * BT;
+  double *xs = c.xs, *s = c.s;
+  for (int r = 0; r <= refine_iter; r++) {
     if (r > 0) {
       for (int e = tid; e < N * BT; e += nthr) xs[e] = s[e];
-      spmv();
+      c.spmv();
     }
     for (int e = tid; e < N * BT; e += nthr) {
-      double v = 0.0;
-      if (on) {
+      double v = rhs0(e);
+      if (c.on && r > 0) {
         const int i = e / BT;
-        if (i < n) {
-          v = -p.q[e];
-          if (r > 0) v -= p.out1[e] + p.out1[nB + e];
-        } else {
-          const int ez = e - (int)nB;
-          const signed char c = act[i - n];
-          if (c) {
-            v = c < 0 ? p.l[ez] : p.u[ez];
-            if (r > 0) v -= p.out1[2 * nB + ez];
-          }
-        }
+        if (i < n) v -= c.p.out1[e] + c.p.out1[nB + e];
+        else if (c.act[i - n]) v -= c.p.out1[2 * nB + (e - (int)nB)];
       }
-      put_rhs(e, v);
+      c.put_rhs(e, v);
     }
-    if (df && tid == 0) st_sc1(xs + 2 * (size_t)sh, 0.0);
-    sync();
-    kkt_solve_lds<BT, MI_PFV_NT(NT, GX), GX, WIDE>(a, p, xs, tid, nthr, wave, nw, lane, mw);
+    if (c.df && tid == 0) st_sc1(xs + 2 * (size_t)a.df_shadow, 0.0);
+    c.sync();
+    kkt_solve_lds<BT, MI_PFV_NT(NT, GX), GX, WIDE>(a, c.p, xs, tid, nthr, c.wave, c.nw, c.lane, c.mw);
     for (int e = tid; e < N * BT; e += nthr) {
       const int i = e / BT;
-      double d = get_sol(e);
-      if (i >= n && !act[i - n]) d = 0.0;
+      double d = c.get_sol(e);
+      if (i >= n && !c.act[i - n]) d = 0.0;
       s[e] = r ? s[e] + d : d;
     }
-    sync();
+    c.sync();
   }
+}
+
+// Polish of the marked QPs: the reduced solve with
+//   b = [-q; l_j (lower-active) | u_j (upper-active) | 0 (inactive)]
+// then x = s_x, z = A x, y = s_y (0 on inactive rows), the projection t = z + y, z = clip(t, l, u), y = t - z, the
+// residuals and the objective exactly as check_kernel computes them, and the acceptance test against the residuals of the
+// termination check.  Accepted: the polished point becomes the iterate, the solution and the info of the QP.
+template <int BT, int NT, bool GX, bool WIDE = false>
+__global__ __launch_bounds__(NT) void polish_kernel(KernelArgs a, PolishArgs pa) {
+  extern __shared__ double smem[];
+  const ReducedTile<BT, GX, WIDE> c(a, pa, smem);
+  if (!c.p.act) return;
+  const Mw mw = c.mw;
+  const int ltid = c.ltid, lwave = c.lwave, lnw = c.lnw, tid = c.tid, nthr = c.nthr, lane = c.lane, b = c.b, slot = c.slot;
+  const bool on = c.on;
+  const TilePtrs<BT> &p = c.p;
+  double *xs = c.xs, *red = c.red, *s = c.s;
+  auto gscratch = [&](int slot) { return a.mw_scratch + (size_t)slot * 256 * 16; };
+  const int n = a.n, m = a.m, N = a.N;
+  const size_t nB = (size_t)n * BT, mB = (size_t)m * BT;
+  reduced_solve_refine<BT, NT>(c, pa.refine_iter, [&](int e) {
+    double v = 0.0;
+    if (on) {
+      const int i = e / BT;
+      if (i < n) v = -p.q[e];
+      else if (const signed char ac = c.act[i - n]) v = ac < 0 ? p.l[e - (int)nB] : p.u[e - (int)nB];
+    }
+    return v;
+  });
   // z = A x
   for (int e = tid; e < N * BT; e += nthr) xs[e] = e < (int)nB ? s[e] : 0.0;
-  spmv();
+  c.spmv();
   // y from y_red, normal-cone projection: t = z + y, z = clip(t, l, u), y = t - z   (z -> out2)
   for (int e = tid; e < (int)mB; e += nthr) {
     const double t = p.out1[2 * nB + e] + s[nB + e];
     const double zn = fmin(fmax(t, p.l[e]), p.u[e]);
     p.out2[e] = zn; s[nB + e] = t - zn;
   }
-  sync();
+  c.sync();
   // residuals and objective at the polished point (check_kernel's arithmetic)
   for (int e = tid; e < N * BT; e += nthr) xs[e] = s[e];
-  spmv();
+  c.spmv();
   const double cinv = p.dscal[DS_CINV * BT + b];
   const bool unscale = a.scaling && !a.scaled_termination;
   double mx[4] = {0.0, 0.0, 0.0, 0.0};
@@ -1885,7 +1908,7 @@ __global__ __launch_bounds__(NT) void polish_kernel(KernelArgs a, PolishArgs pa)
   if (a.scaling) obj *= cinv;
   const double pri0 = p.dscal[DS_PRI_RES * BT + b], dua0 = p.dscal[DS_DUA_RES * BT + b];
   const bool acc = on && ((pri < pri0 && dua < dua0) || (pri < pri0 && dua0 < 1e-10) || (dua < dua0 && pri0 < 1e-10));
-  sync();
+  c.sync();
   if (acc) {
     for (int e = tid; e < (int)nB; e += nthr) {
       const double xv = s[e];
@@ -1905,9 +1928,8 @@ __global__ __launch_bounds__(NT) void polish_kernel(KernelArgs a, PolishArgs pa)
 }
 
 // Adjoint derivative of the active-set solution map (OSQP 1.0 osqp_adjoint_derivative_compute; solver.hip "adjoint", DESIGN.md
-// section 8).  After the polish factor of the marked QPs (pa.stat[slot] = 1), as polish_kernel: same forms, threads, barriers
-// and LDS; the solve-and-refine loop is polish_kernel's with another right-hand side (a copy on purpose: polish_kernel's
-// results are pinned bit for bit).  With T = diag(c D, E_a) the scaled reduced matrix is K~ = (1/c) T K T, so
+// section 8): the reduced solve of the marked QPs with the loss gradient as right-hand side, so the forms, threads, barriers
+// and LDS are polish_kernel's.  With T = diag(c D, E_a) the scaled reduced matrix is K~ = (1/c) T K T, so
 //   g~ = [c D g_x; E g_y (active rows)],   K~ r~ = g~,   r_x = D r~_x,   r_y = E r~_y / c (0 on inactive rows)
 // and, with the caller-space solution (x, y) = (x_out, y_out):
 //   dq = -r_x,  dl_i = r_y,i (lower-active),  du_i = r_y,i (upper-active),  dA_k = -(y_i r_x,j + r_y,i x_j) at (i, j),
@@ -1919,44 +1941,16 @@ __global__ __launch_bounds__(NT) void polish_kernel(KernelArgs a, PolishArgs pa)
 template <int BT, int NT, bool GX, bool WIDE = false>
 __global__ __launch_bounds__(NT) void adjoint_kernel(KernelArgs a, PolishArgs pa, AdjointArgs ga) {
   extern __shared__ double smem[];
-  bool df = false, dfm = false;
-  if constexpr (GX && BT == 1 && WIDE) { df = a.df != 0; dfm = df && a.mw_groups > 1; }
-  const Mw mw{a.mw_bar, dfm ? (unsigned)a.mw_groups : 1u};
-  const int tile = dfm ? 0 : blockIdx.x;
-  const int tid = dfm ? blockIdx.x * blockDim.x + threadIdx.x : threadIdx.x, nthr = dfm ? blockDim.x * mw.G : blockDim.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nthr >> 6;
-  const int b = tid % BT;
-  auto sync = [&]() { if constexpr (GX && BT == 1 && WIDE) wg_or_grid_barrier(mw); else __syncthreads(); };
+  const ReducedTile<BT, GX, WIDE> c(a, pa, smem);
+  if (!c.p.act) return;
+  const int tile = c.tile, tid = c.tid, nthr = c.nthr, b = c.b, slot = c.slot;
+  const bool on = c.on;
+  const TilePtrs<BT> &p = c.p;
+  const signed char *act = c.act;
+  double *s = c.s;
   const int n = a.n, m = a.m, N = a.N;
-  const uint32_t sh = a.df_shadow;
-  double *red;
-  double *xs = solve_vector<BT, GX>(a, smem, tile, red);
-  TilePtrs<BT> p = tile_ptrs<BT>(a, tile);
-  p.act = 0;
-#pragma unroll
-  for (int bb = 0; bb < BT; bb++) {       // QPs not marked stream nothing (same for every thread: wave-uniform)
-    const int sl = tile * BT + bb;
-    if (sl < a.B && pa.stat[sl] == 1) { p.act |= 1 << bb; continue; }
-    p.vfwd.vals[bb] = make_rsrc(nullptr, 0u); p.vbwd.vals[bb] = make_rsrc(nullptr, 0u);
-    p.vchk.vals[bb] = make_rsrc(nullptr, 0u); p.vdt[bb] = make_rsrc(nullptr, 0u);
-  }
-  if (!p.act) return;
-  const int slot = tile * BT + b;
-  const bool on = (p.act >> b) & 1;
-  const size_t so = on ? slot : 0;             // (a QP that is not marked reads the rows of QP 0: in bounds, unused)
-  const signed char *act = pa.act + so * m;
-  double *s = pa.sol + (size_t)tile * N * BT;
-  auto put_rhs = [&](int e, double v) {        // natural entry e / BT of the right-hand side -> the solve vector
-    const uint32_t pe = a.pinv[e / BT];
-    if (df) { st_sc1(xs + pe, v); df_arm_fwd(xs, pe, a.rflag[pe], a.xloc[pe], sh); }
-    else xs[(size_t)pe * BT + b] = v;
-  };
-  auto get_sol = [&](int e) -> double {
-    const uint32_t pe = a.pinv[e / BT];
-    return df ? ld_sc1(xs + df_bloc(pe, a.rflag[pe], sh)) : xs[(size_t)pe * BT + b];
-  };
-  const size_t nB = (size_t)n * BT;
-  {    // g~ once, into out2 (scratch of the polish as well): the loop below then reads one array, as polish_kernel reads q, l, u
+  const size_t nB = (size_t)n * BT, so = on ? slot : 0;
+  {    // g~ once, into out2 (scratch of the polish as well): the loop then reads one array, as polish_kernel's reads q, l, u
     const double cs = a.scaling ? p.dscal[DS_C * BT + b] : 1.0;
     for (int e = tid; e < N * BT; e += nthr) {
       double v = 0.0;
@@ -1973,33 +1967,7 @@ __global__ __launch_bounds__(NT) void adjoint_kernel(KernelArgs a, PolishArgs pa
       p.out2[e] = v;
     }
   }
-  for (int r = 0; r <= pa.refine_iter; r++) {
-    if (r > 0) {
-      for (int e = tid; e < N * BT; e += nthr) xs[e] = s[e];
-      sync();
-      run_spmv<BT, MI_PFV, WIDE>(a.chk, p.vchk, xs, p.out1, wave, lane, 0, 3, nw);
-      sync();
-    }
-    for (int e = tid; e < N * BT; e += nthr) {
-      double v = p.out2[e];
-      if (on && r > 0) {
-        const int i = e / BT;
-        if (i < n) v -= p.out1[e] + p.out1[nB + e];
-        else if (act[i - n]) v -= p.out1[2 * nB + (e - (int)nB)];
-      }
-      put_rhs(e, v);
-    }
-    if (df && tid == 0) st_sc1(xs + 2 * (size_t)sh, 0.0);
-    sync();
-    kkt_solve_lds<BT, MI_PFV_NT(NT, GX), GX, WIDE>(a, p, xs, tid, nthr, wave, nw, lane, mw);
-    for (int e = tid; e < N * BT; e += nthr) {
-      const int i = e / BT;
-      double d = get_sol(e);
-      if (i >= n && !act[i - n]) d = 0.0;
-      s[e] = r ? s[e] + d : d;
-    }
-    sync();
-  }
+  reduced_solve_refine<BT, NT>(c, pa.refine_iter, [&](int e) { return p.out2[e]; });
   // r = T r~ / c in place of the refinement iterate; dq, dl, du
   const double cinv = a.scaling ? p.dscal[DS_CINV * BT + b] : 1.0;
   for (int e = tid; e < N * BT; e += nthr) {
@@ -2016,7 +1984,7 @@ __global__ __launch_bounds__(NT) void adjoint_kernel(KernelArgs a, PolishArgs pa
       if (ga.du) ga.du[(size_t)slot * m + (i - n)] = c > 0 ? v : 0.0;
     }
   }
-  sync();
+  c.sync();
   // the stored values of triu(P) and A, natural CSC order: every thread of the tile serves every marked QP of it
 #pragma unroll
   for (int bb = 0; bb < BT; bb++) {
@@ -3998,11 +3966,29 @@ hipError_t launch_advance(const KernelArgs &a, int BT, int tiles, int threads, s
   return go(&advance_kernel<4, 512>);
 }
 
+// The grid form of a launch (dataflow handle): the caller asks for the one tile of its one QP, the wide global-vector kernel
+// runs on a.mw_groups workgroups that meet at the barrier words (and reduce through the scratch, where the kernel reduces).
+// Kernels with a one-workgroup dataflow path of their own take the grid form from two groups on (from_two).
+// false: the arguments do not fit the form.
+static bool grid_form(const KernelArgs &a, int BT, int &tiles, bool from_two, bool need_scratch) {
+  if (!a.df || (from_two && a.mw_groups <= 1)) return true;
+  if (tiles != 1 || BT != 1 || !a.xs_global || !a.wide || !a.mw_bar || a.mw_groups < 1 || (need_scratch && !a.mw_scratch)) return false;
+  tiles = a.mw_groups;
+  return true;
+}
+// the grid (from two groups on) spins on its barriers: every workgroup must be resident at once
+static bool grid_resident(const void *kern, const KernelArgs &a, int threads, size_t lds, int n_cus) {
+  if (!a.df || a.mw_groups <= 1) return true;
+  int nb = 0;
+  return ensure_dynamic_lds(kern, lds) == hipSuccess && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds) == hipSuccess &&
+         nb * n_cus >= a.mw_groups;
+}
+
 int rf_head_steps() { return MI_RF_R + MI_RF_RL; }
 int rf_lds_steps() { return MI_RF_RL; }
 hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st) {
   if (getenv("MI_OSQP_DEBUG_HIP")) fprintf(stderr, "[mi_osqp] launch_iterate: df %d wide %d xs_global %p BT %d tiles %d threads %d lds %zu groups %d bar %p\n", a.df, a.wide, (void *)a.xs_global, BT, tiles, threads, lds, a.mw_groups, (void *)a.mw_bar);
-  if (a.df) { if (tiles != 1 || BT != 1 || !a.xs_global || !a.wide || !a.mw_bar || a.mw_groups < 1) return hipErrorInvalidValue; tiles = a.mw_groups; }
+  if (!grid_form(a, BT, tiles, false, false)) return hipErrorInvalidValue;
 #ifdef MI_OSQP_DEBUG_BUILD
   if (a.df && debug_drop_group("iterate") && tiles > 1) tiles--;       // fault injection: a workgroup of the grid never shows up
 #endif
@@ -4024,7 +4010,7 @@ hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, s
   MI_DISPATCH(iterate_kernel, a);
 }
 hipError_t launch_check(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st) {
-  if (a.df && a.mw_groups > 1) { if (tiles != 1 || BT != 1 || !a.xs_global || !a.wide || !a.mw_bar || !a.mw_scratch) return hipErrorInvalidValue; tiles = a.mw_groups; }
+  if (!grid_form(a, BT, tiles, true, true)) return hipErrorInvalidValue;
 #ifdef MI_OSQP_DEBUG_BUILD
   if (a.df && a.mw_groups > 1 && debug_drop_group("check") && tiles > 1) tiles--;
 #endif
@@ -4036,7 +4022,7 @@ hipError_t launch_spmv(const KernelArgs &a, int BT, int tiles, int threads, size
 }
 hipError_t launch_kkt_solve(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st,
                             const double *rhs, double *sol) {
-  if (a.df) { if (tiles != 1 || BT != 1 || !a.xs_global || !a.wide || !a.mw_bar || a.mw_groups < 1) return hipErrorInvalidValue; tiles = a.mw_groups; }
+  if (!grid_form(a, BT, tiles, false, false)) return hipErrorInvalidValue;
 #ifdef MI_OSQP_DEBUG_BUILD
   if (a.df && debug_drop_group("kkt") && tiles > 1) tiles--;
 #endif
@@ -4058,27 +4044,13 @@ hipError_t launch_polish_publish(const KernelArgs &a, const PolishArgs &p, const
   return hipGetLastError();
 }
 hipError_t launch_polish(const KernelArgs &a, const PolishArgs &p, int BT, int tiles, int threads, size_t lds, int n_cus, hipStream_t st) {
-  if (a.df && a.mw_groups > 1) {
-    // the grid spins on its barriers: every workgroup must be resident at once
-    if (tiles != 1 || BT != 1 || !a.xs_global || !a.wide || !a.mw_bar || !a.mw_scratch) return hipErrorInvalidValue;
-    int nb = 0;
-    const void *k = reinterpret_cast<const void *>(&polish_kernel<1, 512, true, true>);
-    if (ensure_dynamic_lds(k, lds) != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds) != hipSuccess ||
-        nb * n_cus < a.mw_groups) return hipErrorInvalidValue;
-    tiles = a.mw_groups;
-  }
+  if (!grid_form(a, BT, tiles, true, true) ||
+      !grid_resident(reinterpret_cast<const void *>(&polish_kernel<1, 512, true, true>), a, threads, lds, n_cus)) return hipErrorInvalidValue;
   MI_DISPATCH(polish_kernel, a, p);
 }
 hipError_t launch_adjoint(const KernelArgs &a, const PolishArgs &p, const AdjointArgs &g, int BT, int tiles, int threads, size_t lds, int n_cus, hipStream_t st) {
-  if (a.df && a.mw_groups > 1) {
-    // the grid spins on its barriers: every workgroup must be resident at once
-    if (tiles != 1 || BT != 1 || !a.xs_global || !a.wide || !a.mw_bar) return hipErrorInvalidValue;
-    int nb = 0;
-    const void *k = reinterpret_cast<const void *>(&adjoint_kernel<1, 512, true, true>);
-    if (ensure_dynamic_lds(k, lds) != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, threads, lds) != hipSuccess ||
-        nb * n_cus < a.mw_groups) return hipErrorInvalidValue;
-    tiles = a.mw_groups;
-  }
+  if (!grid_form(a, BT, tiles, true, false) ||
+      !grid_resident(reinterpret_cast<const void *>(&adjoint_kernel<1, 512, true, true>), a, threads, lds, n_cus)) return hipErrorInvalidValue;
   MI_DISPATCH(adjoint_kernel, a, p, g);
 }
 hipError_t launch_adjoint_finish(const int *stat, const AdjointArgs &g, int32_t *status, int B, int n, int m, hipStream_t st) {

@@ -781,6 +781,19 @@ static int mw_barrier_ok(mi_osqp_batch *h) {
   if (w[2]) { g_last_error = "dataflow solve: a wait for a vector entry or a grid barrier timed out"; return MI_OSQP_ERR_DEVICE; }
   return MI_OSQP_OK;
 }
+// A launch that may spin on the grid of a dataflow handle, from the launch to its completion under the device's spin mutex:
+// the barrier words are zeroed, `launch` enqueues on `st` (and returns a status), the stream is drained, the barrier checked.
+template <class Launch>
+static int run_spinning(mi_osqp_batch *h, hipStream_t st, Launch launch) {
+  int rc;
+  {
+    std::unique_lock<std::mutex> spin_lock(spin_mutex(h->device), std::defer_lock);
+    if (h->mw_groups > 0) { spin_lock.lock(); HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), st)); }
+    if ((rc = launch())) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  return mw_barrier_ok(h);
+}
 
 // The launch shape of a handle (threads per workgroup, QPs per tile, where the solve vector lives, the grid of a large single
 // QP): what the pattern analysis is built for.  Shared by setup and by mi_osqp_prefetch_analysis.
@@ -1199,6 +1212,27 @@ static TailArgs make_tail_args(mi_osqp_batch *h, int kbt, const int *work) {
   return da;
 }
 
+// The polish factor instead of the ADMM factor (FactorArgs::pmask; section "polish"): from the active sets of `pol`, regularised
+// by delta, into the polish buffers; a wrong inertia goes to pol->stat.  da = the tail arguments of the same launch chain.
+static void to_polish_factor(mi_osqp_batch *h, const PolishArgs &pol, FactorArgs &fa, TailArgs &da) {
+  fa.pmask = pol.act; fa.arow = h->rz_arow.p; fa.pstat = pol.stat; fa.pdelta = h->st.delta; fa.sigma = h->st.delta;
+  fa.fwd_val = h->pol_fwd.p; fa.bwd_val = h->pol_bwd.p; fa.dinv = h->pol_dinv.p; fa.use_work = nullptr;
+  da.dt_val = h->pol_dt.p; da.dinv = h->pol_dinv.p; da.pstat = pol.stat;
+}
+// the solve arguments `a` with the polish factor's streams in place of the ADMM factor's
+static KernelArgs polish_stream_args(mi_osqp_batch *h, KernelArgs a) {
+  a.fwd_val = h->pol_fwd.p; a.bwd_val = h->pol_bwd.p; a.dinv = h->pol_dinv.p; a.dt_val = h->pol_dt.p; a.use_work = nullptr;
+  return a;
+}
+// the QPs whose status word in h_iscal (the host copy of the flags) is kOptimal
+static std::vector<int> koptimal_slots(const mi_osqp_batch *h) {
+  const int BT = h->BT;
+  std::vector<int> work;
+  for (int q = 0; q < h->B; q++)
+    if (h->h_iscal[(size_t)(q / BT) * IS_COUNT * BT + IS_STATUS * BT + q % BT] == 1) work.push_back(q);
+  return work;
+}
+
 // Row E13 on the device for a list of slots (tile * BT + b): rho vector from the current bounds and rho, KKT
 // assembly, block LDL', scatter into the solve streams.  The work list packs the slots kbt per workgroup.
 // Slots whose new factor has the wrong inertia are appended to *bad (the caller isolates them).
@@ -1210,10 +1244,6 @@ static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::v
   const int BT = h->BT;
   int rc;
   FactorArgs fa = make_factor_args(h, 0);
-  if (pol) {
-    fa.pmask = pol->act; fa.arow = h->rz_arow.p; fa.pstat = pol->stat; fa.pdelta = h->st.delta; fa.sigma = h->st.delta;
-    fa.fwd_val = h->pol_fwd.p; fa.bwd_val = h->pol_bwd.p; fa.dinv = h->pol_dinv.p; fa.use_work = nullptr;
-  }
   // QPs per workgroup of this refactorisation: one while every QP can have a CU of its own (a lone tile is
   // latency-bound: 3.3 ms with one QP, 4.6 ms with two), the solve tiling otherwise (measured: 605 QPs take
   // 10.9 ms whether packed 1, 2 or 4 per workgroup - the memory system, not the tiling, is the limit there)
@@ -1224,6 +1254,8 @@ static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::v
   if (h->work.n < work.size() && (rc = h->work.alloc((size_t)h->ntiles * BT + 4))) return rc;
   HIPCHK(hipMemcpyAsync(h->work.p, work.data(), work.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   fa.work = h->work.p;
+  TailArgs da = make_tail_args(h, kbt, h->work.p);
+  if (pol) to_polish_factor(h, *pol, fa, da);
   // Short work lists (the rho updates of the last few QPs of a batch, a strong-scaling shard, a handle with one QP): the
   // block tasks of a QP are shared by several workgroups with barriers of the group between the phases of a level
   // (3 x levels x ~6 us): one QP of config 5 (ms): 1: 275, 8: 45, 16: 28, 32: 19, 64: 15, 128: 14
@@ -1245,8 +1277,6 @@ static int device_refactor_slots(mi_osqp_batch *h, std::vector<int> work, std::v
   HIPCHK(launch_factor(fa, kbt, wtiles, h->tune.factor_threads, h->stream));
   HIPCHK(hipEventRecord(h->evf1, h->stream));
   if ((*h->anp).dt.k) {      // the tail blocks now hold the Schur complement: invert it into the stream of the symmetric product
-    TailArgs da = make_tail_args(h, kbt, h->work.p);
-    if (pol) { da.dt_val = h->pol_dt.p; da.dinv = h->pol_dinv.p; da.pstat = pol->stat; }
     unsigned long long *d_trace = nullptr;
     const bool tracing = getenv("MI_OSQP_TAIL_TRACE") != nullptr;          // timing stamps only; results are unaffected
     if (tracing) { HIPCHK(hipMalloc((void **)&d_trace, (size_t)wtiles * kbt * 8 * sizeof(unsigned long long))); HIPCHK(hipMemsetAsync(d_trace, 0, (size_t)wtiles * kbt * 64, h->stream)); }
@@ -1339,24 +1369,18 @@ static int polish_impl(mi_osqp_batch *h, const KernelArgs &a) {
   h->pol_count = h->pol_accepted = 0; h->pol_seconds = 0.0;
   h->pol_status.assign((size_t)h->B, 0);
   if ((rc = ensure_polish_buffers(h))) return rc;
-  std::vector<int> work;                // the QPs that ended kOptimal (h_iscal: copied at the end of the solve)
-  for (int q = 0; q < h->B; q++)
-    if (h->h_iscal[(size_t)(q / BT) * IS_COUNT * BT + IS_STATUS * BT + q % BT] == 1) work.push_back(q);
+  std::vector<int> work = koptimal_slots(h);      // (h_iscal: copied at the end of the solve)
   PolishArgs pa{h->pol_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter};
   HIPCHK(hipEventRecord(h->evp0, h->stream));
   HIPCHK(launch_polish_active(a, pa, BT, h->stream));
   const int n_pol = (int)work.size();
   if (n_pol) {
     if ((rc = device_refactor_slots(h, std::move(work), nullptr, &pa))) return rc;
-    KernelArgs ap = a;
-    ap.fwd_val = h->pol_fwd.p; ap.bwd_val = h->pol_bwd.p; ap.dinv = h->pol_dinv.p; ap.dt_val = h->pol_dt.p; ap.use_work = nullptr;
-    std::unique_lock<std::mutex> spin_lock(spin_mutex(h->device), std::defer_lock);
-    if (h->mw_groups > 0) { spin_lock.lock(); HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), h->stream)); }
-    HIPCHK(launch_polish(ap, pa, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds, h->n_cus, h->stream));
-    HIPCHK(hipEventRecord(h->evp1, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (spin_lock.owns_lock()) spin_lock.unlock();
-    if ((rc = mw_barrier_ok(h))) return rc;
+    if ((rc = run_spinning(h, h->stream, [&]() -> int {
+          HIPCHK(launch_polish(polish_stream_args(h, a), pa, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds, h->n_cus, h->stream));
+          HIPCHK(hipEventRecord(h->evp1, h->stream));
+          return MI_OSQP_OK;
+        }))) return rc;
   } else {
     HIPCHK(hipEventRecord(h->evp1, h->stream));
   }
@@ -1391,22 +1415,17 @@ static int adjoint_impl(mi_osqp_batch *h, const AdjointArgs &ga, int32_t *d_stat
   if (h->solved_once) {                 // (before that the status words are not initialised; the continuous mode sets it too)
     HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)ntl * IS_COUNT * BT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (int q = 0; q < h->B; q++)
-      if (h->h_iscal[(size_t)(q / BT) * IS_COUNT * BT + IS_STATUS * BT + q % BT] == 1) work.push_back(q);
+    work = koptimal_slots(h);
   }
   if (!work.empty()) {
     const KernelArgs a = make_args(h);
     PolishArgs pa{h->adj_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter};
     HIPCHK(launch_polish_active(a, pa, BT, h->stream));
     if ((rc = device_refactor_slots(h, std::move(work), nullptr, &pa))) return rc;
-    KernelArgs ap = a;
-    ap.fwd_val = h->pol_fwd.p; ap.bwd_val = h->pol_bwd.p; ap.dinv = h->pol_dinv.p; ap.dt_val = h->pol_dt.p; ap.use_work = nullptr;
-    std::unique_lock<std::mutex> spin_lock(spin_mutex(h->device), std::defer_lock);
-    if (h->mw_groups > 0) { spin_lock.lock(); HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), h->stream)); }
-    HIPCHK(launch_adjoint(ap, pa, ga, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds, h->n_cus, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (spin_lock.owns_lock()) spin_lock.unlock();
-    if ((rc = mw_barrier_ok(h))) return rc;
+    if ((rc = run_spinning(h, h->stream, [&]() -> int {
+          HIPCHK(launch_adjoint(polish_stream_args(h, a), pa, ga, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds, h->n_cus, h->stream));
+          return MI_OSQP_OK;
+        }))) return rc;
   }
   HIPCHK(launch_adjoint_finish(h->adj_stat.p, ga, d_status, h->B, an.n, an.m, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -2504,14 +2523,10 @@ int mi_osqp_batch_kkt_solve(mi_osqp_batch *h, const double *d_rhs, double *d_sol
   DevGuard guard(h->device);
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   KernelArgs a = make_args(h);
-  {
-    std::unique_lock<std::mutex> spin_lock(spin_mutex(h->device), std::defer_lock);
-    if (h->mw_groups > 0) spin_lock.lock();
-    if (h->mw_groups > 0) HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), s));
+  return run_spinning(h, s, [&]() -> int {
     HIPCHK(launch_kkt_solve(a, h->BT, h->ntiles, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds, s, d_rhs, d_sol));
-    HIPCHK(hipStreamSynchronize(s));
-  }
-  return mw_barrier_ok(h);
+    return MI_OSQP_OK;
+  });
 }
 
 int mi_osqp_debug_trace_kkt_solve(mi_osqp_batch *h, int32_t which, const double *d_rhs, double *d_sol, uint32_t *out,
@@ -2762,25 +2777,10 @@ static int enqueue_refactor_list(mi_osqp_batch *h, const int *d_work, int count,
   hipStream_t st = h->stream;
   FactorArgs fa = make_factor_args(h, 0);
   fa.work = d_work; fa.mw_groups = 0;
-  if (pol) {
-    fa.pmask = pol->act; fa.arow = h->rz_arow.p; fa.pstat = pol->stat; fa.pdelta = h->st.delta; fa.sigma = h->st.delta;
-    fa.fwd_val = h->pol_fwd.p; fa.bwd_val = h->pol_bwd.p; fa.dinv = h->pol_dinv.p; fa.use_work = nullptr;
-  }
+  TailArgs da = make_tail_args(h, 1, d_work);
+  if (pol) to_polish_factor(h, *pol, fa, da);
   HIPCHK(launch_factor(fa, 1, count, h->tune.factor_threads, st));
-  if (an.dt.k) {
-    const DenseTail &dt = an.dt;
-    TailArgs da{};
-    da.n = an.n; da.N = an.N; da.s = dt.s; da.k = dt.k; da.kbt = 1; da.home_bt = h->BT;
-    da.storage = an.bf.storage; da.n_slots = dt.n_steps * 64u; da.n_lt = dt.n_lt; da.n_ltcol = dt.n_ltcol; da.n_quads = (uint32_t)(dt.asm_q64.size() / 64);
-    da.nh = h->dt_nh; da.cs_doubles = h->dt_cs_doubles; da.work = d_work;
-    da.lt_pos = h->dt_lt_pos.p; da.ltcol_col = h->dt_ltcol_col.p; da.tile_tab = h->dt_tile_tab.p; da.wave_tiles = h->dt_wave_tiles.p;
-    da.dt_task = h->dt_task.p; da.dt_task_step = h->dt_task_step.p; da.n_tasks = (uint32_t)(dt.task.size() / 4);
-    da.asm_q64 = h->dt_asm_q64.p; da.diag_tile = h->dt_diag_tile.p; da.src_tile = h->dt_src_tile.p;
-    da.Lblk = fa.Lblk; da.Dl = fa.Dl; da.Sd = h->dt_Sd.p; da.dt_val = h->dt_val.p; da.dinv = h->dinv.p; da.npos = h->npos.p; da.iscal = h->iscal.p;
-    da.trace = nullptr;
-    if (pol) { da.dt_val = h->pol_dt.p; da.dinv = h->pol_dinv.p; da.pstat = pol->stat; }
-    HIPCHK(launch_tail(da, count, h->dt_lds_asm, h->dt_lds, st));
-  }
+  if (an.dt.k) HIPCHK(launch_tail(da, count, h->dt_lds_asm, h->dt_lds, st));
   return MI_OSQP_OK;
 }
 
@@ -3000,9 +3000,7 @@ int mi_osqp_batch_polish_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *id
   PolishArgs pa{h->pol_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter};
   HIPCHK(launch_polish_active_list(a, pa, d_ids, nq, BT, h->stream));
   if ((rc = enqueue_refactor_list(h, d_ids, nq, &pa))) return rc;
-  KernelArgs ap = a;
-  ap.fwd_val = h->pol_fwd.p; ap.bwd_val = h->pol_bwd.p; ap.dinv = h->pol_dinv.p; ap.dt_val = h->pol_dt.p; ap.use_work = nullptr;
-  HIPCHK(launch_polish(ap, pa, BT, h->ntiles, h->threads, h->lds, h->n_cus, h->stream));
+  HIPCHK(launch_polish(polish_stream_args(h, a), pa, BT, h->ntiles, h->threads, h->lds, h->n_cus, h->stream));
   HIPCHK(launch_polish_publish(a, pa, d_ids, nq, c.h_pstat, BT, h->stream));
   for (int64_t j = 0; j < n_ids; j++) {
     const size_t q = (size_t)ids[j];
