@@ -469,6 +469,26 @@ typedef struct { int32_t n_joints; int32_t reserved; double a[8], d[8], alpha[8]
 int mi_gomp_scene_create_chain(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints,
                                const mi_gomp_chain *chain, int64_t n_balls, const mi_gomp_ball *balls,
                                int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi);
+/* A capsule obstacle: the segment a .. b swept by a sphere of radius `radius`; a == b is a sphere (host twin:
+ * CapsuleObstacle in include/mi_osqp/gomp.hpp).  For a ball with centre p = fk(q_w), radius r and position Jacobian J:
+ * c = the point of the segment closest to p (c = a + t (b - a), t = min(1, max(0, (p - a).(b - a) / |b - a|^2)); c = a for
+ * a == b), dist = |p - c|, clearance s = dist - (radius + r), normal nrm = (p - c) / dist, or (0, 0, 1) when dist <= 1e-12.
+ * The row of (ball, waypoint, capsule) holds nrm' J in the columns of q_w, whether it is active or not.  It is active when
+ * s < margin: l = (radius + r) - dist + (nrm' J) q_w, u = +1e30 - the linearisation of s(q) >= 0 around q_w, the ball's radius
+ * included; otherwise l = -1e30, u = +1e30.  A trajectory is accepted only if s >= -1e-3 for every ball, waypoint and
+ * capsule.  `margin` is the caller's tool against passing through an obstacle between two waypoints. */
+typedef struct { double a[3], b[3]; double radius; double margin; } mi_gomp_capsule;
+/* mi_gomp_scene_create_chain with capsules besides the lines.  Inside the block of a (ball, waypoint) pair the rows are: the
+ * three box rows of a gripper ball, the lines, then the capsules in the order given, so the constraint matrix must hold
+ * waypoints * sum over the balls of ((gripper ? 3 : 0) + n_lines + n_capsules) rows from the first 3-D row on.
+ * chain == NULL: as mi_gomp_scene_create; n_capsules == 0: exactly mi_gomp_scene_create_chain.  Refused on the host, before any
+ * device call, with *out = NULL, the handle usable and the reason in mi_osqp_last_error(): n_capsules > 0 without capsules
+ * (MI_OSQP_ERR_NULL); n_capsules < 0, a capsule field that is not finite, a negative radius or margin, a constraint matrix
+ * that does not hold the rows (MI_OSQP_ERR_INVALID_DATA). */
+int mi_gomp_scene_create_world(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints,
+                               const mi_gomp_chain *chain, int64_t n_balls, const mi_gomp_ball *balls,
+                               int64_t n_lines, const mi_gomp_line *lines, int64_t n_capsules, const mi_gomp_capsule *capsules,
+                               const double *con_lo, const double *con_hi);
 void mi_gomp_scene_free(mi_gomp_scene *sc);          /* before mi_osqp_batch_free of its handle; one scene per handle */
 /* While a scene exists, mi_osqp_batch_reinit_some / _update_A_bounds_some of its handle also keep the QPs' raw constraint
  * data (as ConstraintBuilder::build() produced it) in the scene, so nothing extra is needed when a trajectory enters the

@@ -6,6 +6,7 @@
 //   RobotBall, linspace,
 //   triDiagonalMatrix        [REF] src/utils.h:33-42,50-64,72-96
 //   ConstraintBuilder<N>     [REF] src/constraints/constraint-builder.h:18-283
+//   CapsuleObstacle          not in the reference: a segment swept by a sphere (posts, pipes, other robots' links; a == b: a sphere)
 //   GOMPSolver<N>            [REF] src/gomp-solver.h:13-201
 //
 // Same names, argument meaning, row layout and control flow as the reference (the known-answer
@@ -174,26 +175,60 @@ class HorizontalLine {
   bool below_;
 };
 
+// ------------------------------------------------------------- capsule obstacles (not in the reference)
+// The segment a .. b swept by a sphere of radius `radius` (mi_gomp_capsule is its device twin, include/mi_osqp.h has the
+// formulas).  A ball with centre P keeps the clearance |P - c| - (radius + ball.radius) >= 0 from it, c the point of the
+// segment closest to P; its constraint row is the linearisation of that clearance in the joints and becomes active
+// `margin` away from the surface.
+class CapsuleObstacle {
+ public:
+  CapsuleObstacle(const Point &a_, const Point &b_, double radius_, double margin_ = 0.0) : a(a_), b(b_), radius(radius_), margin(margin_) {
+    assert(radius >= 0.0 && margin >= 0.0);
+  }
+  static CapsuleObstacle sphere(const Point &centre, double radius, double margin = 0.0) { return {centre, centre, radius, margin}; }
+  Point a, b;
+  double radius, margin;
+  // c = a + t (b - a), t = (P - a).(b - a) / |b - a|^2 clamped to [0, 1]; a for a == b
+  Point closestPoint(const Point &P) const {
+    const Point e{b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+    const double ee = e[0] * e[0] + e[1] * e[1] + e[2] * e[2];
+    if (ee == 0.0) return a;
+    const double t = std::fmin(1.0, std::fmax(0.0, ((P[0] - a[0]) * e[0] + (P[1] - a[1]) * e[1] + (P[2] - a[2]) * e[2]) / ee));
+    return {a[0] + t * e[0], a[1] + t * e[1], a[2] + t * e[2]};
+  }
+  // P - c and its length
+  Point offset(const Point &P) const { const Point c = closestPoint(P); return {P[0] - c[0], P[1] - c[1], P[2] - c[2]}; }
+  double distance(const Point &P) const { const Point v = offset(P); return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
+  double clearance(const Point &P, const RobotBall &ball) const { return distance(P) - (radius + ball.radius); }
+  bool operator==(const CapsuleObstacle &o) const { return a == o.a && b == o.b && radius == o.radius && margin == o.margin; }
+};
+// the capsule part of isSolutionOK, for one ball at one waypoint (shared by the three drivers)
+inline bool capsulesClear(const std::vector<CapsuleObstacle> &capsules, const Point &P, const RobotBall &ball) {
+  bool res = true;
+  for (const CapsuleObstacle &cap : capsules) if (!(cap.clearance(P, ball) >= -ERROR)) res = false;
+  return res;
+}
+
 // ------------------------------------------------------------- constraint-builder.h
 // Rows: (W-1)*D velocity<->position links, then per variable boxes (positions W*D, velocities
-// (W-1)*D, accelerations (W-2)*D), then D*W*(3 + |obstacles|*|balls|) rows for the linearised
+// (W-1)*D, accelerations (W-2)*D), then D*W*(3 + (|obstacles| + |capsules|)*|balls|) rows for the linearised
 // end-effector / obstacle constraints (allocated even when unused: bounds +-INF).
 template <size_t N_DIM>
 class ConstraintBuilder {
   using OptPair = std::pair<std::optional<double>, std::optional<double>>;
 
  public:
-  ConstraintBuilder(size_t waypoints, std::vector<RobotBall> m, std::vector<HorizontalLine> obstacles)
-      : W_(waypoints), balls_(std::move(m)), lines_(std::move(obstacles)) {
-    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size())));
-    lo_.reserve(N_DIM * W_ * (7 + lines_.size() * balls_.size())); up_.reserve(lo_.capacity());
+  ConstraintBuilder(size_t waypoints, std::vector<RobotBall> m, std::vector<HorizontalLine> obstacles, std::vector<CapsuleObstacle> capsules = {})
+      : W_(waypoints), balls_(std::move(m)), lines_(std::move(obstacles)), capsules_(std::move(capsules)) {
+    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size())));
+    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size()) * balls_.size())); up_.reserve(lo_.capacity());
     for (size_t t = 0; t + 1 < W_; ++t)                      // v_t - q_{t+1} + q_t = 0
       for (size_t j = 0; j < N_DIM; ++j) {
         lo_.push_back(-INF); up_.push_back(INF);
         put(lo_.size() - 1, {{nthVelocity(t) + j, 1.0}, {nthPos(t + 1) + j, -1.0}, {nthPos(t) + j, 1.0}}, {0.0, 0.0});
       }
     user_off_ = lo_.size();
-    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + lines_.size() * balls_.size()));
+    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size()) * balls_.size()));
     lo_.resize(user_off_ + extra, -INF);
     up_.resize(user_off_ + extra, INF);
   }
@@ -245,6 +280,7 @@ class ConstraintBuilder {
             axisRow(row++, ball, Z, J, w, -INF, INF);          // dummy: keeps the pattern constant
           }
         }
+        for (const CapsuleObstacle &cap : capsules_) capsuleRow(row++, ball, cap, p, J, q, w);
       }
     }
     return *this;
@@ -258,7 +294,7 @@ class ConstraintBuilder {
     for (const RobotBall &ball : balls_)
       for (size_t w = 0; w < W_; ++w) {
         if (ball.is_gripper) for (Axis axis : XYZ_AXES) axisRow(row++, ball, axis, J, w, -INF, INF);
-        for (size_t k = 0; k < lines_.size(); ++k) axisRow(row++, ball, Z, J, w, -INF, INF);
+        for (size_t k = 0; k < lines_.size() + capsules_.size(); ++k) axisRow(row++, ball, Z, J, w, -INF, INF);
       }
     return *this;
   }
@@ -285,6 +321,7 @@ class ConstraintBuilder {
   size_t W_, user_off_ = 0;
   std::vector<RobotBall> balls_;
   std::vector<HorizontalLine> lines_;
+  std::vector<CapsuleObstacle> capsules_;
   // (col, row) -> value, last write wins ([REF] constraint-builder.h:129).  A write log that is sorted into CSC
   // order and de-duplicated on demand: the builder runs once per trajectory, segment and re-linearisation,
   // and a std::map made it the bottleneck of the batched driver.
@@ -356,6 +393,23 @@ class ConstraintBuilder {
     lo_[row] = low + ball.radius;
     up_[row] = upp - ball.radius;
     assert(lo_[row] <= up_[row]);
+  }
+  // nrm' J with nrm = (p - c) / |p - c| (+Z when p sits on the segment), written whether the row is active or not; active
+  // within `margin` of the surface: (R + r) - dist + (nrm' J) q <= (nrm' J) x, the ball's radius is part of the bound
+  void capsuleRow(size_t row, const RobotBall &ball, const CapsuleObstacle &cap, const Point &p, const std::array<double, 3 * N_DIM> &J,
+                  const Vec<N_DIM> &q, size_t waypoint) {
+    const Point v = cap.offset(p);
+    const double dist = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), reach = cap.radius + ball.radius;
+    const bool far = dist > 1e-12;
+    const Point nrm{far ? v[0] / dist : 0.0, far ? v[1] / dist : 0.0, far ? v[2] / dist : 1.0};
+    double gq = 0.0;
+    for (size_t j = 0; j < N_DIM; ++j) {
+      const double g = nrm[0] * J[0 * N_DIM + j] + nrm[1] * J[1 * N_DIM + j] + nrm[2] * J[2 * N_DIM + j];
+      set(nthPos(waypoint) + j, row, g);
+      gq += g * q[j];
+    }
+    lo_[row] = dist - reach < cap.margin ? (reach - dist) + gq : -INF;
+    up_[row] = INF;
   }
 };
 
@@ -439,6 +493,10 @@ class GOMPSolver {
   // counters for tests / reporting
   int segments_run = 0, qp_solves = 0, qp_updates = 0;
   bool prefetch_patterns = true;
+  // Not in the reference: capsule / sphere obstacles besides the lines; set before run()
+  std::vector<CapsuleObstacle> capsules;
+  // (tests) the acceptance test that ends the SQP loop
+  bool acceptable(const QPVector &q_trajectory) const { return isSolutionOK(q_trajectory); }
 
  private:
   struct PrefetchJoiner { std::vector<std::thread> threads; ~PrefetchJoiner() { for (auto &t : threads) t.join(); } };
@@ -465,7 +523,7 @@ class GOMPSolver {
   }
   ConstraintBuilder<N_DIM> jointSpaceRows(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
     assert(waypoints >= 4);
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -493,6 +551,7 @@ class GOMPSolver {
         }
         for (const HorizontalLine &line : obstacles)
           if (line.hasCollision(w, xyz, ball) && !line.isAbove(p, ball)) res = false;
+        if (!capsulesClear(capsules, p, ball)) res = false;
       }
     }
     return res;
@@ -621,6 +680,7 @@ class BatchGOMPSolver {
   std::vector<int> segments_run, qp_solves, qp_updates;
   int batch_solves = 0;
   bool reuse_solvers = true;      // keep the per-segment solvers across run() calls (see run())
+  std::vector<CapsuleObstacle> capsules;      // capsule / sphere obstacles besides the lines; set before run()
   int solver_reuses = 0;          // how often a kept solver was re-initialised instead of a new one being built
   // where the wall time of the last run() went: building constraints, QP setup (analysis + upload + factorisation),
   // batched solves, feasibility checks + re-linearisation + update
@@ -654,7 +714,7 @@ class BatchGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -682,6 +742,7 @@ class BatchGOMPSolver {
         }
         for (const HorizontalLine &line : obstacles)
           if (line.hasCollision(w, xyz, ball) && !line.isAbove(p, ball)) res = false;
+        if (!capsulesClear(capsules, p, ball)) res = false;
       }
     }
     return res;
@@ -715,6 +776,10 @@ class ContinuousGOMPSolver {
     const size_t B = starts.size();
     assert(ends.size() == B && B > 0);
     starts_ = &starts; ends_ = &ends;
+    if (!(capsules == scene_capsules_)) {                    // the kept scenes hold the capsules of the run that made them
+      for (Stage &st : stages_) if (st.scene) { mi_gomp_scene_free(st.scene); st.scene = nullptr; }
+      scene_capsules_ = capsules;
+    }
     traj_.clear(); traj_.resize(B);
     segments_run.assign(B, 0); qp_solves.assign(B, 0); qp_updates.assign(B, 0);
     advances = 0; solver_reuses = 0;
@@ -755,6 +820,9 @@ class ContinuousGOMPSolver {
   // The DH chain of the balls made by dhBall() (include/mi_osqp/dh_kinematics.hpp, MI_GOMP_MODEL_DH_CHAIN): the device path
   // needs it next to them; without it such balls keep the planner on the host callbacks.
   std::optional<mi_gomp_chain> dh_chain;
+  // Capsule / sphere obstacles besides the lines; set before run().  On the device path they go into the scene
+  // (mi_gomp_scene_create_world).
+  std::vector<CapsuleObstacle> capsules;
   int pipeline_depth = 1;              // 2: a stage enqueues its next advance before it looks at the previous one's results
   int segments_per_advance = 4;        // a launch runs on until a QP of the stage finishes, at most that many segments
   // per stage: {waypoints, advances, seconds admitting, waiting for the device, processing finished QPs, idle}
@@ -796,6 +864,7 @@ class ContinuousGOMPSolver {
   };
   std::vector<Traj> traj_;
   std::array<Stage, SEGMENTS> stages_;
+  std::vector<CapsuleObstacle> scene_capsules_;
   const std::vector<Ctrl<N_DIM>> *starts_ = nullptr, *ends_ = nullptr;
   std::atomic<size_t> finished_{0};
   std::atomic<bool> failed_{false};
@@ -898,7 +967,16 @@ class ContinuousGOMPSolver {
     }
     double lo[3], hi[3];
     for (int k = 0; k < 3; ++k) { lo[k] = con_3d.first ? (*con_3d.first)[k] : -INF; hi[k] = con_3d.second ? (*con_3d.second)[k] : INF; }
-    const int rc = dh_chain ? mi_gomp_scene_create_chain(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, &*dh_chain, (int64_t)balls.size(),
+    std::vector<mi_gomp_capsule> caps;
+    for (const CapsuleObstacle &c : capsules) {
+      mi_gomp_capsule g{};
+      for (int k = 0; k < 3; ++k) { g.a[k] = c.a[k]; g.b[k] = c.b[k]; }
+      g.radius = c.radius; g.margin = c.margin;
+      caps.push_back(g);
+    }
+    const int rc = !caps.empty() ? mi_gomp_scene_create_world(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+                                                              (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(), lo, hi)
+                   : dh_chain ? mi_gomp_scene_create_chain(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, &*dh_chain, (int64_t)balls.size(),
                                                          balls.data(), (int64_t)lines.size(), lines.data(), lo, hi)
                             : mi_gomp_scene_create(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, (int64_t)balls.size(), balls.data(),
                                                    (int64_t)lines.size(), lines.data(), lo, hi);
@@ -980,7 +1058,7 @@ class ContinuousGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -1008,6 +1086,7 @@ class ContinuousGOMPSolver {
         }
         for (const HorizontalLine &line : obstacles)
           if (line.hasCollision(w, xyz, ball) && !line.isAbove(p, ball)) res = false;
+        if (!capsulesClear(capsules, p, ball)) res = false;
       }
     }
     return res;

@@ -264,11 +264,16 @@ enum { MI_GM_UR5E_FLANGE = 1, MI_GM_UR5E_WRIST3 = 2, MI_GM_UR5E_ELBOW = 3, MI_GM
 struct GompChainDev { int n_joints, pad; double a[MI_GOMP_MAXD], d[MI_GOMP_MAXD], ca[MI_GOMP_MAXD], sa[MI_GOMP_MAXD], theta0[MI_GOMP_MAXD]; };
 struct GompBallDev { int model, is_gripper; double radius; double param[12]; };
 struct GompLineDev { double D[3], A[3]; int below, pad; };
+// a capsule obstacle (mi_gomp_capsule): the segment a .. a + e swept by a sphere of radius R; ee = e . e taken once on the
+// host (0: a sphere), margin = the distance from the surface at which the row starts to constrain
+struct GompCapsuleDev { double a[3], e[3], ee, R, margin; };
 struct GompArgs {
   int dims, W, n_balls, n_lines, n, m, nnzA, n_ids, row0, write_rows;
+  int n_caps, pad;
   const int *ids;                // the listed QPs
   const GompBallDev *balls;
   const GompLineDev *lines;
+  const GompCapsuleDev *caps;    // [n_caps]: their rows follow the lines' in every (ball, waypoint) block
   double con_lo[3], con_hi[3];   // work-space box of the gripper balls (+-1e30 = none)
   const int *aidx;               // [3-D row][dims]: position of that row's entry in column nthPos(w) + j of A's value array
   const double *traj;            // [n_ids][n]: the trajectories to linearise around (row = position in the list)

@@ -3690,7 +3690,8 @@ hipError_t launch_ruiz(const RuizArgs &a, hipStream_t st) {
 // bounds con - p_axis + J_axis q_w -+ radius, every (ball, line) pair one Z row - a bound when the ball collides with the
 // line's vertical plane at that waypoint (HorizontalLine::hasCollision: close to it, or on opposite sides of it from a
 // neighbouring waypoint), a dummy row otherwise - and the trajectory is accepted when every ball respects the box and is above
-// (below) the lines it collides with.  One workgroup per trajectory, one thread per (ball, waypoint).
+// (below) the lines it collides with.  Every (ball, capsule) pair gets one row after the lines' (see the loop over g.caps) and
+// must keep a clearance of -1e-3 or more.  One workgroup per trajectory, one thread per (ball, waypoint).
 __device__ __forceinline__ void ur5e_point(const double *q, int frame, double *p, double *J /* 3 x 6 row-major */) {
   const double a[6] = {0.0, -0.425, -0.3922, 0.0, 0.0, 0.0}, d[6] = {0.1625, 0.0, 0.0, 0.1333, 0.0997, 0.0996};
   const double alpha[6] = {1.5707963267948966, 0.0, 0.0, 1.5707963267948966, -1.5707963267948966, 0.0};
@@ -3792,7 +3793,7 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
   extern __shared__ double smem[];                 // xyz[n_balls][W][3]
   __shared__ int s_ok;
   const int jq = blockIdx.x, qp = g.ids[jq], tid = threadIdx.x;
-  const int D = g.dims, W = g.W, NB = g.n_balls, NL = g.n_lines;
+  const int D = g.dims, W = g.W, NB = g.n_balls, NL = g.n_lines, NC = g.n_caps;
   const double *traj = g.traj + (size_t)jq * g.n;
   if (tid == 0) s_ok = 1;
   double p[3] = {0, 0, 0}, J[3 * MI_GOMP_MAXD], q[MI_GOMP_MAXD];
@@ -3825,8 +3826,8 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
     for (int ax = 0; ax < 3; ax++) { double sacc = 0.0; for (int j = 0; j < D; j++) sacc += J[ax * D + j] * q[j]; Jq[ax] = sacc; }
     // this pair's first row: the balls before it (all their waypoints), then the waypoints before it of this ball
     int row = g.row0;
-    for (int b2 = 0; b2 < bi; b2++) row += W * ((g.balls[b2].is_gripper ? 3 : 0) + NL);
-    row += w * ((ball.is_gripper ? 3 : 0) + NL);
+    for (int b2 = 0; b2 < bi; b2++) row += W * ((g.balls[b2].is_gripper ? 3 : 0) + NL + NC);
+    row += w * ((ball.is_gripper ? 3 : 0) + NL + NC);
     auto put = [&](int r, int axis, double low, double upp) {
       if (!wr) return;
       const int *ai = g.aidx + (size_t)(r - g.row0) * D;
@@ -3856,6 +3857,30 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
         const bool above = ln.below ? (p[2] - ln.A[2]) <= -ball.radius + 1e-3 : (p[2] - ln.A[2]) >= ball.radius - 1e-3;
         if (!above) ok = 0;
       } else put(row++, 2, -MI_INFTY, MI_INFTY);                                            // dummy row: keeps the pattern constant
+    }
+    // capsules (CapsuleObstacle of gomp.hpp): the row is n' J with n the unit vector from the closest point of the segment to
+    // the ball's centre, active within `margin` of the surface; the ball's radius is part of the bound (put() would add it
+    // again).  Capsule ci is the same for every lane: uniform loads, nothing indexed per lane; no neighbouring waypoint.
+    for (int ci = 0; ci < NC; ci++, row++) {
+      const GompCapsuleDev &cp = g.caps[ci];
+      double t = 0.0;
+      if (cp.ee != 0.0) t = fmin(1.0, fmax(0.0, ((p[0] - cp.a[0]) * cp.e[0] + (p[1] - cp.a[1]) * cp.e[1] + (p[2] - cp.a[2]) * cp.e[2]) / cp.ee));
+      const double v0 = p[0] - (cp.a[0] + t * cp.e[0]), v1 = p[1] - (cp.a[1] + t * cp.e[1]), v2 = p[2] - (cp.a[2] + t * cp.e[2]);
+      const double dist = sqrt(v0 * v0 + v1 * v1 + v2 * v2), reach = cp.R + ball.radius;
+      const double s = dist - reach;
+      if (!(s >= -1e-3)) ok = 0;
+      if (!wr) continue;
+      const bool far = dist > 1e-12;
+      const double n0 = far ? v0 / dist : 0.0, n1 = far ? v1 / dist : 0.0, n2 = far ? v2 / dist : 1.0;
+      const int *ai = g.aidx + (size_t)(row - g.row0) * D;
+      double gq = 0.0;
+      for (int j = 0; j < D; j++) {
+        const double gj = n0 * J[0 * D + j] + n1 * J[1 * D + j] + n2 * J[2 * D + j];
+        g.A[(size_t)qp * g.nnzA + ai[j]] = gj;                                               // written for inactive rows too
+        gq += gj * q[j];
+      }
+      g.l[(size_t)qp * g.m + row] = s < cp.margin ? (reach - dist) + gq : -MI_INFTY;
+      g.u[(size_t)qp * g.m + row] = MI_INFTY;
     }
   }
   }

@@ -3323,10 +3323,11 @@ int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t
 // Besides the built-in models a scene may hold one DH chain (mi_gomp_chain) with balls fixed in its link frames.
 struct mi_gomp_scene {
   mi_osqp_batch *h = nullptr;
-  int dims = 0, W = 0, n_balls = 0, n_lines = 0, row0 = 0, n_rows3d = 0;
+  int dims = 0, W = 0, n_balls = 0, n_lines = 0, n_caps = 0, row0 = 0, n_rows3d = 0;
   double con_lo[3] = {-1e30, -1e30, -1e30}, con_hi[3] = {1e30, 1e30, 1e30};
   DevBuf<GompBallDev> balls;
   DevBuf<GompLineDev> lines;
+  DevBuf<GompCapsuleDev> caps;
   GompChainDev chain{};                       // the DH chain of the MI_GM_DH_CHAIN balls (n_joints 0: the scene has none)
   DevBuf<int> aidx;
   DevBuf<double> A, l, u;                     // QP-major raw rows as ConstraintBuilder::build() lays them out
@@ -3349,9 +3350,9 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
   if ((rc = ring_upload(h, sp, (size_t)nq * n * sizeof(double)))) return rc;
   hipStream_t st = h->stream;
   GompArgs g{};
-  g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
+  g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n_caps = sc->n_caps; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
   g.row0 = sc->row0; g.write_rows = write_rows;
-  g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
+  g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.caps = sc->caps.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
   for (int k = 0; k < 3; k++) { g.con_lo[k] = sc->con_lo[k]; g.con_hi[k] = sc->con_hi[k]; }
   g.A = sc->A.p; g.l = sc->l.p; g.u = sc->u.p; g.ok = sc->h_ok;
   g.chain = sc->chain;
@@ -3362,13 +3363,24 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
   return MI_OSQP_OK;
 }
 
-// mi_gomp_scene_create (chain null: model 6 is refused as it always was) and mi_gomp_scene_create_chain.  Everything that can
-// be refused is refused here on the host, the checks that need no handle first.
+// mi_gomp_scene_create (chain null: model 6 is refused as it always was), mi_gomp_scene_create_chain and
+// mi_gomp_scene_create_world (capsules besides).  Everything that can be refused is refused here on the host, the checks that
+// need no handle first.
 static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain, bool chain_entry,
-                             int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
+                             int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
+                             int64_t n_capsules, const mi_gomp_capsule *capsules, const double *con_lo, const double *con_hi) {
   if (!out) return MI_OSQP_ERR_NULL;
   *out = nullptr;
   if ((n_balls > 0 && !balls) || (n_lines > 0 && !lines)) return MI_OSQP_ERR_NULL;
+  if (n_capsules > 0 && !capsules) { g_last_error = "n_capsules > 0 and no capsules"; return MI_OSQP_ERR_NULL; }
+  if (n_capsules < 0) { g_last_error = "n_capsules is negative"; return MI_OSQP_ERR_INVALID_DATA; }
+  for (int64_t c = 0; c < n_capsules; c++) {
+    const mi_gomp_capsule &cp = capsules[c];
+    bool finite = std::isfinite(cp.radius) && std::isfinite(cp.margin);
+    for (int k = 0; k < 3; k++) finite = finite && std::isfinite(cp.a[k]) && std::isfinite(cp.b[k]);
+    if (!finite) { g_last_error = "capsule " + std::to_string(c) + " has a field that is not finite"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (cp.radius < 0.0 || cp.margin < 0.0) { g_last_error = "capsule " + std::to_string(c) + ": radius and margin must not be negative"; return MI_OSQP_ERR_INVALID_DATA; }
+  }
   GompChainDev hc{};
   if (chain_entry) {
     for (int64_t b = 0; b < n_balls; b++)
@@ -3405,14 +3417,14 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
   for (int b = 0; b < (int)n_balls; b++) {
     if (balls[b].model < MI_GM_UR5E_FLANGE || balls[b].model > (hc.n_joints ? MI_GM_DH_CHAIN : MI_GM_TABLE)) return MI_OSQP_ERR_INVALID_DATA;
     if ((balls[b].model <= MI_GM_UR5E_ELBOW && D != 6) || ((balls[b].model == MI_GM_YAW_2LINK || balls[b].model == MI_GM_TABLE) && D != 3)) return MI_OSQP_ERR_INVALID_DATA;
-    rows3d += W * ((balls[b].is_gripper ? 3 : 0) + (int)n_lines);
+    rows3d += W * ((balls[b].is_gripper ? 3 : 0) + (int)n_lines + (int)n_capsules);
   }
-  if (row0 + rows3d > an.m) return MI_OSQP_ERR_INVALID_DATA;
+  if (row0 + rows3d > an.m) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene"; return MI_OSQP_ERR_INVALID_DATA; }
   DevGuard guard(h->device);
   mi_gomp_scene *sc = new (std::nothrow) mi_gomp_scene();
   if (!sc) return MI_OSQP_ERR_ALLOC;
   std::unique_ptr<mi_gomp_scene> own(sc);
-  sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->row0 = row0; sc->n_rows3d = rows3d;
+  sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->n_caps = (int)n_capsules; sc->row0 = row0; sc->n_rows3d = rows3d;
   sc->chain = hc;
   for (int k = 0; k < 3; k++) { sc->con_lo[k] = con_lo ? con_lo[k] : -1e30; sc->con_hi[k] = con_hi ? con_hi[k] : 1e30; }
   // where the entries of the 3-D rows sit in A's value array: row r of waypoint w holds D entries in the columns of q_w
@@ -3421,7 +3433,7 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
     int r = row0;
     for (int b = 0; b < (int)n_balls; b++)
       for (int w = 0; w < W; w++)
-        for (int k = 0; k < (balls[b].is_gripper ? 3 : 0) + (int)n_lines; k++, r++)
+        for (int k = 0; k < (balls[b].is_gripper ? 3 : 0) + (int)n_lines + (int)n_capsules; k++, r++)
           for (int j = 0; j < D; j++) {
             const int col = w * D + j;
             const int *lo = an.Ai.data() + an.Ap[col], *hi = an.Ai.data() + an.Ap[col + 1];
@@ -3440,8 +3452,15 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
     for (int k = 0; k < 3; k++) hl[li].A[k] = lines[li].point[k];
     hl[li].below = lines[li].below; hl[li].pad = 0;
   }
+  std::vector<GompCapsuleDev> hcap((size_t)n_capsules);
+  for (int c = 0; c < (int)n_capsules; c++) {
+    GompCapsuleDev &d = hcap[c];
+    for (int k = 0; k < 3; k++) { d.a[k] = capsules[c].a[k]; d.e[k] = capsules[c].b[k] - capsules[c].a[k]; }
+    d.ee = d.e[0] * d.e[0] + d.e[1] * d.e[1] + d.e[2] * d.e[2];
+    d.R = capsules[c].radius; d.margin = capsules[c].margin;
+  }
   int rc;
-  if ((rc = sc->balls.upload(hb)) || (rc = sc->lines.upload(hl)) || (rc = sc->aidx.upload(aidx)) ||
+  if ((rc = sc->balls.upload(hb)) || (rc = sc->lines.upload(hl)) || (n_capsules && (rc = sc->caps.upload(hcap))) || (rc = sc->aidx.upload(aidx)) ||
       (rc = sc->A.alloc((size_t)h->B * std::max(an.Ap[an.n], 1))) || (rc = sc->l.alloc((size_t)h->B * std::max(an.m, 1))) || (rc = sc->u.alloc((size_t)h->B * std::max(an.m, 1)))) return rc;
   HIPCHK(hostpool::alloc((void **)&sc->h_ok, (size_t)h->B * sizeof(int), &sc->h_ok_cap));
   HIPCHK(hipEventCreateWithFlags(&sc->ev, hipEventDisableTiming));
@@ -3455,11 +3474,16 @@ extern "C" {
 
 int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, int64_t n_balls, const mi_gomp_ball *balls,
                          int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_chain(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, 0, nullptr, con_lo, con_hi);
+}
+int mi_gomp_scene_create_world(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
+                               int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
+                               int64_t n_capsules, const mi_gomp_capsule *capsules, const double *con_lo, const double *con_hi) {
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, con_lo, con_hi);
 }
 
 void mi_gomp_scene_free(mi_gomp_scene *sc) {
