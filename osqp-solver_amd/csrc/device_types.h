@@ -147,6 +147,8 @@ struct PolishArgs {
   signed char *act;             // [slot][m]: -1 lower-active, +1 upper-active, 0 inactive (polish_active_kernel)
   double *sol;                  // [tile][N][BT]: the refinement iterate [x; y_red] in natural order
   int refine_iter;
+  int inner;                    // polish only: rounds of refinement against K_d itself behind every solve (0 = the plain solve)
+  double delta;                 // the d of K_d (read when inner > 0)
 };
 // active set of every kOptimal QP from its final iterate, stat = 1 for those QPs, 0 for the others
 hipError_t launch_polish_active(const KernelArgs &a, const PolishArgs &p, int BT, hipStream_t st);

@@ -1808,36 +1808,52 @@ struct ReducedTile {
 // s = K_d^-1 b, then refine_iter rounds of  s += K_d^-1 (b - K s)      K_d = [[P + d I, A~'], [A~, -d I]], K: d = 0,
 // A~ = A without its inactive rows.  rhs0(e) = entry e of b in natural order (0 on inactive rows and for a QP not marked).
 // K s runs through the check schedule (P x / A'y / A x): A~'s_y = A's_y (s_y is 0 on inactive rows), A~ s_x = A s_x masked.
+//
+// One solve with the polish factor is not K_d^-1: the LDL' has no pivoting and eliminates rows of the -d I block before their
+// variables (multipliers of 1 / d: an error of u / d of the solution), and the dense tail inverts its block (u / d^2).  With
+// inner > 0 (the polish) every application of K_d^-1 is therefore followed by `inner` rounds of refinement against K_d ITSELF.
+// Round r of the outer loop solves K_d t = b + d J s_prev (J = diag(I, -I), s_prev = the iterate it started from, 0 in round 0),
+// which is s_prev + K_d^-1 (b - K s_prev); its inner rounds are t += K_d^-1 (b + d J s_prev - K_d t), starting from t = s_prev,
+// so that inner round 0 is the plain round and inner = 0 (the adjoint) is the loop without any of this, bit for bit.  s_prev
+// lives in the tile's out2 scratch, which polish_kernel uses only behind the loop; each thread reads the entries it wrote.
 template <int BT, int NT, bool GX, bool WIDE, class Rhs0>
-__device__ __forceinline__ void reduced_solve_refine(const ReducedTile<BT, GX, WIDE> &c, int refine_iter, Rhs0 rhs0) {
+__device__ __forceinline__ void reduced_solve_refine(const ReducedTile<BT, GX, WIDE> &c, int refine_iter, Rhs0 rhs0, int inner = 0,
+                                                     double delta = 0.0) {
   const KernelArgs &a = c.a;
   const int n = a.n, N = a.N, tid = c.tid, nthr = c.nthr;
   const size_t nB = (size_t)n * BT;
-  double *xs = c.xs, *s = c.s;
+  double *xs = c.xs, *s = c.s, *prev = c.p.out2;
   for (int r = 0; r <= refine_iter; r++) {
-    if (r > 0) {
-      for (int e = tid; e < N * BT; e += nthr) xs[e] = s[e];
-      c.spmv();
-    }
-    for (int e = tid; e < N * BT; e += nthr) {
-      double v = rhs0(e);
-      if (c.on && r > 0) {
-        const int i = e / BT;
-        if (i < n) v -= c.p.out1[e] + c.p.out1[nB + e];
-        else if (c.act[i - n]) v -= c.p.out1[2 * nB + (e - (int)nB)];
+    if (inner > 0) for (int e = tid; e < N * BT; e += nthr) prev[e] = r ? s[e] : 0.0;
+    for (int j = 0; j <= inner; j++) {
+      const bool first = r == 0 && j == 0;
+      if (!first) {
+        for (int e = tid; e < N * BT; e += nthr) xs[e] = s[e];
+        c.spmv();
       }
-      c.put_rhs(e, v);
+      for (int e = tid; e < N * BT; e += nthr) {
+        double v = rhs0(e);
+        if (c.on && !first) {
+          const int i = e / BT;
+          if (j == 0) {
+            if (i < n) v -= c.p.out1[e] + c.p.out1[nB + e];
+            else if (c.act[i - n]) v -= c.p.out1[2 * nB + (e - (int)nB)];
+          } else if (i < n) v += delta * (prev[e] - s[e]) - (c.p.out1[e] + c.p.out1[nB + e]);
+          else if (c.act[i - n]) v -= delta * (prev[e] - s[e]) + c.p.out1[2 * nB + (e - (int)nB)];
+        }
+        c.put_rhs(e, v);
+      }
+      if (c.df && tid == 0) st_sc1(xs + 2 * (size_t)a.df_shadow, 0.0);
+      c.sync();
+      kkt_solve_lds<BT, MI_PFV_NT(NT, GX), GX, WIDE>(a, c.p, xs, tid, nthr, c.wave, c.nw, c.lane, c.mw);
+      for (int e = tid; e < N * BT; e += nthr) {
+        const int i = e / BT;
+        double d = c.get_sol(e);
+        if (i >= n && !c.act[i - n]) d = 0.0;
+        s[e] = first ? d : s[e] + d;
+      }
+      c.sync();
     }
-    if (c.df && tid == 0) st_sc1(xs + 2 * (size_t)a.df_shadow, 0.0);
-    c.sync();
-    kkt_solve_lds<BT, MI_PFV_NT(NT, GX), GX, WIDE>(a, c.p, xs, tid, nthr, c.wave, c.nw, c.lane, c.mw);
-    for (int e = tid; e < N * BT; e += nthr) {
-      const int i = e / BT;
-      double d = c.get_sol(e);
-      if (i >= n && !c.act[i - n]) d = 0.0;
-      s[e] = r ? s[e] + d : d;
-    }
-    c.sync();
   }
 }
 
@@ -1867,7 +1883,7 @@ __global__ __launch_bounds__(NT) void polish_kernel(KernelArgs a, PolishArgs pa)
       else if (const signed char ac = c.act[i - n]) v = ac < 0 ? p.l[e - (int)nB] : p.u[e - (int)nB];
     }
     return v;
-  });
+  }, pa.inner, pa.delta);
   // z = A x
   for (int e = tid; e < N * BT; e += nthr) xs[e] = e < (int)nB ? s[e] : 0.0;
   c.spmv();

@@ -1358,6 +1358,10 @@ static int ensure_polish_buffers(mi_osqp_batch *h) {
   return MI_OSQP_OK;
 }
 
+// Rounds of refinement against K_d behind every solve of a polish (kernels.hip reduced_solve_refine): one solve is off by up to
+// 1e-3 of the solution at d = 1e-6 with a dense tail, four rounds take that below round-off.
+static constexpr int kPolishInner = 4;
+
 // Solution polishing after a blocking solve (OSQP polish.c on the scaled data): the active set of
 // every kOptimal QP (polish_active_kernel), the reduced KKT matrix of those QPs factored in the handle's own pattern into
 // the polish buffers (device_refactor_slots in polish mode: same work list / grouped workgroups / dense tail as a
@@ -1370,7 +1374,7 @@ static int polish_impl(mi_osqp_batch *h, const KernelArgs &a) {
   h->pol_status.assign((size_t)h->B, 0);
   if ((rc = ensure_polish_buffers(h))) return rc;
   std::vector<int> work = koptimal_slots(h);      // (h_iscal: copied at the end of the solve)
-  PolishArgs pa{h->pol_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter};
+  PolishArgs pa{h->pol_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter, kPolishInner, h->st.delta};
   HIPCHK(hipEventRecord(h->evp0, h->stream));
   HIPCHK(launch_polish_active(a, pa, BT, h->stream));
   const int n_pol = (int)work.size();
@@ -2997,7 +3001,7 @@ int mi_osqp_batch_polish_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *id
   if ((rc = cont_stage_ids(h, n_ids, ids, &d_ids, nullptr))) return rc;
   KernelArgs a = make_args(h);
   a.x_out = c.xh; a.y_out = c.yh; a.cert_out = c.ch;
-  PolishArgs pa{h->pol_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter};
+  PolishArgs pa{h->pol_stat.p, h->pol_act.p, h->pol_sol.p, (int)h->st.polish_refine_iter, kPolishInner, h->st.delta};
   HIPCHK(launch_polish_active_list(a, pa, d_ids, nq, BT, h->stream));
   if ((rc = enqueue_refactor_list(h, d_ids, nq, &pa))) return rc;
   HIPCHK(launch_polish(polish_stream_args(h, a), pa, BT, h->ntiles, h->threads, h->lds, h->n_cus, h->stream));
