@@ -30,6 +30,9 @@
 #define OQ_MIN_SCALING  1e-4
 #define OQ_MAX_SCALING  1e4
 #define OQ_DIVISION_TOL (1.0 / OQ_INFTY)
+/* the guard of the two normalising divisions of the rho estimate [EXT-unverified]: the value the project's specification of
+ * the rule states (tests/admm_refs.py), recalled from OSQP 0.6 and not pinned against upstream's source */
+#define OQ_RHO_EST_DIV  1e-10
 #define OQ_ADAPTIVE_RHO_MULTIPLE_TERMINATION 4
 #define OQ_ADAPTIVE_RHO_FIXED 100
 
@@ -838,10 +841,10 @@ static oq_float compute_rho_estimate(const oq_work *w) {
   oq_float pri = vec_norm_inf(w->z_prev, m);      /* scaled residual vectors left by update_info */
   oq_float dua = vec_norm_inf(w->x_prev, n);
   oq_float pn = MAXF(vec_norm_inf(w->z, m), vec_norm_inf(w->Ax, m));
-  pri /= (pn + OQ_DIVISION_TOL);
+  pri /= (pn + OQ_RHO_EST_DIV);
   oq_float dn = MAXF(vec_norm_inf(w->q, n), vec_norm_inf(w->Aty, n));
   dn = MAXF(dn, vec_norm_inf(w->Px, n));
-  dua /= (dn + OQ_DIVISION_TOL);
+  dua /= (dn + OQ_RHO_EST_DIV);
   oq_float est = w->settings.rho * sqrt(pri / dua);
   est = MINF(MAXF(est, OQ_RHO_MIN), OQ_RHO_MAX);
   return est;

@@ -36,6 +36,9 @@ static hipError_t ensure_dynamic_lds(const void *kern, size_t lds);      // (lau
 #define MI_INFTY 1e30
 #define MI_MIN_SCALING 1e-4
 #define MI_DIV_TOL 1e-30
+// the guard of the two normalising divisions of the rho estimate: the value this project's specification of the rule states
+// (tests/admm_refs.py); recalled from OSQP 0.6, not pinned against upstream's source, whose later 0.6.x may use 1 / INFTY
+#define MI_RHO_EST_DIV 1e-10
 #define MI_RHO_MIN 1e-6
 #define MI_RHO_MAX 1e6
 #define MI_NOROW 0xFFFFFFFFu
@@ -1311,8 +1314,8 @@ __device__ __forceinline__ int check_body(const KernelArgs &a, double *smem, int
   double rho_est = p.dscal[DS_RHO_EST * BT + b];
   // ---- E13: rho estimate from the SCALED residual norms
   auto rho_estimate = [&]() -> double {
-    const double pr = mx[8] / (fmax(mx[10], mx[11]) + MI_DIV_TOL);
-    const double du = mx[0] / (fmax(fmax(mx[2], mx[3]), mx[4]) + MI_DIV_TOL);
+    const double pr = mx[8] / (fmax(mx[10], mx[11]) + MI_RHO_EST_DIV);
+    const double du = mx[0] / (fmax(fmax(mx[2], mx[3]), mx[4]) + MI_RHO_EST_DIV);
     double e = rho * sqrt(pr / du);
     return fmin(fmax(e, MI_RHO_MIN), MI_RHO_MAX);
   };

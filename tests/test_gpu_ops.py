@@ -114,6 +114,7 @@ def run_spmv(s, x, y, outputs=("Px", "Aty", "Ax"), sentinel=None):
     for key, w in (("Px", n), ("Aty", n), ("Ax", m)):
         if key in outputs:
             bufs[key] = torch.full((B + 1, max(w, 1)), np.nan if sentinel is None else sentinel, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()                                       # (the fills run on torch's stream, the op on the handle's own)
     s.spmv_device(tx, ty, *(bufs[k][:B] if k in bufs else None for k in ("Px", "Aty", "Ax")))
     out = {k: v.cpu().numpy() for k, v in bufs.items()}
     if sentinel is not None:
@@ -304,6 +305,7 @@ def kkt_check(s, pr, rho=None, qps=None, seed=3):
         rho = [s.settings.rho] * B
     rhs = np.random.default_rng(seed).standard_normal((B, n + m))
     trhs = torch.tensor(rhs, device="cuda"); sol = torch.full_like(trhs, np.nan)
+    torch.cuda.synchronize()                                       # (the fill runs on torch's stream, the op on the handle's own)
     s.kkt_solve_device(trhs, sol)
     sol = sol.cpu().numpy()
     worst = 0.0
