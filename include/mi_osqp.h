@@ -222,6 +222,10 @@ int mi_osqp_batch_update_P(mi_osqp_batch *h, const int64_t *P_colptr, const int6
 int mi_osqp_batch_update_P_A(mi_osqp_batch *h, const int64_t *P_colptr, const int64_t *P_rowidx, const double *P_val,
                              const int64_t *A_colptr, const int64_t *A_rowidx, const double *A_val);  /* osqp_update_P_A */
 int mi_osqp_batch_warm_start_y(mi_osqp_batch *h, const double *y);                                 /* osqp_warm_start_y */
+/* The pattern of triu(P) as the analysis keeps it (CSC, n + 1 column pointers, *nnz_out = nnzPu row indices): the order of
+ * the adjoint's dP and of every P array of the _device and _some forms below, whichever form P had at setup.  Either array may
+ * be NULL; *nnz_out is always written.  No device is touched; the continuous mode stays. */
+int mi_osqp_batch_get_P_upper_pattern(mi_osqp_batch *h, int64_t *colptr, int64_t *rowidx, int64_t *nnz_out);   /* [n+1], [nnzPu] */
 /* Blocking solve of all B QPs (the ADMM iterate runs on the GPU). */
 int mi_osqp_batch_solve(mi_osqp_batch *h);
 int mi_osqp_batch_get_primal(mi_osqp_batch *h, double *x_out /*[B][n]*/);
@@ -259,6 +263,19 @@ int mi_osqp_batch_update_bounds_device(mi_osqp_batch *h, const double *d_l, cons
 int mi_osqp_batch_update_A_bounds_device(mi_osqp_batch *h, const double *d_Av, const double *d_l, const double *d_u, void *stream);
 /* osqp_update_lin_cost with q ([B][n], unscaled) in HBM: nothing crosses PCIe; `stream`: the stream that wrote it */
 int mi_osqp_batch_update_q_device(mi_osqp_batch *h, const double *d_q, void *stream);
+/* osqp_update_P with the new values in HBM: d_Pv [B][nnzPu] holds triu(P) in the order of
+ * mi_osqp_batch_get_P_upper_pattern - the layout of the adjoint's dP, so a gradient step on dP can be handed straight back.
+ * Semantics of mi_osqp_batch_update_P (unscale q, A and the bounds with the scaling in force, replace triu(P), equilibrate,
+ * refactor every QP with its current rho vectors, snapshot, restart the count of rho updates; the raw P the handle keeps
+ * follows); P does not cross PCIe.  `stream`: the stream that wrote the values (NULL: none pending).
+ * _update_P_A_bounds_device: new A values ([B][nnzA]) and bounds ([B][m]) with it - one equilibration, one refactorisation and
+ * one snapshot for everything given.  d_Pv == NULL is mi_osqp_batch_update_A_bounds_device; d_Av, d_l and d_u all NULL is
+ * mi_osqp_batch_update_P_device; any other NULL is MI_OSQP_ERR_NULL.  l > u anywhere: MI_OSQP_ERR_INVALID_DATA, nothing
+ * changes.  Handles that equilibrate on host threads (fewer than 16 QPs, or large ones) fetch the values and take the host
+ * path: same results, the data crosses PCIe twice. */
+int mi_osqp_batch_update_P_device(mi_osqp_batch *h, const double *d_Pv, void *stream);
+int mi_osqp_batch_update_P_A_bounds_device(mi_osqp_batch *h, const double *d_Pv, const double *d_Av, const double *d_l, const double *d_u,
+                                           void *stream);
 /* Solve and leave x[B][n] (and optionally status[B]/iters[B], int32) in HBM. */
 int mi_osqp_batch_solve_device(mi_osqp_batch *h, double *d_x_out, int32_t *d_status, int32_t *d_iters, void *stream);
 /* Back to the state right after setup (or after the last update that refactored): cold-start every QP, restore rho,
@@ -357,6 +374,7 @@ int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t
  *
  *     reinit_some / update_A_bounds_some / warm_start_x_some   new data for QPs that are not iterating
  *     update_q_some / warm_start_y_some
+ *     update_P_some / update_P_A_bounds_some
  *     solve_begin_some                                         Solve() entry of those QPs (own iteration count from 0)
  *     advance(n_segments)                                      enqueue ONE launch in which every iterating QP runs up to
  *                                                              n_segments segments of L iterations + check, L =
@@ -379,13 +397,23 @@ int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t
  * in flight are forgotten).  Not available for handles whose solve vector does not fit LDS (large single QPs).
  *
  * reinit_some = QPSolver::QPSolver for those QPs ([REF] src/osqp-wrapper.h:16-31) with the P and q in force (those given
- * at setup, or by the last mi_osqp_batch_update_P / _update_P_A / _update_q / update_q_some of the QP) and new A values / bounds: equilibration from the raw data, rho = settings.rho, zero iterates, no rho updates - the state
+ * at setup, or by the last mi_osqp_batch_update_P / _update_P_A / _update_P_device / update_P_some / _update_q / update_q_some of the QP) and new A values / bounds: equilibration from the raw data, rho = settings.rho, zero iterates, no rho updates - the state
  * mi_osqp_batch_setup leaves for that QP, bit for bit, without analysis or allocation.
  * update_A_bounds_some = QPSolver::update ([REF] src/osqp-wrapper.h:33-43) for those QPs. */
 int mi_osqp_batch_reinit_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids,
                               const double *A_val /*[n_ids][nnzA]*/, const double *l /*[n_ids][m]*/, const double *u);
 int mi_osqp_batch_update_A_bounds_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids,
                                        const double *A_val, const double *l, const double *u);
+/* osqp_update_P for those QPs, and with QPSolver::update in one equilibration and refactorisation: P_val [n_ids][nnzPu] holds
+ * triu(P) in the order of mi_osqp_batch_get_P_upper_pattern (host memory, like every per-QP argument).  The listed QPs get
+ * what mi_osqp_batch_update_P (then _update_A_bounds) gives them, bit for bit; the other QPs - iterating or not, the other QP
+ * of a two-QP tile included - are not touched.  The QP's count of rho updates restarts, a failed factor is forgotten (an
+ * indefinite P ends the QP's next solve as kNonConvex, a later good P clears that), the QP is no longer polishable, its
+ * share of the reset state is retaken, and a later reinit_some of the slot starts from the new P.  ids must be idle, in range
+ * and not repeated (MI_OSQP_ERR_INVALID_DATA, as is l > u); a refused call has enqueued and changed nothing. */
+int mi_osqp_batch_update_P_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *P_val /*[n_ids][nnzPu]*/);
+int mi_osqp_batch_update_P_A_bounds_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *P_val,
+                                         const double *A_val, const double *l, const double *u);
 int mi_osqp_batch_warm_start_x_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *x /*[n_ids][n]*/);
 /* osqp_update_lin_cost / osqp_warm_start_y for those QPs (see mi_osqp_update_q / mi_osqp_warm_start_y) */
 int mi_osqp_batch_update_q_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *q /*[n_ids][n]*/);

@@ -312,6 +312,29 @@ class BatchQPSolver {
     return mi_osqp_batch_update_bounds(h_, lbuf_.data(), ubuf_.data()) == MI_OSQP_OK;
   }
 
+  // The pattern of triu(P) as the handle keeps it (column pointers, row indices): the order of every P value array below and
+  // of the adjoint's dP, whichever form the P of the constructor had.
+  std::pair<std::vector<long long>, std::vector<long long>> upperPatternP() const {
+    int64_t nnz = 0;
+    if (mi_osqp_batch_get_P_upper_pattern(h_, nullptr, nullptr, &nnz) != MI_OSQP_OK) throw std::invalid_argument(mi_osqp_error_name(MI_OSQP_ERR_NULL));
+    std::vector<long long> outer((size_t)n_ + 1), inner((size_t)nnz);
+    (void)mi_osqp_batch_get_P_upper_pattern(h_, reinterpret_cast<int64_t *>(outer.data()), reinterpret_cast<int64_t *>(inner.data()), &nnz);
+    return {outer, inner};
+  }
+  // New values of triu(P) of every QP from device memory ([K][nnzPu], order of upperPatternP(); `stream`: the hipStream_t that
+  // wrote them), alone or with new A values ([K][nnzA]) and bounds ([K][m]) in one equilibration and refactorisation
+  // (mi_osqp_batch_update_P_device / _update_P_A_bounds_device).  reinit() no longer applies afterwards.
+  void updatePDevice(const double *d_Pv, void *stream = nullptr) {
+    pristine_ = false;
+    const int rc = mi_osqp_batch_update_P_device(h_, d_Pv, stream);
+    if (rc != MI_OSQP_OK) throw std::invalid_argument(std::string(mi_osqp_error_name(rc)) + " (" + mi_osqp_last_error() + ")");
+  }
+  void updateDevice(const double *d_Pv, const double *d_Av, const double *d_l, const double *d_u, void *stream = nullptr) {
+    pristine_ = false;
+    const int rc = mi_osqp_batch_update_P_A_bounds_device(h_, d_Pv, d_Av, d_l, d_u, stream);
+    if (rc != MI_OSQP_OK) throw std::invalid_argument(std::string(mi_osqp_error_name(rc)) + " (" + mi_osqp_last_error() + ")");
+  }
+
   // settings after construction, as QPSolver::updateSettings; updateRho: one rho per QP, every QP refactored
   mi_osqp_settings settings() const { mi_osqp_settings s; mi_osqp_default_settings(&s); (void)mi_osqp_batch_get_settings(h_, &s); return s; }
   void updateSettings(const mi_osqp_settings &s) {
@@ -387,13 +410,20 @@ class ContinuousQPSolver {
   bool compatible(long long slots, const QPConstraints &c0, const QPMatrixSparse &P) const {
     const QPMatrixSparse &A = std::get<1>(c0);
     return status_ == MI_OSQP_OK && slots == K_ && A.rows == m_ && A.cols == n_ && A.outer == A_outer_ && A.inner == A_inner_ &&
-           P.outer == P_.outer && P.inner == P_.inner && P.values == P_.values;
+           !p_updated_ && P.outer == P_.outer && P.inner == P_.inner && P.values == P_.values;
   }
 
   // QPSolver's constructor for the listed slots (new A values and bounds; P as built)
   void reinit(const std::vector<long long> &ids, const std::vector<const QPConstraints *> &cs) { newData(ids, cs, true); }
   // QPSolver::update for the listed slots
   void update(const std::vector<long long> &ids, const std::vector<const QPConstraints *> &cs) { newData(ids, cs, false); }
+  // osqp_update_P for the listed idle slots: Ps[j] holds the values of triu(P) of slot ids[j] in the handle's order
+  // (mi_osqp_batch_get_P_upper_pattern; for a P built as an upper triangle: the order of its values).  With cs: QPSolver::update
+  // in the same equilibration and refactorisation.  Nothing waits; the other slots are not touched.  A later reinit() of the
+  // slot starts from the new P, and compatible() no longer holds.  Refusals (a slot running, listed twice or out of range,
+  // a wrong size, l > u) throw std::invalid_argument and change nothing.
+  void updateP(const std::vector<long long> &ids, const std::vector<const QPVector *> &Ps) { newP(ids, Ps, nullptr); }
+  void updateP(const std::vector<long long> &ids, const std::vector<const QPVector *> &Ps, const std::vector<const QPConstraints *> &cs) { newP(ids, Ps, &cs); }
   void setWarmStart(const std::vector<long long> &ids, const std::vector<const QPVector *> &xs) {
     if (ids.empty()) return;
     xbuf_.clear();
@@ -472,9 +502,34 @@ class ContinuousQPSolver {
   mi_osqp_batch *handle() const { return h_; }          // for the device-side companions of the solver (mi_gomp_scene)
 
  private:
+  void newP(const std::vector<long long> &ids, const std::vector<const QPVector *> &Ps, const std::vector<const QPConstraints *> *cs) {
+    if (ids.empty()) return;
+    if (ids.size() != Ps.size() || (cs && ids.size() != cs->size())) throw std::invalid_argument(mi_osqp_error_name(MI_OSQP_ERR_INVALID_DATA));
+    int64_t nnzPu = 0;
+    if (mi_osqp_batch_get_P_upper_pattern(h_, nullptr, nullptr, &nnzPu) != MI_OSQP_OK) throw std::invalid_argument(mi_osqp_error_name(MI_OSQP_ERR_NULL));
+    pbuf_.clear();
+    for (const QPVector *v : Ps) {
+      if ((long long)v->size() != nnzPu) throw std::invalid_argument(mi_osqp_error_name(MI_OSQP_ERR_INVALID_DATA));
+      pbuf_.insert(pbuf_.end(), v->begin(), v->end());
+    }
+    if (cs) stage(*cs);
+    const int64_t *pid = reinterpret_cast<const int64_t *>(ids.data());
+    const int rc = cs ? mi_osqp_batch_update_P_A_bounds_some(h_, (int64_t)ids.size(), pid, pbuf_.data(), abuf_.data(), lbuf_.data(), ubuf_.data())
+                      : mi_osqp_batch_update_P_some(h_, (int64_t)ids.size(), pid, pbuf_.data());
+    if (rc != MI_OSQP_OK) throw std::invalid_argument(std::string(mi_osqp_error_name(rc)) + " (" + mi_osqp_last_error() + ")");
+    p_updated_ = true;
+  }
   void newData(const std::vector<long long> &ids, const std::vector<const QPConstraints *> &cs, bool fresh) {
     if (ids.empty()) return;
     if (ids.size() != cs.size()) throw std::invalid_argument(mi_osqp_error_name(MI_OSQP_ERR_INVALID_DATA));
+    stage(cs);
+    const int64_t *pid = reinterpret_cast<const int64_t *>(ids.data());
+    const int rc = fresh ? mi_osqp_batch_reinit_some(h_, (int64_t)ids.size(), pid, abuf_.data(), lbuf_.data(), ubuf_.data())
+                         : mi_osqp_batch_update_A_bounds_some(h_, (int64_t)ids.size(), pid, abuf_.data(), lbuf_.data(), ubuf_.data());
+    if (rc != MI_OSQP_OK) throw std::invalid_argument(std::string(mi_osqp_error_name(rc)) + " (" + mi_osqp_last_error() + ")");
+  }
+  // the A values and bounds of cs, slot-major, into abuf_ / lbuf_ / ubuf_
+  void stage(const std::vector<const QPConstraints *> &cs) {
     abuf_.clear(); lbuf_.clear(); ubuf_.clear();
     for (const QPConstraints *c : cs) {
       const auto &[lo, A, up] = *c;
@@ -484,17 +539,14 @@ class ContinuousQPSolver {
       lbuf_.insert(lbuf_.end(), lo.begin(), lo.end());
       ubuf_.insert(ubuf_.end(), up.begin(), up.end());
     }
-    const int64_t *pid = reinterpret_cast<const int64_t *>(ids.data());
-    const int rc = fresh ? mi_osqp_batch_reinit_some(h_, (int64_t)ids.size(), pid, abuf_.data(), lbuf_.data(), ubuf_.data())
-                         : mi_osqp_batch_update_A_bounds_some(h_, (int64_t)ids.size(), pid, abuf_.data(), lbuf_.data(), ubuf_.data());
-    if (rc != MI_OSQP_OK) throw std::invalid_argument(std::string(mi_osqp_error_name(rc)) + " (" + mi_osqp_last_error() + ")");
   }
   mi_osqp_batch *h_ = nullptr;
   long long K_ = 0, n_ = 0, m_ = 0, nnzA_ = 0;
   int status_ = 0;
   QPMatrixSparse P_;
+  bool p_updated_ = false;          // a slot's P is no longer the constructor's: compatible() must not hand the solver on
   std::vector<long long> A_outer_, A_inner_;
-  std::vector<double> abuf_, lbuf_, ubuf_, xbuf_;
+  std::vector<double> abuf_, lbuf_, ubuf_, xbuf_, pbuf_;
   mi_osqp_info last_{};
 };
 

@@ -105,6 +105,11 @@ def lib():
         L.mi_osqp_batch_update_P.argtypes = [vp, ip, ip, dp]
         L.mi_osqp_batch_update_P_A.argtypes = [vp, ip, ip, dp, ip, ip, dp]
         L.mi_osqp_batch_warm_start_y.argtypes = [vp, dp]
+        L.mi_osqp_batch_get_P_upper_pattern.argtypes = [vp, ip, ip, ip]
+        L.mi_osqp_batch_update_P_device.argtypes = [vp, vp, vp]
+        L.mi_osqp_batch_update_P_A_bounds_device.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.mi_osqp_batch_update_P_some.argtypes = [vp, C.c_int64, ip, dp]
+        L.mi_osqp_batch_update_P_A_bounds_some.argtypes = [vp, C.c_int64, ip, dp, dp, dp, dp]
         L.mi_osqp_batch_update_q_some.argtypes = [vp, C.c_int64, ip, dp]
         L.mi_osqp_batch_warm_start_y_some.argtypes = [vp, C.c_int64, ip, dp]
         L.mi_osqp_settings_update_check.argtypes = [C.POINTER(Settings), C.POINTER(Settings)]
@@ -434,6 +439,39 @@ class BatchSolver:
         _chk(lib().mi_osqp_batch_update_P_A(self._h, _ip(Pp), _ip(Pi), _dp(Px), _ip(self._Ap), _ip(self._Ai), _dp(Ax)),
              "update_P_A")
 
+    def P_upper_pattern(self):
+        """(colptr [n + 1], rowidx [nnzPu]) of triu(P) as the analysis keeps it: the order of adjoint()'s dP and of the Px of
+        update_P_device / update_P_A_bounds_device / update_P_some / update_P_A_bounds_some, whichever form P had at setup."""
+        nnz = C.c_int64()
+        _chk(lib().mi_osqp_batch_get_P_upper_pattern(self._h, None, None, C.byref(nnz)), "get_P_upper_pattern")
+        Pp, Pi = np.empty(self.n + 1, dtype=np.int64), np.empty(nnz.value, dtype=np.int64)
+        _chk(lib().mi_osqp_batch_get_P_upper_pattern(self._h, _ip(Pp), _ip(Pi), C.byref(nnz)), "get_P_upper_pattern")
+        return Pp, Pi
+
+    def _check_Pu(self, Px, rows):
+        """Px must be [rows, nnzPu]: a P with both triangles, as update_P takes it, is not the form of these calls"""
+        if getattr(self, "_nnzPu", None) is None:
+            nnz = C.c_int64()
+            _chk(lib().mi_osqp_batch_get_P_upper_pattern(self._h, None, None, C.byref(nnz)), "get_P_upper_pattern")
+            self._nnzPu = nnz.value
+        if tuple(Px.shape) != (rows, self._nnzPu):
+            raise ValueError(f"Px must have shape ({rows}, {self._nnzPu}): triu(P) in the order of P_upper_pattern(); got {tuple(Px.shape)}")
+
+    def update_P_device(self, Px, stream=None):
+        """update_P from a torch CUDA tensor ([B, nnzPu], float64, contiguous): triu(P) in the order of P_upper_pattern()."""
+        self._check_Pu(Px, self.B)
+        _chk(lib().mi_osqp_batch_update_P_device(self._h, C.c_void_p(Px.data_ptr()), None if stream is None else C.c_void_p(stream)),
+             "update_P_device")
+
+    def update_P_A_bounds_device(self, Px, Ax, l, u, stream=None):
+        """New triu(P) values, A values and bounds from torch CUDA tensors with one equilibration and one refactorisation.
+        Px None: update_A_bounds_device; Ax, l and u all None: update_P_device."""
+        if Px is not None:
+            self._check_Pu(Px, self.B)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _chk(lib().mi_osqp_batch_update_P_A_bounds_device(self._h, p(Px), p(Ax), p(l), p(u), None if stream is None else C.c_void_p(stream)),
+             "update_P_A_bounds_device")
+
     def warm_start_y(self, y):
         y = _f64(y).reshape(self.B, -1)
         _chk(lib().mi_osqp_batch_warm_start_y(self._h, _dp(y)), "warm_start_y")
@@ -533,6 +571,19 @@ class BatchSolver:
         ids = _i64(ids); k = len(ids)
         Ax, l, u = _f64(Ax).reshape(k, -1), _f64(l).reshape(k, -1), _f64(u).reshape(k, -1)
         _chk(lib().mi_osqp_batch_update_A_bounds_some(self._h, k, _ip(ids), _dp(Ax), _dp(l), _dp(u)), "update_A_bounds_some")
+
+    def update_P_some(self, ids, Px):
+        """New triu(P) values [len(ids), nnzPu] (order of P_upper_pattern()) for the listed idle QPs; nothing waits."""
+        ids = _i64(ids); Px = _f64(Px).reshape(len(ids), -1)
+        self._check_Pu(Px, len(ids))
+        _chk(lib().mi_osqp_batch_update_P_some(self._h, len(ids), _ip(ids), _dp(Px)), "update_P_some")
+
+    def update_P_A_bounds_some(self, ids, Px, Ax, l, u):
+        ids = _i64(ids); k = len(ids)
+        Px, Ax, l, u = _f64(Px).reshape(k, -1), _f64(Ax).reshape(k, -1), _f64(l).reshape(k, -1), _f64(u).reshape(k, -1)
+        self._check_Pu(Px, k)
+        _chk(lib().mi_osqp_batch_update_P_A_bounds_some(self._h, k, _ip(ids), _dp(Px), _dp(Ax), _dp(l), _dp(u)),
+             "update_P_A_bounds_some")
 
     def warm_start_x_some(self, ids, x):
         ids = _i64(ids); x = _f64(x).reshape(len(ids), -1)

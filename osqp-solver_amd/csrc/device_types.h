@@ -222,7 +222,8 @@ struct RuizArgs {
   int fresh;                                 // 1: equilibrate from the raw P and q kept since setup (rawP / rawq, [QP][nnzP], [QP][n]) instead of
   const double *rawP, *rawq;                 //    unscaling the values in force: bit for bit what setup computes for (P, q, rawA, rawl, rawu)
   const int32_t *Prow, *Pcol, *Arow, *Acol;   // per entry of triu(P) / A: row, column
-  const double *rawPnew;                     // non-null (fresh = 0): [B][nnzP] new values of triu(P) (analysis order) replace the unscaled P
+  const double *rawPnew;                     // non-null (fresh = 0): [B][nnzP] new values of triu(P) (analysis order) replace the unscaled P;
+                                             //    indexed by j whatever raw_by_qp says (fresh = 1 reads rawP: the caller writes its rows first)
   const double *rawA;                        // [B][nnzA] new values of A (natural CSC order), or null: unscale A with the E, D in force
   const double *rawl, *rawu;                 // [B][m] new bounds, or null: keep the bounds (unscale, rescale)
   double *pa_val, *q, *Dsc, *Dsc_inv, *Esc, *Esc_inv, *l, *u, *dscal;      // tile-interleaved state of the handle

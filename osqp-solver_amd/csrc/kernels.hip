@@ -3446,7 +3446,7 @@ __global__ __launch_bounds__(512) void ruiz_kernel(RuizArgs a) {
   const size_t tile = (size_t)(qp / a.BT), b = (size_t)(qp % a.BT), BT = (size_t)a.BT;
   auto H = [&](size_t len, size_t i) { return (tile * len + i) * BT + b; };
   double *dn = a.dn + (size_t)qp * n, *en = a.en + (size_t)qp * m;
-  const int jr = a.raw_by_qp ? qp : jq;          // row of the raw A / bounds arguments
+  const int jr = a.raw_by_qp ? qp : jq;          // row of the raw A / bounds arguments (rawPnew: always jq, it comes with the call)
   const double *rawA = a.rawA ? a.rawA + (size_t)jr * nnzA : nullptr;
   // (dn / en are updated by atomics, which execute in L2: they are read and reset past the CU's L1 as well)
   auto ld = [](const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
@@ -3460,7 +3460,7 @@ __global__ __launch_bounds__(512) void ruiz_kernel(RuizArgs a) {
     for (int j = tid; j < n; j += nthr) a.q[H(n, j)] = a.rawq[(size_t)qp * n + j];
   } else {
     if (a.rawPnew) {
-      for (int k = tid; k < nnzP; k += nthr) a.pa_val[H(pa_len, k)] = a.rawPnew[(size_t)jr * nnzP + k];
+      for (int k = tid; k < nnzP; k += nthr) a.pa_val[H(pa_len, k)] = a.rawPnew[(size_t)jq * nnzP + k];
     } else {
       for (int k = tid; k < nnzP; k += nthr) {
         double v = a.pa_val[H(pa_len, k)];
@@ -3590,7 +3590,7 @@ __global__ __launch_bounds__(512) void ruiz_reg_kernel(RuizArgs a) {
       const int r = a.Prow[k], cc = a.Pcol[k];
       sl = ((unsigned)r << 16) | (unsigned)cc;
       if (a.fresh) x = a.rawP[(size_t)qp * nnzP + k];
-      else if (a.rawPnew) x = a.rawPnew[(size_t)jr * nnzP + k];
+      else if (a.rawPnew) x = a.rawPnew[(size_t)jq * nnzP + k];
       else { x = a.pa_val[H(pa_len, k)]; x *= cinv0; x *= a.Dsc_inv[H(n, r)]; x *= a.Dsc_inv[H(n, cc)]; }
     } else if (k < pa_len) {
       const int r = a.Arow[k - nnzP], cc = a.Acol[k - nnzP];

@@ -2383,30 +2383,39 @@ static int update_q_impl(mi_osqp_batch *h, const double *q_host, const double *d
 
 // New values of triu(P) (and of A when Av != null): unscale with the scaling in force, replace, equilibrate again from
 // P, q and A, rescale the bounds, refactor every QP with its current rho vectors, snapshot - as mi_osqp_batch_update_A
-// does for A.  src: triu_sources() of the caller's P.
-static int update_P_impl(mi_osqp_batch *h, const std::vector<int64_t> &src, int64_t nnzPin, const double *Pv, const double *Av) {
+// does for A.  src: triu_sources() of the caller's P (null: Pv is triu(P) in the analysis's order already).
+// dP (and dA, dl, du - all three or none): the same data in HBM, [B][nnzP] in the analysis's order, [B][nnzA], [B][m]; only
+// handles that equilibrate on the device take them.  l, u: new bounds on the host, for handles that equilibrate there.
+static int update_P_impl(mi_osqp_batch *h, const std::vector<int64_t> *src, int64_t nnzPin, const double *Pv, const double *Av,
+                         const double *l = nullptr, const double *u = nullptr,
+                         const double *dP = nullptr, const double *dA = nullptr, const double *dl = nullptr, const double *du = nullptr) {
   const Analysis &an = (*h->anp);
-  const int n = an.n, B = h->B, nnzP = an.Pp[n], nnzA = an.Ap[n], pa_len = nnzP + nnzA;
+  const int n = an.n, m = an.m, B = h->B, nnzP = an.Pp[n], nnzA = an.Ap[n], pa_len = nnzP + nnzA;
   h->clear_rho_updates = true;
   int rc;
-  const size_t cP = (size_t)B * nnzP, cA = Av ? (size_t)B * nnzA : 0, cpa = (size_t)B * pa_len;
+  const size_t cP = dP ? 0 : (size_t)B * nnzP, cA = Av ? (size_t)B * nnzA : 0, cpa = (size_t)B * pa_len;      // (what is staged)
   if ((rc = ensure_pin(h, cP + cA + 1)) || (rc = ensure_stage(h, cP + cA + cpa + 1, (size_t)B))) return rc;
-  // the new triu(P) of every QP, QP-major in the analysis's order (what rawP keeps)
-  parallel_for(B, [&](int qi, int) {
-    double *dst = h->pin + (size_t)qi * nnzP;
-    const double *sv = Pv + (size_t)qi * nnzPin;
-    for (int t = 0; t < nnzP; t++) dst[t] = sv[src[t]];
-  });
-  if (Av) par_copy(h->pin + cP, Av, cA);
-  if (cP + cA) HIPCHK(hipMemcpyAsync(h->stage.p, h->pin, (cP + cA) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (cP) HIPCHK(hipMemcpyAsync(h->rawP.p, h->stage.p, cP * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  if (dP) {
+    if ((size_t)B * nnzP) HIPCHK(hipMemcpyAsync(h->rawP.p, dP, (size_t)B * nnzP * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  } else {
+    // the new triu(P) of every QP, QP-major in the analysis's order (what rawP keeps)
+    parallel_for(B, [&](int qi, int) {
+      double *dst = h->pin + (size_t)qi * nnzP;
+      const double *sv = Pv + (size_t)qi * nnzPin;
+      for (int t = 0; t < nnzP; t++) dst[t] = sv[src ? (*src)[t] : t];
+    });
+    if (Av) par_copy(h->pin + cP, Av, cA);
+    if (cP + cA) HIPCHK(hipMemcpyAsync(h->stage.p, h->pin, (cP + cA) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (cP) HIPCHK(hipMemcpyAsync(h->rawP.p, h->stage.p, cP * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  }
   std::vector<int> all(B);
   for (int i = 0; i < B; i++) all[i] = i;
   if (!host_ruiz(h)) {
     RuizArgs r{};
-    r.n = n; r.m = an.m; r.nnzP = nnzP; r.nnzA = nnzA; r.B = B; r.BT = h->BT; r.iters = (int)h->st.scaling;
+    r.n = n; r.m = m; r.nnzP = nnzP; r.nnzA = nnzA; r.B = B; r.BT = h->BT; r.iters = (int)h->st.scaling;
     r.Prow = h->rz_prow.p; r.Pcol = h->rz_pcol.p; r.Arow = h->rz_arow.p; r.Acol = h->rz_acol.p;
-    r.rawPnew = h->stage.p; r.rawA = Av ? h->stage.p + cP : nullptr; r.rawl = r.rawu = nullptr;
+    if (dP) { r.rawPnew = dP; r.rawA = dA; r.rawl = dl; r.rawu = du; }
+    else { r.rawPnew = h->stage.p; r.rawA = Av ? h->stage.p + cP : nullptr; r.rawl = r.rawu = nullptr; }
     r.pa_val = h->pa_val.p; r.q = h->q.p; r.Dsc = h->Dsc.p; r.Dsc_inv = h->Dsc_inv.p; r.Esc = h->Esc.p; r.Esc_inv = h->Esc_inv.p;
     r.l = h->l.p; r.u = h->u.p; r.dscal = h->dscal.p;
     r.dn = h->out1.p; r.en = h->out1.p + (size_t)B * n;              // (scratch of check_kernel: (2n + m) doubles per QP)
@@ -2427,9 +2436,16 @@ static int update_P_impl(mi_osqp_batch *h, const std::vector<int64_t> &src, int6
         QPNumeric &Q = h->qp[qi];
         if (h->st.scaling) unscale_qp(an, Q);
         const double *sv = Pv + (size_t)qi * nnzPin;
-        for (int t = 0; t < nnzP; t++) Q.Pv[t] = sv[src[t]];
+        for (int t = 0; t < nnzP; t++) Q.Pv[t] = sv[src ? (*src)[t] : t];
         if (Av) std::copy(Av + (size_t)qi * nnzA, Av + (size_t)(qi + 1) * nnzA, Q.Av.begin());
         if (h->st.scaling) scale_qp(an, h->st, Q);
+        if (l) {          // (as mi_osqp_batch_update_A_bounds: the new bounds under the new E)
+          for (int i = 0; i < m; i++) {
+            Q.l[i] = std::max(l[(size_t)qi * m + i], -kInfty); Q.u[i] = std::min(u[(size_t)qi * m + i], kInfty);
+            if (h->st.scaling) { Q.l[i] *= Q.E[i]; Q.u[i] *= Q.E[i]; }
+          }
+          (void)refresh_rho_types(an, Q);
+        }
       });
       std::vector<int> ids(all.begin() + c0, all.begin() + c1);
       if ((rc = upload_problem(h, ids, true)) || (rc = sync_scalars_to_device(h, ids, true))) return rc;
@@ -2447,7 +2463,7 @@ static int update_P_checked(mi_osqp_batch *h, const int64_t *Pp, const int64_t *
   std::vector<int64_t> src;
   if (!triu_sources(an, Pp, Pi, src)) return MI_OSQP_ERR_PATTERN_CHANGED;
   if (Av && !same_A_pattern(an, Ap, Ai)) return MI_OSQP_ERR_PATTERN_CHANGED;
-  return update_P_impl(h, src, Pp[an.n], Pv, Av);
+  return update_P_impl(h, &src, Pp[an.n], Pv, Av);
 }
 
 int mi_osqp_batch_update_q(mi_osqp_batch *h, const double *q) {
@@ -2477,6 +2493,65 @@ int mi_osqp_batch_update_P_A(mi_osqp_batch *h, const int64_t *Pp, const int64_t 
   CallTimer timer_("batch_update_P_A");
   if (!h || !Pp || !Pi || !Pv || !Ap || !Ai || !Av) return MI_OSQP_ERR_NULL;
   return update_P_checked(h, Pp, Pi, Pv, Ap, Ai, Av);
+}
+
+int mi_osqp_batch_get_P_upper_pattern(mi_osqp_batch *h, int64_t *colptr, int64_t *rowidx, int64_t *nnz_out) {
+  if (!h || !nnz_out) return MI_OSQP_ERR_NULL;
+  const Analysis &an = (*h->anp);
+  *nnz_out = an.Pp[an.n];
+  if (colptr) for (int j = 0; j <= an.n; j++) colptr[j] = an.Pp[j];
+  if (rowidx) for (int k = 0; k < an.Pp[an.n]; k++) rowidx[k] = an.Pi[k];
+  return MI_OSQP_OK;
+}
+
+// osqp_update_P (+ QPSolver::update) with the new values in HBM: triu(P) [B][nnzPu] in the analysis's order - the layout of
+// the adjoint's dP - and optionally A [B][nnzA] and the bounds [B][m].  One equilibration, one refactorisation, one snapshot.
+static int update_P_device_impl(mi_osqp_batch *h, const double *d_Pv, const double *d_Av, const double *d_l, const double *d_u, hipStream_t s) {
+  DevGuard guard(h->device);
+  { const int rc_ = cont_leave(h); if (rc_) return rc_; }
+  const Analysis &an = (*h->anp);
+  const int m = an.m, B = h->B, nnzP = an.Pp[an.n], nnzA = an.Ap[an.n];
+  if (host_ruiz(h)) {            // equilibrated on host threads, so the values come down first (as mi_osqp_batch_update_A_bounds_device)
+    std::vector<double> hP((size_t)B * nnzP), hA, hl, hu;
+    HIPCHK(hipStreamSynchronize(s));
+    if (!hP.empty()) HIPCHK(hipMemcpy(hP.data(), d_Pv, hP.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (d_Av) {
+      hA.resize((size_t)B * nnzA); hl.resize((size_t)B * m); hu.resize((size_t)B * m);
+      if (!hA.empty()) HIPCHK(hipMemcpy(hA.data(), d_Av, hA.size() * sizeof(double), hipMemcpyDeviceToHost));
+      if (m) {
+        HIPCHK(hipMemcpy(hl.data(), d_l, hl.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hu.data(), d_u, hu.size() * sizeof(double), hipMemcpyDeviceToHost));
+      }
+      for (size_t k = 0; k < hl.size(); k++) if (hl[k] > hu[k]) return MI_OSQP_ERR_INVALID_DATA;
+    }
+    return update_P_impl(h, nullptr, nnzP, hP.data(), d_Av ? hA.data() : nullptr, d_Av ? hl.data() : nullptr, d_Av ? hu.data() : nullptr);
+  }
+  if (d_Av && m) {               // l <= u, checked without writing (pass 1 of the bounds update)
+    HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), s));
+    HIPCHK(launch_bounds(d_l, d_u, h->out1.p, h->out2.p, h->Esc.p, h->rho_vec.p, h->dscal.p, h->flag.p, B, m, h->BT, h->st.scaling ? 1 : 0, s));
+    int flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (flag & 2) return MI_OSQP_ERR_INVALID_DATA;
+  } else HIPCHK(hipStreamSynchronize(s));
+  return update_P_impl(h, nullptr, nnzP, nullptr, nullptr, nullptr, nullptr, d_Pv, d_Av, d_l, d_u);
+}
+
+int mi_osqp_batch_update_P_device(mi_osqp_batch *h, const double *d_Pv, void *stream) {
+  CallTimer timer_("batch_update_P_device");
+  if (!h || !d_Pv) return MI_OSQP_ERR_NULL;
+  return update_P_device_impl(h, d_Pv, nullptr, nullptr, nullptr, stream ? (hipStream_t)stream : h->stream);
+}
+
+int mi_osqp_batch_update_P_A_bounds_device(mi_osqp_batch *h, const double *d_Pv, const double *d_Av, const double *d_l, const double *d_u,
+                                           void *stream) {
+  if (!h) return MI_OSQP_ERR_NULL;
+  const int given = (d_Av ? 1 : 0) + (d_l ? 1 : 0) + (d_u ? 1 : 0);
+  if (given != 0 && given != 3) return MI_OSQP_ERR_NULL;           // (A and the bounds come together or not at all)
+  if (!d_Pv) return given ? mi_osqp_batch_update_A_bounds_device(h, d_Av, d_l, d_u, stream) : MI_OSQP_ERR_NULL;
+  if (!given) return mi_osqp_batch_update_P_device(h, d_Pv, stream);
+  CallTimer timer_("batch_update_P_A_bounds_device");
+  return update_P_device_impl(h, d_Pv, d_Av, d_l, d_u, stream ? (hipStream_t)stream : h->stream);
 }
 
 int mi_osqp_batch_warm_start_y(mi_osqp_batch *h, const double *y) {
@@ -2791,29 +2866,37 @@ static int enqueue_refactor_list(mi_osqp_batch *h, const int *d_work, int count,
 // new A values + bounds of the listed QPs: equilibration on the device (fresh: from the raw P and q of setup; else unscale
 // with the scaling in force first, as QPSolver::update does), check streams, refactorisation, snapshot.  All enqueued.
 // (dA / dl / du non-null: the new data is on the device already, [B][nnzA] / [B][m] by QP number - the GOMP scene's kept rows)
+// Pv non-null (fresh = false): new values of triu(P) as well, [n_ids][nnzP] in the analysis's order; the rawP rows of the
+// listed QPs take them before the equilibration (a later reinit_some starts from them).  Av, l, u may then be null: A and the
+// bounds stay (unscaled and rescaled), as in mi_osqp_batch_update_P.
 static int cont_new_data(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *Av, const double *l, const double *u, bool fresh,
-                         const double *dA = nullptr, const double *dl = nullptr, const double *du = nullptr) {
+                         const double *dA = nullptr, const double *dl = nullptr, const double *du = nullptr, const double *Pv = nullptr) {
   const Analysis &an = (*h->anp);
   const int n = an.n, m = an.m, nnzP = an.Pp[n], nnzA = an.Ap[n], pa_len = nnzP + nnzA, nq = (int)n_ids;
   int rc;
-  if (!dA) for (size_t k = 0; k < (size_t)nq * m; k++) if (l[k] > u[k]) return MI_OSQP_ERR_INVALID_DATA;
+  const bool hostA = !dA && Av;
+  if (hostA) for (size_t k = 0; k < (size_t)nq * m; k++) if (l[k] > u[k]) return MI_OSQP_ERR_INVALID_DATA;
   int *d_ids = nullptr;
-  const size_t cA = (size_t)nq * nnzA, cb = (size_t)nq * m, cpa = (size_t)nq * pa_len;
-  if ((rc = ring_reserve(h, (size_t)nq * sizeof(int) + (dA ? 0 : (cA + 2 * cb) * sizeof(double)) + std::max<size_t>(cpa, 1) * sizeof(double), 3))) return rc;
+  const size_t cP = Pv ? (size_t)nq * nnzP : 0, cA = hostA ? (size_t)nq * nnzA : 0, cb = hostA ? (size_t)nq * m : 0, cpa = (size_t)nq * pa_len;
+  const size_t cin = cP + cA + 2 * cb;          // one span: [P | A | l | u] rows of the call
+  // (the whole call from one lap of the ring: ids, the rows in, the scaled values out)
+  if ((rc = ring_reserve(h, (size_t)nq * sizeof(int) + cin * sizeof(double) + std::max<size_t>(cpa, 1) * sizeof(double), 3))) return rc;
   if ((rc = cont_stage_ids(h, n_ids, ids, &d_ids, nullptr))) return rc;
   RingSpan in{nullptr, nullptr}, out;
-  if (!dA && (rc = ring_take(h, (cA + 2 * cb) * sizeof(double), in))) return rc;
+  if (cin && (rc = ring_take(h, cin * sizeof(double), in))) return rc;
   if ((rc = ring_take(h, std::max<size_t>(cpa, 1) * sizeof(double), out))) return rc;
   double *hin = (double *)in.host, *din = (double *)in.dev;
-  if (!dA) {
-    memcpy(hin, Av, cA * sizeof(double)); memcpy(hin + cA, l, cb * sizeof(double)); memcpy(hin + cA + cb, u, cb * sizeof(double));
-    if ((rc = ring_upload(h, in, (cA + 2 * cb) * sizeof(double)))) return rc;
+  if (cin) {
+    if (Pv) memcpy(hin, Pv, cP * sizeof(double));
+    if (hostA) { memcpy(hin + cP, Av, cA * sizeof(double)); memcpy(hin + cP + cA, l, cb * sizeof(double)); memcpy(hin + cP + cA + cb, u, cb * sizeof(double)); }
+    if ((rc = ring_upload(h, in, cin * sizeof(double)))) return rc;
   }
   hipStream_t us = h->stream;
-  if (!dA && h->cont.keepA) {
-    HIPCHK(launch_keep_rows(h->cont.keepA, din, d_ids, nq, nnzA, us));
-    HIPCHK(launch_keep_rows(h->cont.keepl, din + cA, d_ids, nq, m, us));
-    HIPCHK(launch_keep_rows(h->cont.keepu, din + cA + cb, d_ids, nq, m, us));
+  if (Pv) HIPCHK(launch_keep_rows(h->rawP.p, din, d_ids, nq, nnzP, us));
+  if (hostA && h->cont.keepA) {
+    HIPCHK(launch_keep_rows(h->cont.keepA, din + cP, d_ids, nq, nnzA, us));
+    HIPCHK(launch_keep_rows(h->cont.keepl, din + cP + cA, d_ids, nq, m, us));
+    HIPCHK(launch_keep_rows(h->cont.keepu, din + cP + cA + cb, d_ids, nq, m, us));
   }
   KernelArgs ka = make_args(h);
   if (fresh) HIPCHK(launch_fresh_slots(ka, d_ids, nq, h->BT, h->st.rho, us));
@@ -2821,8 +2904,9 @@ static int cont_new_data(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, co
   r.n = n; r.m = m; r.nnzP = nnzP; r.nnzA = nnzA; r.B = nq; r.BT = h->BT; r.iters = (int)h->st.scaling;
   r.ids = d_ids; r.fresh = fresh ? 1 : 0; r.rawP = h->rawP.p; r.rawq = h->rawq.p;
   r.Prow = h->rz_prow.p; r.Pcol = h->rz_pcol.p; r.Arow = h->rz_arow.p; r.Acol = h->rz_acol.p;
+  if (Pv && !fresh) r.rawPnew = din;             // (row = position in the list, like every argument that comes with the call)
   if (dA) { r.rawA = dA; r.rawl = dl; r.rawu = du; r.raw_by_qp = 1; }
-  else { r.rawA = din; r.rawl = din + cA; r.rawu = din + cA + cb; }
+  else if (hostA) { r.rawA = din + cP; r.rawl = din + cP + cA; r.rawu = din + cP + cA + cb; }
   r.pa_val = h->pa_val.p; r.q = h->q.p; r.Dsc = h->Dsc.p; r.Dsc_inv = h->Dsc_inv.p; r.Esc = h->Esc.p; r.Esc_inv = h->Esc_inv.p;
   r.l = h->l.p; r.u = h->u.p; r.dscal = h->dscal.p;
   r.dn = h->cont.rz_scratch.p; r.en = h->cont.rz_scratch.p + (size_t)h->B * n;        // (not the check kernels' scratch: they may be running)
@@ -2834,6 +2918,15 @@ static int cont_new_data(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, co
   for (int64_t j = 0; j < n_ids; j++) { h->cont.clear_rho[(size_t)ids[j]] = 1; h->failed[(size_t)ids[j]] = 0; h->cont.polishable[(size_t)ids[j]] = 0; }
   if (fresh) for (int64_t j = 0; j < n_ids; j++) h->cont.cert_status[(size_t)ids[j]] = 0;      // (a new QP in the slot: it has not finished a solve)
   h->host_scaling_stale = true; h->host_bounds_stale = true; h->host_rho_stale = true;
+  return MI_OSQP_OK;
+}
+// the listed ids once each (the per-QP P updates: two rows for one QP have no defined winner in rawP)
+static int cont_check_unique(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids) {
+  std::vector<char> seen((size_t)h->B, 0);
+  for (int64_t j = 0; j < n_ids; j++) {
+    if (seen[(size_t)ids[j]]) { g_last_error = "QP " + std::to_string(ids[j]) + " is listed twice"; return MI_OSQP_ERR_INVALID_DATA; }
+    seen[(size_t)ids[j]] = 1;
+  }
   return MI_OSQP_OK;
 }
 
@@ -2857,6 +2950,29 @@ int mi_osqp_batch_update_A_bounds_some(mi_osqp_batch *h, int64_t n_ids, const in
   if ((rc = cont_enter(h)) || (rc = cont_check_ids(h, n_ids, ids, true))) return rc;
   if (!n_ids) return MI_OSQP_OK;
   return cont_new_data(h, n_ids, ids, Av, l, u, false);
+}
+
+// osqp_update_P (and QPSolver::update) for the listed (idle) QPs: ring upload, the rawP rows, equilibration, refactorisation
+// and snapshot of those QPs; nothing waits
+int mi_osqp_batch_update_P_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *Pv) {
+  CallTimer timer_("batch_update_P_some");
+  if (!h || (n_ids > 0 && !Pv)) return MI_OSQP_ERR_NULL;
+  DevGuard guard(h->device);
+  int rc;
+  if ((rc = cont_enter(h)) || (rc = cont_check_ids(h, n_ids, ids, true)) || (rc = cont_check_unique(h, n_ids, ids))) return rc;
+  if (!n_ids) return MI_OSQP_OK;
+  return cont_new_data(h, n_ids, ids, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, Pv);
+}
+
+int mi_osqp_batch_update_P_A_bounds_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *Pv, const double *Av,
+                                         const double *l, const double *u) {
+  CallTimer timer_("batch_update_P_A_bounds_some");
+  if (!h || (n_ids > 0 && (!Pv || !Av || !l || !u))) return MI_OSQP_ERR_NULL;
+  DevGuard guard(h->device);
+  int rc;
+  if ((rc = cont_enter(h)) || (rc = cont_check_ids(h, n_ids, ids, true)) || (rc = cont_check_unique(h, n_ids, ids))) return rc;
+  if (!n_ids) return MI_OSQP_OK;
+  return cont_new_data(h, n_ids, ids, Av, l, u, false, nullptr, nullptr, nullptr, Pv);
 }
 
 int mi_osqp_batch_warm_start_x_some(mi_osqp_batch *h, int64_t n_ids, const int64_t *ids, const double *x) {
