@@ -113,6 +113,7 @@ typedef struct {
   int64_t pipelined_refactors;   /* rho-update points since setup whose refactorisation ran in chunks, overlapped with the iterate segment behind it */
   int64_t resident_factor_steps, lds_bytes_factor;   /* resident head of S^-1: 512 B steps of the dense-tail stream every wave of a tile keeps in registers and LDS across a segment (0 = streamed); LDS of its part, which the iterate launches take on top of lds_bytes_iterate */
   int64_t dense_tail_tasks, dense_tail_waves_used, dense_tail_wave_tasks_max;   /* deal of the dense-tail product: 64 x 64 block tasks, waves of a tile that own at least one, most tasks of one wave */
+  int64_t refactor_lanes;   /* the most chunk lanes a pipelined rho-update point has run on since setup: streams that each run factor -> tail -> iterate of their chunks (1 = one refactorisation stream and one iterate stream; 0 = none pipelined yet) */
 } mi_osqp_stats;
 
 typedef struct mi_osqp_solver mi_osqp_solver; /* one QP  */
@@ -630,6 +631,18 @@ int mi_osqp_debug_host_block_factor(int64_t n, int64_t m,
 int mi_osqp_debug_refactor_chunks(int64_t n_flagged, const int64_t *flagged, int64_t n_active, const int64_t *active, int64_t tile,
                                   int64_t chunk_qps, int64_t max_chunks, int64_t *n_chunks, int64_t *work_begin, int64_t *tiles,
                                   int64_t *tile_begin);
+
+/* Host only: the chunk lanes of those chunks (MI_OSQP_REFACTOR_LANES; solver.hip "pipelined refactorisation").  kbt = slots
+ * per workgroup of the refactorisation kernels, lanes = 1 .. 3, chunk0_first = chunk 0 in front of the last lane instead of
+ * behind the shortest one, scratch_slots = slots the refactorisation scratch holds (too few: one lane).  Out: *n_lanes,
+ * lane_of[n_chunks], order[n_chunks] (the chunks lane after lane in launch order) with order_begin[n_lanes + 1],
+ * scratch_begin[n_chunks] (first scratch slot of every chunk) and *n_waits pairs: the iterate of chunk wait_chunk[i] waits
+ * for the tail of chunk wait_for[i] on another lane.  Per-chunk arrays hold max_chunks + 2 entries, order_begin 4, the
+ * wait arrays (max_chunks + 1)^2. */
+int mi_osqp_debug_refactor_lanes(int64_t n_flagged, const int64_t *flagged, int64_t n_active, const int64_t *active, int64_t tile,
+                                 int64_t chunk_qps, int64_t max_chunks, int64_t kbt, int64_t lanes, int64_t chunk0_first,
+                                 int64_t scratch_slots, int64_t *n_lanes, int64_t *lane_of, int64_t *order, int64_t *order_begin,
+                                 int64_t *scratch_begin, int64_t *n_waits, int64_t *wait_chunk, int64_t *wait_for);
 
 /* Device diagnostics (tile 2, LDS mode only): one KKT solve of the whole batch with
  * per-phase / per-wave shader-clock stamps of two tiles (first, middle).

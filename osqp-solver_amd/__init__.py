@@ -60,7 +60,8 @@ class Stats(C.Structure):
                [("nnz_L_before_tail", C.c_int64), ("solve_groups", C.c_int64), ("solve_group_threads", C.c_int64),
                 ("resident_state", C.c_int64), ("lds_bytes_iterate", C.c_int64), ("pipelined_refactors", C.c_int64),
                 ("resident_factor_steps", C.c_int64), ("lds_bytes_factor", C.c_int64),
-                ("dense_tail_tasks", C.c_int64), ("dense_tail_waves_used", C.c_int64), ("dense_tail_wave_tasks_max", C.c_int64)]
+                ("dense_tail_tasks", C.c_int64), ("dense_tail_waves_used", C.c_int64), ("dense_tail_wave_tasks_max", C.c_int64),
+                ("refactor_lanes", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -199,6 +200,7 @@ def lib():
         L.mi_osqp_debug_host_kkt_solve.argtypes = [C.c_int64, C.c_int64, ip, ip, dp, ip, ip, dp, dp, dp,
                                                    C.POINTER(Settings), C.c_int64, dp, dp, dp, C.POINTER(Stats)]
         L.mi_osqp_debug_refactor_chunks.argtypes = [C.c_int64, ip, C.c_int64, ip, C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip]
+        L.mi_osqp_debug_refactor_lanes.argtypes = [C.c_int64, ip, C.c_int64, ip] + [C.c_int64] * 7 + [ip] * 8
         L.mi_osqp_prefetch_analysis.argtypes = [C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip, C.c_int64]
         L.mi_osqp_debug_host_block_factor.argtypes = [C.c_int64, C.c_int64, ip, ip, dp, ip, ip, dp, dp, dp,
                                                       C.POINTER(Settings), dp, dp, ip]
@@ -907,6 +909,28 @@ def debug_refactor_chunks(flagged, active, tile, chunk_qps, max_chunks=8):
                                              _ip(tb)), "debug_refactor_chunks")
     k = int(nch.value)
     return ([f[wb[c]:wb[c + 1]].tolist() for c in range(k)], [tl[tb[c]:tb[c + 1]].tolist() for c in range(k)])
+
+
+def debug_refactor_lanes(flagged, active, tile, chunk_qps, lanes, kbt=None, chunk0_first=False, scratch_slots=None, max_chunks=8):
+    """Host-only: the chunk lanes of a pipelined refactorisation (the chunks are those of debug_refactor_chunks).  kbt: slots
+    per workgroup of the refactorisation kernels (default: tile); scratch_slots: what the scratch buffers hold (default: no
+    limit).  Returns a dict: n_lanes, lane_of (per chunk), order (per lane, its chunks in launch order), scratch (per chunk:
+    (first slot, slots) of its scratch), waits (pairs (c, d): the iterate of chunk c waits for the tail of chunk d, another lane)."""
+    f, a = _i64(flagged), _i64(active)
+    kbt = tile if kbt is None else kbt
+    work, _ = debug_refactor_chunks(flagged, active, tile, chunk_qps, max_chunks)
+    k = len(work)
+    nl, nw = C.c_int64(), C.c_int64()
+    lane_of = np.zeros(max_chunks + 2, dtype=np.int64); order = np.zeros(max_chunks + 2, dtype=np.int64)
+    ob = np.zeros(4, dtype=np.int64); sb = np.zeros(max_chunks + 2, dtype=np.int64)
+    wc = np.zeros((max_chunks + 1) ** 2, dtype=np.int64); wf = np.zeros((max_chunks + 1) ** 2, dtype=np.int64)
+    _chk(lib().mi_osqp_debug_refactor_lanes(len(f), _ip(f), len(a), _ip(a), tile, chunk_qps, max_chunks, kbt, lanes, int(bool(chunk0_first)),
+                                            2 ** 31 - 1 if scratch_slots is None else scratch_slots, C.byref(nl), _ip(lane_of), _ip(order),
+                                            _ip(ob), _ip(sb), C.byref(nw), _ip(wc), _ip(wf)), "debug_refactor_lanes")
+    L = int(nl.value)
+    return dict(n_lanes=L, lane_of=lane_of[:k].tolist(), order=[order[ob[l]:ob[l + 1]].tolist() for l in range(L)],
+                scratch=[(int(sb[c]), (len(work[c]) + kbt - 1) // kbt * kbt) for c in range(k)],
+                waits=list(zip(wc[:nw.value].tolist(), wf[:nw.value].tolist())))
 
 
 def debug_host_block_factor(P, A, l, u, **settings):

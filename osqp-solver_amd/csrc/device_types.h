@@ -103,6 +103,9 @@ struct FactorArgs {
   int home_bt;        // QPs per tile of the per-QP arrays ([tile][len][home_bt]); the kernel's own BT (QPs per workgroup) may differ
   const int *work;    // non-null: work list of the slots (tile * BT + b) to refactor, packed BT per work tile, -1 = none;
                       // null: every slot of the batch (force_all) / the slots whose IS_NEED_REFACTOR flag is set
+  int wg_base;        // work tiles in front of this launch's in the whole list: workgroup j reads work[] at j and keeps its block storage /
+                      // D scratch at j + wg_base, so launches of one list that run side by side (chunk lanes, solver.hip) never share any;
+                      // 0 = a launch over the whole list
   double sigma;
   int dt_k;           // rows of the dense tail: their pivots are counted by dense_inverse_kernel, which then checks the inertia
   // the ONE QP of a handle shared by mw_groups workgroups (single large QPs; grid barriers between the phases of a level)
@@ -127,6 +130,7 @@ struct TailArgs {
   int nh;                       // row tiles of one staged half of the panel
   uint32_t cs_doubles;          // LDS doubles reserved for the staged panel / the pivot block's image (Ps follows)
   const int *work;              // slot of every (work tile, lane class), -1 = none
+  int wg_base;                  // as FactorArgs::wg_base, in entries of work[] (a multiple of kbt): the scratch (Lblk, Dl, Sd) of workgroup j is that of j + wg_base
   const uint32_t *lt_pos, *ltcol_col, *tile_tab, *wave_tiles, *diag_tile;
   const uint64_t *asm_q64;
   const int32_t *src_tile;      // per stream slot: tile-order offset in the scratch, MI_SRC_ZERO = 0 (host replay; unused by the kernel)
@@ -287,6 +291,8 @@ struct GompArgs {
 hipError_t launch_gomp_relinearise(const GompArgs &g, hipStream_t st);
 hipError_t launch_gather_status(const int *iscal, int32_t *status, int32_t *iters, int B, int BT, hipStream_t st);
 hipError_t launch_fail_slots(const KernelArgs &a, const int *slots, int nfail, int BT, int iter, hipStream_t st);
+// the same for every listed slot (slots[j] < 0: none) whose new factor lost its inertia (IS_NEED_REFACTOR < 0), decided on the device
+hipError_t launch_fail_flagged(const KernelArgs &a, const int *slots, int nslots, int BT, int iter, hipStream_t st);
 hipError_t launch_bounds(const double *gl, const double *gu, double *l, double *u, const double *Esc,
                          const double *rho_vec, const double *dscal, int *changed, int B, int m, int BT,
                          int scaling, hipStream_t st);

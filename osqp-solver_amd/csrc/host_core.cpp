@@ -1039,6 +1039,8 @@ Tuning tuning_from_env() {
   if (const char *e = getenv("MI_OSQP_REFACTOR_PIPELINE_MIN")) t.pipeline_min = std::max(0, atoi(e));
   if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNKS")) t.pipeline_chunks = std::max(0, std::min(8, atoi(e)));
   if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNK_QPS")) t.pipeline_chunk_qps = std::max(0, atoi(e));
+  if (const char *e = getenv("MI_OSQP_REFACTOR_LANES")) t.refactor_lanes = std::max(1, std::min(3, atoi(e)));
+  if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNK0")) t.lanes_chunk0 = atoi(e) != 0;
   AnalysisTuning &a = t.analysis;
   if (const char *e = getenv("MI_OSQP_DENSE_TAIL")) a.dense_tail = atoi(e);
   if (const char *e = getenv("MI_OSQP_ORDERING")) a.ordering = e[0];
@@ -1074,6 +1076,45 @@ RefactorChunks refactor_chunks(const std::vector<int> &flagged, const std::vecto
   for (const auto &p : tc) { rc.tiles.push_back(p.second); rc.tile_begin[(size_t)p.first + 1]++; }
   for (int c = 0; c < rc.n_chunks; c++) rc.tile_begin[(size_t)c + 1] += rc.tile_begin[c];
   return rc;
+}
+
+RefactorLanes refactor_lanes(const RefactorChunks &ch, const std::vector<int> &flagged, int bt, int kbt, int lanes, bool chunk0_first, int scratch_slots) {
+  RefactorLanes rl;
+  const int nc = ch.n_chunks, n_ref = nc - 1;
+  bt = std::max(1, bt); kbt = std::max(1, kbt);
+  int L = std::max(1, std::min(std::min(3, lanes), std::max(1, n_ref)));
+  std::vector<int> padded((size_t)nc + 1, 0);
+  for (int c = 1; c < nc; c++) padded[(size_t)c + 1] = padded[c] + (ch.work_begin[(size_t)c + 1] - ch.work_begin[c] + kbt - 1) / kbt * kbt;
+  if (padded[nc] > scratch_slots) L = 1;
+  rl.n_lanes = L;
+  rl.lane_of.assign(nc, 0);
+  rl.order.assign(L, std::vector<int>());
+  rl.scratch_begin.assign((size_t)nc + 1, 0);
+  if (L == 1) {
+    for (int c = 0; c < nc; c++) rl.order[0].push_back(c);
+    return rl;
+  }
+  rl.scratch_begin = padded;
+  for (int c = 1; c < nc; c++) { rl.lane_of[c] = (c - 1) % L; rl.order[(c - 1) % L].push_back(c); }
+  if (chunk0_first) { rl.lane_of[0] = L - 1; rl.order[L - 1].insert(rl.order[L - 1].begin(), 0); }
+  else {
+    int at = L - 1;           // the last of the shortest lanes
+    for (int a = L - 1; a >= 0; a--) if (rl.order[a].size() < rl.order[at].size()) at = a;
+    rl.lane_of[0] = at; rl.order[at].push_back(0);
+  }
+  for (int c = 1; c < nc; c++) {
+    std::vector<char> need(nc, 0);
+    for (int t = ch.tile_begin[c]; t < ch.tile_begin[(size_t)c + 1]; t++) {
+      const int tile = ch.tiles[t];
+      size_t g = std::lower_bound(flagged.begin(), flagged.end(), tile * bt) - flagged.begin();
+      for (; g < flagged.size() && flagged[g] / bt == tile; g++) {
+        const int d = (int)(std::upper_bound(ch.work_begin.begin() + 1, ch.work_begin.end(), (int)g) - ch.work_begin.begin()) - 1;
+        if (d >= 1 && d < c && rl.lane_of[d] != rl.lane_of[c]) need[d] = 1;
+      }
+    }
+    for (int d = 1; d < c; d++) if (need[d]) { rl.wait_chunk.push_back(c); rl.wait_for.push_back(d); }
+  }
+  return rl;
 }
 
 // --------------------------------------------------------------------- analyze

@@ -65,6 +65,8 @@ struct Tuning {
   int pipeline_chunks = 0;         // MI_OSQP_REFACTOR_CHUNKS: k > 0 even chunks of the work list (1 .. 8)
   int pipeline_chunk_qps = 0;      // MI_OSQP_REFACTOR_CHUNK_QPS: chunks of so many QPs, the last one shorter (when pipeline_chunks == 0)
                                    // both 0 (the measured default): the fewest even chunks of at most one QP per CU - 3 x 202 for 605 QPs
+  int refactor_lanes = 0;          // MI_OSQP_REFACTOR_LANES: 1 .. 3 chunk lanes (refactor_lanes below); 1 = the two-stream form; 0 = the default
+  int lanes_chunk0 = -1;           // MI_OSQP_REFACTOR_CHUNK0: 1 chunk 0 in front of the last lane, 0 behind the shortest lane; -1 = the default
   AnalysisTuning analysis;
 };
 Tuning tuning_from_env();
@@ -82,6 +84,24 @@ struct RefactorChunks {
   std::vector<int> tile_begin;     // n_chunks + 1: chunk c iterates tiles[tile_begin[c] .. tile_begin[c + 1])
 };
 RefactorChunks refactor_chunks(const std::vector<int> &flagged, const std::vector<int> &active, int bt, int chunk_qps, int max_chunks);
+
+// Chunk lanes of a pipelined refactorisation: a lane is a stream that runs the chain factor -> tail -> iterate of its chunks one
+// after the other.  Chunk c >= 1 goes to lane (c - 1) % n_lanes; chunk 0 (tiles without a flagged slot: an iterate only) goes
+// behind the last chunk of the shortest lane (chunk0_first = false) or in front of the last lane (true).  One lane is the
+// two-stream form: every refactorisation on one stream in order, every iterate on a second one in order, chunk 0 first.
+// A tile's iterate needs the factor of every flagged slot of the tile; those sit in consecutive chunks, and the ones on
+// another lane than the tile's own chunk are the cross-lane waits.  kbt = slots per workgroup of the refactorisation kernels:
+// every chunk's part of the work list is padded to whole workgroups, and scratch_begin is where it starts in the padded list -
+// chunks that may run side by side keep their scratch there.  When the padded list is longer than scratch_slots (what the
+// scratch buffers hold), the lanes fall back to one and every chunk's scratch begins at 0, re-used in stream order.
+struct RefactorLanes {
+  int n_lanes = 1;
+  std::vector<int> lane_of;                     // n_chunks: lane of every chunk
+  std::vector<std::vector<int>> order;          // per lane: its chunks in launch order
+  std::vector<int> scratch_begin;               // n_chunks + 1: first slot of chunk c in the padded work list (0 throughout after the fall-back)
+  std::vector<int> wait_chunk, wait_for;        // pairs: the iterate of chunk wait_chunk[i] waits for the tail of chunk wait_for[i] (another lane)
+};
+RefactorLanes refactor_lanes(const RefactorChunks &ch, const std::vector<int> &flagged, int bt, int kbt, int lanes, bool chunk0_first, int scratch_slots);
 
 // One pull-schedule: every target row t gets  xs[t] -= sum_k val[k] * xs[idx[k]]  (or xs[t] = sum, "store").
 //

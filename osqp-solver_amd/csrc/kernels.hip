@@ -2472,8 +2472,9 @@ __global__ __launch_bounds__(1024) void factor_kernel(FactorArgs a) {
   double *Ss = smem + (size_t)(threadIdx.x >> 6) * MI_CHUNK * MI_CHUNK * BT;
   double *lds_rest = smem + (size_t)(blockDim.x >> 6) * MI_CHUNK * MI_CHUNK * BT;
   double *Lb, *Dl;
+  const size_t stile = (size_t)tile + (size_t)a.wg_base;      // where this work tile keeps its scratch (FactorArgs::wg_base)
   if constexpr (LBL) { Lb = lds_rest; Dl = lds_rest + (size_t)a.storage * BT; }
-  else { Lb = a.Lblk + (size_t)tile * a.storage * BT; Dl = a.Dl + (size_t)tile * N * BT; }
+  else { Lb = a.Lblk + stile * a.storage * BT; Dl = a.Dl + stile * N * BT; }
   const double rho = a.dscal[H(DS_COUNT, DS_RHO)];
   // ---- rho vector of the QPs being refactored ([EXT] osqp_update_rho); not for a polish factor
   if (flag && !a.force_all && !a.pmask) {
@@ -2530,7 +2531,7 @@ __global__ __launch_bounds__(1024) void factor_kernel(FactorArgs a) {
   int npos = 0, bad_inertia = 0;
   double *dnew;
   if constexpr (LBL) dnew = lds_rest + ((size_t)a.storage + (size_t)N) * BT;
-  else dnew = a.dinv_scratch + (size_t)tile * N * BT;
+  else dnew = a.dinv_scratch + stile * N * BT;
   for (int L = 0; L < a.n_levels; L++) {
     const uint32_t *lv = a.lvl + 6 * L;
     // (task descriptors: one 16-byte load each, requested one task ahead - a lone QP is a chain of dependent memory round
@@ -2734,8 +2735,8 @@ __global__ __launch_bounds__(1024) void tail_assemble_kernel(TailArgs a) {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int slot = a.work[g];
   if (slot < 0) return;
-  const int k = a.k, kbt = a.kbt, wt = g / kbt, wb = g % kbt;
-  double *A = a.Sd + (size_t)g * k * k;
+  const int k = a.k, kbt = a.kbt, gs = g + a.wg_base, wt = gs / kbt, wb = gs % kbt;      // gs: whose scratch (TailArgs::wg_base)
+  double *A = a.Sd + (size_t)gs * k * k;
   const double *Lb = a.Lblk + (size_t)wt * a.storage * kbt + wb;
   const double *Dl = a.Dl + (size_t)wt * a.N * kbt + wb;
   const int l15 = lane & 15, l4 = lane >> 4;
@@ -2818,10 +2819,10 @@ __global__ __launch_bounds__(512) void tail_kernel(TailArgs a) {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int slot = a.work[g];
   if (slot < 0) return;
-  const int k = a.k, kbt = a.kbt, wt = g / kbt, wb = g % kbt, nt = k / 16;
+  const int k = a.k, kbt = a.kbt, gs = g + a.wg_base, wt = gs / kbt, wb = gs % kbt, nt = k / 16;
   const size_t hbt = (size_t)a.home_bt, home = (size_t)slot / hbt, hb = (size_t)slot % hbt;
   auto H = [&](size_t len, size_t i) { return (home * len + i) * hbt + hb; };
-  double *A = a.Sd + (size_t)g * k * k;                     // the tiles tail_assemble_kernel left here
+  double *A = a.Sd + (size_t)gs * k * k;                    // the tiles tail_assemble_kernel left here
   (void)wt; (void)wb;
   const int l15 = lane & 15, l4 = lane >> 4;
   // timing stamps of wave 0 (MI_OSQP_TAIL_TRACE=1: a.trace != null; results are not affected): assembly, pivot blocks,
@@ -3215,6 +3216,22 @@ __device__ __forceinline__ void fail_one_slot(const KernelArgs &a, int slot, int
     double *ds = a.dscal + tile * DS_COUNT * BT;
     ds[DS_OBJ * BT + b] = nanv; ds[DS_PRI_RES * BT + b] = nanv; ds[DS_DUA_RES * BT + b] = nanv;
   }
+}
+// fail_slots_kernel behind a refactorisation whose flags the host has not read: one workgroup per slot of its work list, of
+// which those whose new factor lost its inertia (IS_NEED_REFACTOR < 0) fail.  The flag goes back to 0, the status tells the host.
+__global__ void fail_flagged_kernel(KernelArgs a, const int *__restrict__ slots, int BT, int iter) {
+  const int slot = slots[blockIdx.x];
+  if (slot < 0) return;
+  int *flag = a.iscal + ((size_t)slot / BT) * IS_COUNT * BT + IS_NEED_REFACTOR * BT + (size_t)slot % BT;
+  if (*flag >= 0) return;
+  fail_one_slot(a, slot, BT, iter, threadIdx.x, blockDim.x);
+  __syncthreads();            // (every thread has read the flag)
+  if (threadIdx.x == 0) *flag = 0;
+}
+hipError_t launch_fail_flagged(const KernelArgs &a, const int *slots, int nslots, int BT, int iter, hipStream_t st) {
+  if (nslots <= 0) return hipSuccess;
+  hipLaunchKernelGGL(fail_flagged_kernel, dim3(nslots), dim3(256), 0, st, a, slots, BT, iter);
+  return hipGetLastError();
 }
 // Solve() entry of the listed QPs ([EXT] osqp_solve: status unsolved, iteration count 0; warm_start off: cold iterates).
 // A QP without a valid factor (the last refactorisation of its KKT matrix lost the inertia) ends at once as kNonConvex.

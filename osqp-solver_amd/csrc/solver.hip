@@ -152,8 +152,8 @@ static void release_all() {
 
 // The same for pinned host memory and for streams + events: hipHostMalloc costs ~0.5 ms per call and a handle needs four
 // of them, a stream and five events - 2-3 ms of a 4 ms setup for the small QPs of a sequential GOMP run.
-// (pipe_r / pipe_i / pipe_ev: the two streams and the events of a pipelined refactorisation, created by the first handle that
-//  needs them and handed on with the bundle; null until then)
+// (pipe_r / pipe_i / pipe_x / pipe_ev: the streams and the events of a pipelined refactorisation, created by the first handle
+//  that needs them and handed on with the bundle; null until then)
 namespace hostpool {
 static std::mutex mu;
 static std::multimap<size_t, void *> blocks;          // capacity in bytes -> pinned pointer
@@ -190,12 +190,13 @@ static hipError_t alloc(void **p, size_t bytes, size_t *cap) {
 }  // namespace hostpool
 namespace streampool {
 constexpr int kPipeChunks = 8;                      // refactorisation chunks of a pipelined region, at most
-constexpr int kPipeEvents = 3 + 3 * kPipeChunks;    // fork, begin / end of the iterate stream, then (begin, factor done, tail done) per chunk
-struct Bundle { int dev; hipStream_t stream; hipEvent_t ev[5]; hipStream_t pipe_r, pipe_i; hipEvent_t pipe_ev[kPipeEvents]; };
+constexpr int kPipeLanes = 3;                       // chunk lanes, at most: with the solve stream four streams, the hardware queues a process gets by default
+constexpr int kPipeEvents = 3 + 3 * kPipeChunks + kPipeLanes;    // fork, begin / end of the iterates, (begin, factor done, tail done) per chunk, end of every lane
+struct Bundle { int dev; hipStream_t stream; hipEvent_t ev[5]; hipStream_t pipe_r, pipe_i, pipe_x; hipEvent_t pipe_ev[kPipeEvents]; };
 static void destroy(const Bundle &b) {
   for (hipEvent_t e : b.ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : b.pipe_ev) if (e) (void)hipEventDestroy(e);
-  for (hipStream_t st : {b.stream, b.pipe_r, b.pipe_i}) if (st) (void)hipStreamDestroy(st);
+  for (hipStream_t st : {b.stream, b.pipe_r, b.pipe_i, b.pipe_x}) if (st) (void)hipStreamDestroy(st);
 }
 static std::mutex mu;
 static std::vector<Bundle> idle;
@@ -324,11 +325,13 @@ struct mi_osqp_batch {
   double *pin = nullptr;      // pinned staging of the host update paths (a pageable hipMemcpy runs at ~1 GB/s here, and unevenly)
   size_t pin_n = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, evf0 = nullptr, evf1 = nullptr, evf2 = nullptr;
-  // pipelined refactorisation (solve_impl): stream R of the refactorisation chunks, stream I of the chunk iterates, their events
-  hipStream_t pipe_r = nullptr, pipe_i = nullptr;
+  // pipelined refactorisation (solve_impl): stream R of the refactorisation chunks, stream I of the chunk iterates, their events;
+  // with chunk lanes the three are lanes 0, 1, 2 (pipe_x is only ever the third lane)
+  hipStream_t pipe_r = nullptr, pipe_i = nullptr, pipe_x = nullptr;
   hipEvent_t pipe_ev[streampool::kPipeEvents] = {};
   DevBuf<int> tile_list;                      // the active tiles chunk after chunk (KernelArgs::tiles)
   int64_t pipelined_refactors = 0;            // rho-update points of this handle that took the pipelined form
+  int64_t refactor_lanes = 0;                 // the most chunk lanes one of them ran on (1 = the two-stream form)
   double factor_ms_sum = 0.0, dense_ms_sum = 0.0;
   int64_t refactor_launches = 0, refactor_qps = 0, peak_qps = 0;
   double peak_factor_ms = 0.0, peak_tail_ms = 0.0;
@@ -409,7 +412,8 @@ struct mi_osqp_batch {
     hostpool::give(h_iscal, h_iscal_cap); hostpool::give(h_dscal, h_dscal_cap); hostpool::give(pin, pin_cap); hostpool::give(h_npos, h_npos_cap);
     if (pipe_r) (void)hipStreamSynchronize(pipe_r);
     if (pipe_i) (void)hipStreamSynchronize(pipe_i);
-    streampool::Bundle sb{device, stream, {ev0, ev1, evf0, evf1, evf2}, pipe_r, pipe_i, {}};
+    if (pipe_x) (void)hipStreamSynchronize(pipe_x);
+    streampool::Bundle sb{device, stream, {ev0, ev1, evf0, evf1, evf2}, pipe_r, pipe_i, pipe_x, {}};
     for (int k = 0; k < streampool::kPipeEvents; k++) sb.pipe_ev[k] = pipe_ev[k];
     if (stream && ev0 && ev1 && evf0 && evf1 && evf2) streampool::give(sb);
     else streampool::destroy(sb);
@@ -924,7 +928,7 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
     streampool::Bundle sb;
     if (streampool::take(h->device, sb)) {
       h->stream = sb.stream; h->ev0 = sb.ev[0]; h->ev1 = sb.ev[1]; h->evf0 = sb.ev[2]; h->evf1 = sb.ev[3]; h->evf2 = sb.ev[4];
-      h->pipe_r = sb.pipe_r; h->pipe_i = sb.pipe_i;
+      h->pipe_r = sb.pipe_r; h->pipe_i = sb.pipe_i; h->pipe_x = sb.pipe_x;
       for (int k = 0; k < streampool::kPipeEvents; k++) h->pipe_ev[k] = sb.pipe_ev[k];
     }
     else {
@@ -1443,24 +1447,45 @@ static int adjoint_impl(mi_osqp_batch *h, const AdjointArgs &ga, int32_t *d_stat
 // with an event behind each; stream I runs iterate_kernel over the tiles of a chunk (KernelArgs::tiles) once that chunk's event
 // has fired - chunk 0, the tiles without a flagged QP, at once.  Both fork from the solve stream and join it again, so callers
 // see the ordering they always saw.  Only ordinary LDS-vector batches: no launch here spins on other workgroups.
+// Chunk lanes (MI_OSQP_REFACTOR_LANES > 1; host_core.hpp refactor_lanes): up to three streams that each run the whole chain
+// factor -> tail -> iterate of their chunks, so the drain of one chain's kernel is filled by the other chains.  Chunks on
+// different lanes run side by side: each keeps its block storage / D / Schur scratch at its own offset of the work list
+// (FactorArgs / TailArgs wg_base); a tile of several QPs whose flagged QPs sit in chunks of different lanes waits for the
+// other lanes' tail events.  The events are recorded in ascending chunk order on the host, so every wait sees its record.
+// Behind the join fail_flagged_kernel ends the slots whose new factor lost its inertia; the host learns of them from the flag
+// copy behind the check that follows (pipelined_region_finish) - no host turn between the region and that check.
+struct PipeRegion {
+  bool open = false;
+  int iter = 0, n_chunks = 0, n_lanes = 1;
+  bool tail = false;
+  double host_s = 0.0;                // host time up to the fork
+  std::vector<int> work, wl, tiles;   // the flagged slots; the lists the copies read
+  std::vector<int> lane_last;         // per lane: its last refactorisation chunk (0: none)
+};
+// the defaults of MI_OSQP_REFACTOR_LANES / MI_OSQP_REFACTOR_CHUNK0 (measured, DESIGN.md section 4: two lanes beat three at the
+// headline batch - three chains of equal chunks run in lockstep, factor beside factor, tail beside tail, and overlap nothing)
+constexpr int kDefaultLanes = 2;
+constexpr bool kDefaultChunk0First = false;
 static bool pipeline_applies(const mi_osqp_batch *h, int n_ref) {
   const int longer_than = h->tune.pipeline_min > 0 ? h->tune.pipeline_min : h->n_cus;
   return h->tune.refactor_pipeline && n_ref > longer_than && h->mw_groups <= 0 && !h->global_xs && !(*h->anp).wide && !(*h->anp).df;
 }
 
-// Refactors the slots of `work` and runs iterations (a.iter_begin, a.iter_end] of the tiles that hold a slot of `active`.
-// Slots whose new factor has the wrong inertia are appended to *bad: their iterate left them alone (tile_ptrs), the caller
-// fails them before the check.  Accounting: see mi_osqp_batch_last_solve_stats / DESIGN.md section 4.
-static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, const std::vector<int> &work, const std::vector<int> &active, std::vector<int> *bad) {
-  using streampool::kPipeChunks; using streampool::kPipeEvents;
+// Enqueues the refactorisation of the slots of `work`, iterations (a.iter_begin, a.iter_end] of the tiles that hold a slot of
+// `active` and, behind the join, the failure of the slots whose new factor has the wrong inertia (their iterate left them
+// alone, tile_ptrs) at iteration a.iter_begin.  Nothing is synchronised: the caller enqueues the check, reads the flags and
+// calls pipelined_region_finish.  Accounting: see mi_osqp_batch_last_solve_stats / DESIGN.md section 4.
+static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, const std::vector<int> &work, const std::vector<int> &active, PipeRegion *pr) {
+  using streampool::kPipeChunks; using streampool::kPipeEvents; using streampool::kPipeLanes;
   const double t_begin = now_s();
   const int BT = h->BT, nq = (int)work.size();
   int rc;
   if (!h->pipe_r) HIPCHK(hipStreamCreateWithFlags(&h->pipe_r, hipStreamNonBlocking));
   if (!h->pipe_i) HIPCHK(hipStreamCreateWithFlags(&h->pipe_i, hipStreamNonBlocking));
   for (int k = 0; k < kPipeEvents; k++) if (!h->pipe_ev[k]) HIPCHK(hipEventCreate(&h->pipe_ev[k]));
-  hipEvent_t ev_fork = h->pipe_ev[0], ev_i0 = h->pipe_ev[1], ev_i1 = h->pipe_ev[2];
+  hipEvent_t ev_fork = h->pipe_ev[0], ev_i0 = h->pipe_ev[1], ev_join = h->pipe_ev[2];
   auto ev_chunk = [&](int c, int k) { return h->pipe_ev[3 + 3 * (c - 1) + k]; };      // chunk c >= 1; k = 0 begin, 1 factor done, 2 tail done
+  auto ev_lane = [&](int l) { return h->pipe_ev[3 + 3 * kPipeChunks + l]; };          // end of lane l (one lane: of stream I)
   // default: the fewest even chunks that are one round of one-workgroup-per-QP kernels each (headline batch, 605 QPs on 256 CUs:
   // 3 x 202 beat 2 x 303, 4 x 152, 6 x 101 and 256 + 256 + 93)
   int n_even = h->tune.pipeline_chunks > 0 ? h->tune.pipeline_chunks : (nq + h->n_cus - 1) / h->n_cus;
@@ -1469,66 +1494,127 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
   const RefactorChunks ch = refactor_chunks(work, active, BT, chunk_qps, kPipeChunks);
   // the work list chunk after chunk, each packed kbt slots per workgroup (as device_refactor_slots packs the whole list)
   const int kbt = nq <= h->n_cus ? 1 : BT;
-  std::vector<int> wl, wl_begin(1, 0);
+  const int lanes_asked = h->tune.refactor_lanes > 0 ? h->tune.refactor_lanes : kDefaultLanes;
+  const RefactorLanes rl = refactor_lanes(ch, work, BT, kbt, std::min(lanes_asked, kPipeLanes), h->tune.lanes_chunk0 < 0 ? kDefaultChunk0First : h->tune.lanes_chunk0 != 0,
+                                          h->ntiles * BT + 4);      // (what Lblk, Dl, dinv_scratch and dt_Sd hold: setup)
+  const int L = rl.n_lanes;
+  if (L > 2 && !h->pipe_x) HIPCHK(hipStreamCreateWithFlags(&h->pipe_x, hipStreamNonBlocking));
+  std::vector<int> &wl = pr->wl;
+  std::vector<int> wl_begin(1, 0);
+  wl.clear();
   for (int c = 1; c < ch.n_chunks; c++) {
     wl.insert(wl.end(), work.begin() + ch.work_begin[c], work.begin() + ch.work_begin[c + 1]);
     wl.resize((wl.size() + kbt - 1) / kbt * kbt, -1);
     wl_begin.push_back((int)wl.size());
   }
+  pr->tiles = ch.tiles; pr->work = work;
   if (h->work.n < wl.size() && (rc = h->work.alloc((size_t)h->ntiles * BT + 4 + (size_t)BT * kPipeChunks))) return rc;
   if (h->tile_list.n < ch.tiles.size() && (rc = h->tile_list.alloc((size_t)h->ntiles))) return rc;
   HIPCHK(hipMemcpyAsync(h->work.p, wl.data(), wl.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->tile_list.p, ch.tiles.data(), ch.tiles.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  const double t_fork = now_s();
+  HIPCHK(hipMemcpyAsync(h->tile_list.p, pr->tiles.data(), pr->tiles.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  pr->host_s = now_s() - t_begin;
   HIPCHK(hipEventRecord(ev_fork, h->stream));
-  HIPCHK(hipStreamWaitEvent(h->pipe_r, ev_fork, 0));
-  HIPCHK(hipStreamWaitEvent(h->pipe_i, ev_fork, 0));
-  // ---- stream R
   FactorArgs fa = make_factor_args(h, 0);
   const bool tail = (*h->anp).dt.k != 0;
-  for (int c = 1; c < ch.n_chunks; c++) {
+  // factor_kernel -> tail_assemble_kernel -> tail_kernel of chunk c >= 1 on stream st, its scratch at slot `base` of the scratch buffers
+  auto enqueue_refactor = [&](int c, int base, hipStream_t st) -> int {
     const int *wc = h->work.p + wl_begin[c - 1];
     const int slots = wl_begin[c] - wl_begin[c - 1];
-    fa.work = wc;
-    HIPCHK(hipEventRecord(ev_chunk(c, 0), h->pipe_r));
-    HIPCHK(launch_factor(fa, kbt, slots / kbt, h->tune.factor_threads, h->pipe_r));
-    HIPCHK(hipEventRecord(ev_chunk(c, 1), h->pipe_r));
-    if (tail) HIPCHK(launch_tail(make_tail_args(h, kbt, wc), slots, h->dt_lds_asm, h->dt_lds, h->pipe_r));
-    HIPCHK(hipEventRecord(ev_chunk(c, 2), h->pipe_r));
-  }
-  // ---- stream I
+    fa.work = wc; fa.wg_base = base / kbt;
+    HIPCHK(hipEventRecord(ev_chunk(c, 0), st));
+    HIPCHK(launch_factor(fa, kbt, slots / kbt, h->tune.factor_threads, st));
+    HIPCHK(hipEventRecord(ev_chunk(c, 1), st));
+    if (tail) {
+      TailArgs da = make_tail_args(h, kbt, wc);
+      da.wg_base = base;
+      HIPCHK(launch_tail(da, slots, h->dt_lds_asm, h->dt_lds, st));
+    }
+    HIPCHK(hipEventRecord(ev_chunk(c, 2), st));
+    return 0;
+  };
   KernelArgs ai = a;
-  HIPCHK(hipEventRecord(ev_i0, h->pipe_i));
-  for (int c = 0; c < ch.n_chunks; c++) {
+  auto enqueue_iterate = [&](int c, hipStream_t st) -> int {
     const int nt = ch.tile_begin[c + 1] - ch.tile_begin[c];
-    if (c) HIPCHK(hipStreamWaitEvent(h->pipe_i, ev_chunk(c, 2), 0));
-    if (!nt) continue;
+    if (!nt) return 0;
     ai.tiles = h->tile_list.p + ch.tile_begin[c];
-    HIPCHK(launch_iterate(ai, BT, nt, h->threads, h->lds_iter + h->lds_factor, h->pipe_i));
+    HIPCHK(launch_iterate(ai, BT, nt, h->threads, h->lds_iter + h->lds_factor, st));
+    return 0;
+  };
+  pr->lane_last.assign(L, 0);
+  if (L == 1) {
+    HIPCHK(hipStreamWaitEvent(h->pipe_r, ev_fork, 0));
+    HIPCHK(hipStreamWaitEvent(h->pipe_i, ev_fork, 0));
+    // ---- stream R
+    for (int c = 1; c < ch.n_chunks; c++) if ((rc = enqueue_refactor(c, 0, h->pipe_r))) return rc;
+    pr->lane_last[0] = ch.n_chunks - 1;
+    // ---- stream I
+    HIPCHK(hipEventRecord(ev_i0, h->pipe_i));
+    for (int c = 0; c < ch.n_chunks; c++) {
+      if (c) HIPCHK(hipStreamWaitEvent(h->pipe_i, ev_chunk(c, 2), 0));
+      if ((rc = enqueue_iterate(c, h->pipe_i))) return rc;
+    }
+    // ---- join (stream I has waited for every chunk of R)
+    HIPCHK(hipEventRecord(ev_lane(0), h->pipe_i));
+    HIPCHK(hipStreamWaitEvent(h->stream, ev_lane(0), 0));
+  } else {
+    hipStream_t lane[kPipeLanes] = {h->pipe_r, h->pipe_i, h->pipe_x};
+    for (int l = 0; l < L; l++) HIPCHK(hipStreamWaitEvent(lane[l], ev_fork, 0));
+    const bool chunk0_first = rl.order[rl.lane_of[0]].front() == 0;
+    if (chunk0_first && (rc = enqueue_iterate(0, lane[rl.lane_of[0]]))) return rc;
+    size_t w = 0;         // (the waits are sorted by the waiting chunk)
+    for (int c = 1; c < ch.n_chunks; c++) {
+      const int l = rl.lane_of[c];
+      if ((rc = enqueue_refactor(c, rl.scratch_begin[c], lane[l]))) return rc;
+      pr->lane_last[l] = c;
+      for (; w < rl.wait_chunk.size() && rl.wait_chunk[w] == c; w++) HIPCHK(hipStreamWaitEvent(lane[l], ev_chunk(rl.wait_for[w], 2), 0));
+      if ((rc = enqueue_iterate(c, lane[l]))) return rc;
+    }
+    if (!chunk0_first && (rc = enqueue_iterate(0, lane[rl.lane_of[0]]))) return rc;
+    // ---- join
+    for (int l = 0; l < L; l++) { HIPCHK(hipEventRecord(ev_lane(l), lane[l])); HIPCHK(hipStreamWaitEvent(h->stream, ev_lane(l), 0)); }
   }
-  HIPCHK(hipEventRecord(ev_i1, h->pipe_i));
-  // ---- join (stream I has waited for every chunk of R), flags of the new factors
-  HIPCHK(hipStreamWaitEvent(h->stream, ev_i1, 0));
-  HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)h->ntiles * IS_COUNT * BT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  const double t_end = now_s();
-  float f_ms = 0.f, d_ms = 0.f, r_ms = 0.f, i_ms = 0.f;
-  for (int c = 1; c < ch.n_chunks; c++) {
+  HIPCHK(hipEventRecord(ev_join, h->stream));
+  // a rho update that makes the factor lose its inertia ends THAT QP as kNonConvex ([EXT] osqp_solve: adapt_rho fails ->
+  // OSQP_NON_CVX, break); every other QP of the batch goes on
+  HIPCHK(launch_fail_flagged(a, h->work.p, (int)wl.size(), BT, a.iter_begin, h->stream));
+  pr->open = true; pr->iter = a.iter_begin; pr->n_chunks = ch.n_chunks; pr->n_lanes = L; pr->tail = tail;
+  h->refactor_lanes = std::max<int64_t>(h->refactor_lanes, L);
+  return 0;
+}
+
+// Behind the synchronisation that follows the region's check: its accounting from the events, and the slots fail_flagged_kernel
+// ended (status kNonConvex in the flag copy h_iscal) into h->failed.
+static int pipelined_region_finish(mi_osqp_batch *h, PipeRegion *pr) {
+  using streampool::kPipeChunks;
+  if (!pr->open) return 0;
+  pr->open = false;
+  const int BT = h->BT, nq = (int)pr->work.size();
+  hipEvent_t ev_fork = h->pipe_ev[0], ev_i0 = h->pipe_ev[1], ev_join = h->pipe_ev[2];
+  auto ev_chunk = [&](int c, int k) { return h->pipe_ev[3 + 3 * (c - 1) + k]; };
+  float f_ms = 0.f, d_ms = 0.f, r_ms = 0.f, i_ms = 0.f, w_ms = 0.f;
+  for (int c = 1; c < pr->n_chunks; c++) {
     float f = 0.f, d = 0.f;
     HIPCHK(hipEventElapsedTime(&f, ev_chunk(c, 0), ev_chunk(c, 1))); HIPCHK(hipEventElapsedTime(&d, ev_chunk(c, 1), ev_chunk(c, 2)));
-    f_ms += f; d_ms += tail ? d : 0.f;
+    f_ms += f; d_ms += pr->tail ? d : 0.f;
   }
-  HIPCHK(hipEventElapsedTime(&r_ms, ev_fork, ev_chunk(ch.n_chunks - 1, 2)));
-  HIPCHK(hipEventElapsedTime(&i_ms, ev_i0, ev_i1));
-  // refactor_s: up to the last chunk's event; device_s: what remained exposed of the iterate, up to the join - together the wall time
-  const double wall = t_end - t_begin, ref_s = std::min(wall, (t_fork - t_begin) + 1e-3 * r_ms);
+  for (int c : pr->lane_last) {         // the latest tail-done event of any lane
+    float r = 0.f;
+    if (c) HIPCHK(hipEventElapsedTime(&r, ev_fork, ev_chunk(c, 2)));
+    r_ms = std::max(r_ms, r);
+  }
+  HIPCHK(hipEventElapsedTime(&w_ms, ev_fork, ev_join));
+  // the span of the iterates as one launch (it contains waiting): of stream I, or with lanes - an iterate on some lane from
+  // the first chunk's tail on at the latest, chunk 0 from the fork on - of the whole region
+  if (pr->n_lanes == 1) HIPCHK(hipEventElapsedTime(&i_ms, ev_i0, h->pipe_ev[3 + 3 * kPipeChunks])); else i_ms = w_ms;
+  // refactor_s: up to the last tail event; device_s: what remained exposed of the iterate, up to the join - together the wall time
+  const double wall = pr->host_s + 1e-3 * std::max(w_ms, r_ms), ref_s = pr->host_s + 1e-3 * r_ms;
   h->last_refactor_s += ref_s; h->last_device_s += wall - ref_s;
-  h->kernel_ms_sum += i_ms; h->kernel_launches++; h->last_launches++;       // the span of stream I as one launch: it contains waiting
+  h->kernel_ms_sum += i_ms; h->kernel_launches++; h->last_launches++;
   h->factor_ms_sum += f_ms; h->dense_ms_sum += d_ms; h->refactor_launches++; h->refactor_qps += nq;
   if (nq >= h->peak_qps) { h->peak_qps = nq; h->peak_factor_ms = f_ms; h->peak_tail_ms = d_ms; }
   h->pipelined_refactors++;
-  for (int s : work)
-    if (h->h_iscal[(size_t)(s / BT) * IS_COUNT * BT + IS_NEED_REFACTOR * BT + s % BT] < 0) bad->push_back(s);
+  for (int s : pr->work)
+    if (s >= 0 && s < h->B && h->h_iscal[(size_t)(s / BT) * IS_COUNT * BT + IS_STATUS * BT + s % BT] == -7) h->failed[s] = 1;
   return 0;
 }
 
@@ -1563,6 +1649,7 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
   auto loop = [&]() -> int {
     int iter = 0;
     bool iterated = false;       // the segment's iterations have run already, pipelined with the refactorisation before them
+    PipeRegion region;           // ... and this is that region, enqueued and not yet accounted for
     while (true) {
       const int seg_end = segment_end(iter);
       a.iter_begin = iter; a.iter_end = seg_end; a.info_at_end = 1;
@@ -1598,7 +1685,7 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
         h->last_device_s += ms * 1e-3; h->kernel_ms_sum += ms; h->kernel_launches++; h->last_launches++;
-      }
+      } else if ((rc = pipelined_region_finish(h, &region))) return rc;
       iterated = false;
       iter = seg_end;
       // QPs still iterating / asking for a refactorisation.  A QP that runs into max_iter at a rho-update iteration
@@ -1622,9 +1709,9 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
           // a long list: its chunks overlap with the next segment's iterations, chunk after chunk
           KernelArgs nx = a;
           nx.iter_begin = iter; nx.iter_end = segment_end(iter); nx.info_at_end = 1;
-          if ((rc2 = pipelined_refactor_iterate(h, nx, work, active, &bad))) return rc2;
+          if ((rc2 = pipelined_refactor_iterate(h, nx, work, active, &region))) return rc2;
           iterated = true;
-          tr = now_s();         // (the region has done its own accounting)
+          tr = now_s();         // (the region does its own accounting, and fails the QPs that lost their inertia on the device)
         } else if ((rc2 = device_refactor_slots(h, std::move(work), &bad))) return rc2;
         // a rho update that makes the factor lose its inertia ends THAT QP as kNonConvex ([EXT] osqp_solve: adapt_rho
         // fails -> OSQP_NON_CVX, break); every other QP of the batch goes on
@@ -1646,6 +1733,7 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
   if (rc) {
     if (h->pipe_r) (void)hipStreamSynchronize(h->pipe_r);
     if (h->pipe_i) (void)hipStreamSynchronize(h->pipe_i);
+    if (h->pipe_x) (void)hipStreamSynchronize(h->pipe_x);
     (void)hipStreamSynchronize(h->stream);
     return rc;
   }
@@ -1927,6 +2015,7 @@ int mi_osqp_batch_get_stats(mi_osqp_batch *h, mi_osqp_stats *st) {
   if (!h || !st) return MI_OSQP_ERR_NULL;
   *st = h->stats;
   st->pipelined_refactors = h->pipelined_refactors;
+  st->refactor_lanes = h->refactor_lanes;
   return MI_OSQP_OK;
 }
 
@@ -3740,6 +3829,30 @@ int mi_osqp_debug_refactor_chunks(int64_t n_flagged, const int64_t *flagged, int
   std::copy(ch.work_begin.begin(), ch.work_begin.end(), work_begin);
   std::copy(ch.tiles.begin(), ch.tiles.end(), tiles);
   std::copy(ch.tile_begin.begin(), ch.tile_begin.end(), tile_begin);
+  return MI_OSQP_OK;
+}
+int mi_osqp_debug_refactor_lanes(int64_t n_flagged, const int64_t *flagged, int64_t n_active, const int64_t *active, int64_t tile,
+                                 int64_t chunk_qps, int64_t max_chunks, int64_t kbt, int64_t lanes, int64_t chunk0_first,
+                                 int64_t scratch_slots, int64_t *n_lanes, int64_t *lane_of, int64_t *order, int64_t *order_begin,
+                                 int64_t *scratch_begin, int64_t *n_waits, int64_t *wait_chunk, int64_t *wait_for) {
+  if (!n_lanes || !lane_of || !order || !order_begin || !scratch_begin || !n_waits || !wait_chunk || !wait_for ||
+      (n_flagged > 0 && !flagged) || (n_active > 0 && !active)) return MI_OSQP_ERR_NULL;
+  if (n_flagged < 0 || n_active < 0 || tile < 1 || chunk_qps < 1 || max_chunks < 1 || kbt < 1 || lanes < 1 || lanes > 3 || scratch_slots < 0)
+    return MI_OSQP_ERR_INVALID_DATA;
+  const std::vector<int> f(flagged, flagged + n_flagged), a(active, active + n_active);
+  const RefactorChunks ch = refactor_chunks(f, a, (int)tile, (int)chunk_qps, (int)max_chunks);
+  const RefactorLanes rl = refactor_lanes(ch, f, (int)tile, (int)kbt, (int)lanes, chunk0_first != 0, (int)std::min<int64_t>(scratch_slots, INT32_MAX));
+  *n_lanes = rl.n_lanes;
+  std::copy(rl.lane_of.begin(), rl.lane_of.end(), lane_of);
+  order_begin[0] = 0;
+  for (int l = 0; l < rl.n_lanes; l++) {
+    std::copy(rl.order[l].begin(), rl.order[l].end(), order + order_begin[l]);
+    order_begin[l + 1] = order_begin[l] + (int64_t)rl.order[l].size();
+  }
+  std::copy(rl.scratch_begin.begin(), rl.scratch_begin.begin() + ch.n_chunks, scratch_begin);
+  *n_waits = (int64_t)rl.wait_chunk.size();
+  std::copy(rl.wait_chunk.begin(), rl.wait_chunk.end(), wait_chunk);
+  std::copy(rl.wait_for.begin(), rl.wait_for.end(), wait_for);
   return MI_OSQP_OK;
 }
 int mi_osqp_get_stats(mi_osqp_solver *h, mi_osqp_stats *st) { return h ? mi_osqp_batch_get_stats(h->b, st) : MI_OSQP_ERR_NULL; }
