@@ -114,6 +114,7 @@ typedef struct {
   int64_t resident_factor_steps, lds_bytes_factor;   /* resident head of S^-1: 512 B steps of the dense-tail stream every wave of a tile keeps in registers and LDS across a segment (0 = streamed); LDS of its part, which the iterate launches take on top of lds_bytes_iterate */
   int64_t dense_tail_tasks, dense_tail_waves_used, dense_tail_wave_tasks_max;   /* deal of the dense-tail product: 64 x 64 block tasks, waves of a tile that own at least one, most tasks of one wave */
   int64_t refactor_lanes;   /* the most chunk lanes a pipelined rho-update point has run on since setup: streams that each run factor -> tail -> iterate of their chunks (1 = one refactorisation stream and one iterate stream; 0 = none pipelined yet) */
+  int64_t iterate_launches_deep_ring, iterate_launches_long_head;   /* iterate launches since setup by the form of the resident head they ran (MI_OSQP_RF_FORM, MI_OSQP_RF_LONG_MIN): 16 steps resident and a product ring of 16, or resident_factor_steps (32) and a ring of 8; both 0 on a handle without a head */
 } mi_osqp_stats;
 
 typedef struct mi_osqp_solver mi_osqp_solver; /* one QP  */
@@ -643,6 +644,11 @@ int mi_osqp_debug_refactor_lanes(int64_t n_flagged, const int64_t *flagged, int6
                                  int64_t chunk_qps, int64_t max_chunks, int64_t kbt, int64_t lanes, int64_t chunk0_first,
                                  int64_t scratch_slots, int64_t *n_lanes, int64_t *lane_of, int64_t *order, int64_t *order_begin,
                                  int64_t *scratch_begin, int64_t *n_waits, int64_t *wait_chunk, int64_t *wait_for);
+
+/* Host only: the form of the resident head of S^-1 one iterate launch takes (host_core.hpp iterate_form).  tiles = tiles the
+ * launch iterates, has_head = the handle keeps a head, forced_form = MI_OSQP_RF_FORM (0 none, 1 deep ring, 2 long head),
+ * long_min = MI_OSQP_RF_LONG_MIN (-1 = the default, 0).  Out: *form = 0 streamed, 1 deep ring, 2 long head. */
+int mi_osqp_debug_iterate_form(int64_t tiles, int64_t has_head, int64_t forced_form, int64_t long_min, int64_t *form);
 
 /* Device diagnostics (tile 2, LDS mode only): one KKT solve of the whole batch with
  * per-phase / per-wave shader-clock stamps of two tiles (first, middle).

@@ -61,7 +61,8 @@ class Stats(C.Structure):
                 ("resident_state", C.c_int64), ("lds_bytes_iterate", C.c_int64), ("pipelined_refactors", C.c_int64),
                 ("resident_factor_steps", C.c_int64), ("lds_bytes_factor", C.c_int64),
                 ("dense_tail_tasks", C.c_int64), ("dense_tail_waves_used", C.c_int64), ("dense_tail_wave_tasks_max", C.c_int64),
-                ("refactor_lanes", C.c_int64)]
+                ("refactor_lanes", C.c_int64),
+                ("iterate_launches_deep_ring", C.c_int64), ("iterate_launches_long_head", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -201,6 +202,7 @@ def lib():
                                                    C.POINTER(Settings), C.c_int64, dp, dp, dp, C.POINTER(Stats)]
         L.mi_osqp_debug_refactor_chunks.argtypes = [C.c_int64, ip, C.c_int64, ip, C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip]
         L.mi_osqp_debug_refactor_lanes.argtypes = [C.c_int64, ip, C.c_int64, ip] + [C.c_int64] * 7 + [ip] * 8
+        L.mi_osqp_debug_iterate_form.argtypes = [C.c_int64] * 4 + [ip]
         L.mi_osqp_prefetch_analysis.argtypes = [C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip, C.c_int64]
         L.mi_osqp_debug_host_block_factor.argtypes = [C.c_int64, C.c_int64, ip, ip, dp, ip, ip, dp, dp, dp,
                                                       C.POINTER(Settings), dp, dp, ip]
@@ -931,6 +933,15 @@ def debug_refactor_lanes(flagged, active, tile, chunk_qps, lanes, kbt=None, chun
     return dict(n_lanes=L, lane_of=lane_of[:k].tolist(), order=[order[ob[l]:ob[l + 1]].tolist() for l in range(L)],
                 scratch=[(int(sb[c]), (len(work[c]) + kbt - 1) // kbt * kbt) for c in range(k)],
                 waits=list(zip(wc[:nw.value].tolist(), wf[:nw.value].tolist())))
+
+
+def debug_iterate_form(tiles, has_head=True, forced_form=0, long_min=-1):
+    """Host-only: the form of the resident head of S^-1 an iterate launch of `tiles` iterating tiles takes: 0 streamed (a
+    handle without a head), 1 deep ring, 2 long head.  forced_form: MI_OSQP_RF_FORM; long_min: MI_OSQP_RF_LONG_MIN (-1 = the
+    default)."""
+    form = C.c_int64()
+    _chk(lib().mi_osqp_debug_iterate_form(tiles, int(bool(has_head)), forced_form, long_min, C.byref(form)), "debug_iterate_form")
+    return int(form.value)
 
 
 def debug_host_block_factor(P, A, l, u, **settings):

@@ -35,6 +35,9 @@ enum { DS_C = 0, DS_CINV, DS_RHO, DS_RHO_EST, DS_PRI_RES, DS_DUA_RES, DS_OBJ, DS
 //  alone.  IS_EPOCH counts the solves begun in the slot: the host tells a finished solve from the previous one by it.)
 enum { IS_STATUS = 0, IS_ITER, IS_RHO_UPDATES, IS_DONE, IS_NEED_REFACTOR, IS_CUR, IS_PENDING, IS_EPOCH, IS_COUNT };
 
+// forms of the resident iterate's S^-1 product (kernels.hip dense_tail_apply_rf; host_core.hpp iterate_form picks one per launch)
+enum { RF_FORM_NONE = 0, RF_FORM_DEEP_RING = 1, RF_FORM_LONG_HEAD = 2 };
+
 struct KernelArgs {
   int n, m, N, B;
   SchedDev fwd, bwd, chk;
@@ -62,6 +65,7 @@ struct KernelArgs {
   int xs_len;                           // length of the solve vector: Analysis::Next >= n + m
   int rs_off;                           // iterate / advance launches: LDS offset (in doubles) of the resident state (iterate_body RS), 0 = streamed
   int rf_off;                           // iterate launches: LDS offset (in doubles) of the LDS part of the resident head of S^-1 (iterate_body RF), 0 = streamed
+  int rf_form;                          // with rf_off: the form of the head this launch runs (RF_FORM_DEEP_RING, RF_FORM_LONG_HEAD); every launch reloads its head, so launches of one solve may differ
   int wide;                             // 32-bit gather / row indices (Schedule::idxw64): vectors of 65 535 entries and more; needs xs_global, BT = 1
   // settings (row S)
   double sigma, alpha, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, rho_tolerance;
@@ -180,8 +184,8 @@ bool factor_fits_lds(const FactorArgs &a, int threads);      // the LDS-resident
 int max_coresident_groups(int threads, size_t lds, int n_cus);
 int max_coresident_factor_groups(int threads, int n_cus);
 hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st);
-// resident head of S^-1 of the resident iterate (kernels.hip dense_tail_apply_rf): steps per wave in all / in LDS
-int rf_head_steps();
+// resident head of S^-1 of the resident iterate (kernels.hip dense_tail_apply_rf): steps per wave in all (of form RF_FORM_*) / in LDS (every form)
+int rf_head_steps(int form);
 int rf_lds_steps();
 hipError_t launch_check(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st);
 // up to max_segments segments of seg_len iterations + check per tile in one launch (advance_kernel; LDS-resident tiles only);

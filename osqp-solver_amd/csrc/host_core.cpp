@@ -1041,6 +1041,8 @@ Tuning tuning_from_env() {
   if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNK_QPS")) t.pipeline_chunk_qps = std::max(0, atoi(e));
   if (const char *e = getenv("MI_OSQP_REFACTOR_LANES")) t.refactor_lanes = std::max(1, std::min(3, atoi(e)));
   if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNK0")) t.lanes_chunk0 = atoi(e) != 0;
+  if (const char *e = getenv("MI_OSQP_RF_FORM")) { const int v = atoi(e); if (v == kIterDeepRing || v == kIterLongHead) t.rf_form = v; }
+  if (const char *e = getenv("MI_OSQP_RF_LONG_MIN")) t.rf_long_min = std::max(0, atoi(e));
   AnalysisTuning &a = t.analysis;
   if (const char *e = getenv("MI_OSQP_DENSE_TAIL")) a.dense_tail = atoi(e);
   if (const char *e = getenv("MI_OSQP_ORDERING")) a.ordering = e[0];
@@ -1115,6 +1117,13 @@ RefactorLanes refactor_lanes(const RefactorChunks &ch, const std::vector<int> &f
     for (int d = 1; d < c; d++) if (need[d]) { rl.wait_chunk.push_back(c); rl.wait_for.push_back(d); }
   }
   return rl;
+}
+
+int iterate_form(int tiles, bool has_head, const Tuning &t) {
+  if (!has_head) return kIterStreamed;
+  if (t.rf_form == kIterDeepRing || t.rf_form == kIterLongHead) return t.rf_form;
+  const int long_min = t.rf_long_min >= 0 ? t.rf_long_min : kRfLongMinDefault;
+  return tiles > 0 && tiles >= long_min ? kIterLongHead : kIterDeepRing;       // (a launch without a tile does nothing in either form)
 }
 
 // --------------------------------------------------------------------- analyze

@@ -67,9 +67,23 @@ struct Tuning {
                                    // both 0 (the measured default): the fewest even chunks of at most one QP per CU - 3 x 202 for 605 QPs
   int refactor_lanes = 0;          // MI_OSQP_REFACTOR_LANES: 1 .. 3 chunk lanes (refactor_lanes below); 1 = the two-stream form; 0 = the default
   int lanes_chunk0 = -1;           // MI_OSQP_REFACTOR_CHUNK0: 1 chunk 0 in front of the last lane, 0 behind the shortest lane; -1 = the default
+  // form of the resident head of S^-1 per iterate launch (iterate_form below)
+  int rf_form = 0;                 // MI_OSQP_RF_FORM: 1 the deep ring, 2 the long head in every launch of the handle; 0 = by the threshold
+  int rf_long_min = -1;            // MI_OSQP_RF_LONG_MIN: launches that iterate at least so many tiles take the long head (0 = every launch); -1 = the default, kRfLongMinDefault
   AnalysisTuning analysis;
 };
 Tuning tuning_from_env();
+
+// Form of the S^-1 product of one iterate launch of a handle with the resident head (kernels.hip dense_tail_apply_rf; the
+// values are device_types.h RF_FORM_*).  tiles = the tiles the launch will actually iterate (finished tiles of the grid leave
+// at once), has_head = the handle keeps a head at all (else: the streaming form, whatever is forced).  The long head (32
+// steps resident, a product ring of 8) streams 16 steps per wave and iteration less than the deep ring (16 steps resident, a
+// ring of 16); a launch that iterates at least rf_long_min tiles takes it.  Measured ("Measurements
+// (two forms of the resident head)"): the long head is faster on the full launches and no slower on launches of a few
+// tiles, so the default threshold is 0 - every launch.
+enum IterateForm { kIterStreamed = 0, kIterDeepRing = 1, kIterLongHead = 2 };
+constexpr int kRfLongMinDefault = 0;
+int iterate_form(int tiles, bool has_head, const Tuning &t);
 
 // Chunks of a pipelined refactorisation.  `flagged` = the slots (tile * bt + b) that get a new factor, ascending; `active` =
 // the slots that iterate on afterwards, ascending.  The flagged slots are cut in order into chunks 1 .. n_chunks - 1 of

@@ -788,21 +788,40 @@ __device__ __forceinline__ void dense_tail_apply(const DenseTailDev &dt, const m
 // [wave][step][lane], written and read by the same lane: no barrier), steps [RL, H) in the registers `keep` (constant
 // indices only).  Every task is 32 or 64 steps long, so with H <= 32 the head lies inside the first task whatever its kind,
 // and with H a multiple of the ring depth the ring takes the rest of the task in whole revolutions.
-// R = 8, RL = 8 (113 VGPRs, no scratch): with 24 or 16 register steps, both tried, the kernel spills 21 VGPRs at the 128 a
-// wave may have at 16 waves per CU - a form that spills is not taken at any R ("Resident head of S^-1").
+// The ring depth PF is the form's own (dense_tail_apply keeps 2 * MI_DT_PF for a lone stream): eight steps of ring and eight
+// steps of head cost 16 VGPRs either way, and the kernel has 128 at 16 waves per CU.  Two forms (KernelArgs::rf_form):
+//   deep ring  R = 8,  RL = 8, PF = 16  (H = 16, 102 VGPRs) - the form the head began with;
+//   long head  R = 24, RL = 8, PF = 8   (H = 32, 118 VGPRs) - the whole of a 32-step first task, half of a 64-step one.
+// Neither has scratch.  What made room for R = 24 beside the ring it traded in: the thread's own index is opaque at the two
+// places of an iteration that walk per-row tables (kkt_middle_rf, the vector step of iterate_body), so the table addresses
+// are formed there instead of living in VGPR pairs across the whole call ("Resident head of S^-1").  The LDS
+// part is the same in both forms, so a handle's LDS does not depend on the form of a launch.
 // `first` (the call's first iteration) issues the head's loads - the same raw_buffer_load_b64 at the same offsets as
 // dense_tail_apply, the null descriptor of a finished or failed QP returning 0 - and keeps what they return; later iterations
 // load nothing for the head and start the ring at begin + H.  Every launch reloads the head: the new factor of a rho update,
-// a reset, an objective or an A update needs no invalidation.  Same barriers, same tj / ti loads, same fma order and
-// rotations, same flush: bitwise the result of dense_tail_apply<1, 1, PF>.  A wave without a task keeps nothing.
+// a reset, an objective or an A update needs no invalidation, and neither does a change of form between two launches.
+// Same barriers, same tj / ti loads, same fma order and rotations, same flush: bitwise the result of
+// dense_tail_apply<1, 1, PF> at any PF.  A wave without a task keeps nothing.
 // The ring's loads past a wave's range, which dense_tail_apply issues and drops, are left out here: what follows the range
 // is the head of the next wave, which nobody else loads any more - they would cost HBM traffic instead of an L2 hit.
-#ifndef MI_RF_R
-#define MI_RF_R 8
-#endif
 #ifndef MI_RF_RL
 #define MI_RF_RL 8
 #endif
+#ifndef MI_RF_R_DEEP
+#define MI_RF_R_DEEP 8
+#endif
+#ifndef MI_RF_PF_DEEP
+#define MI_RF_PF_DEEP (2 * MI_DT_PF)
+#endif
+#ifndef MI_RF_R_LONG
+#define MI_RF_R_LONG 24
+#endif
+#ifndef MI_RF_PF_LONG
+#define MI_RF_PF_LONG 8
+#endif
+// register steps / ring depth of form RF (RF_FORM_DEEP_RING, RF_FORM_LONG_HEAD; 1 / MI_RF_PF_DEEP without a head)
+__host__ __device__ constexpr int rf_reg_steps(int RF) { return RF == RF_FORM_LONG_HEAD ? MI_RF_R_LONG : RF == RF_FORM_DEEP_RING ? MI_RF_R_DEEP : 1; }
+__host__ __device__ constexpr int rf_ring_steps(int RF) { return RF == RF_FORM_LONG_HEAD ? MI_RF_PF_LONG : MI_RF_PF_DEEP; }
 template <int R, int RL, int PF>
 __device__ __forceinline__ void dense_tail_apply_rf(const DenseTailDev &dt, const mi_rsrc &vals, const double *xt, double *yr, double *yc,
                                                     double (&keep)[R], double *hl, bool first, int wave, int lane) {
@@ -930,17 +949,21 @@ __device__ __forceinline__ void kkt_middle(const KernelArgs &a, const double *di
 }
 
 // kkt_middle of the resident iterate with the resident head of S^-1 (one QP per tile, LDS vector, dense tail)
-template <int R, int RL>
+template <int R, int RL, int PF>
 __device__ __forceinline__ void kkt_middle_rf(const KernelArgs &a, const double *dinv, const mi_rsrc &vdt, double *xs, double (&keep)[R],
                                               double *hl, bool first, int tid, int nthr, int wave, int lane) {
   const int s = a.dt.s, k = a.dt.k;
   double *yr = xs + (size_t)a.xs_len, *yc = yr + (size_t)k;
-  for (int e = tid; e < a.N; e += nthr) {
+  // (the first row opaque: xloc + e and dinv + e are then formed here in every iteration - hoisted out of the iteration loop
+  //  they hold two VGPR pairs through the sweeps and the product, which is what spilled at R = 24)
+  int e0 = tid;
+  asm volatile("" : "+v"(e0));
+  for (int e = e0; e < a.N; e += nthr) {
     if (e < s) xs[(size_t)a.xloc[e]] *= dinv[e];
     else { yr[e - s] = dinv[e] * xs[e]; yc[e - s] = 0.0; }
   }
   __syncthreads();
-  dense_tail_apply_rf<R, RL, 2 * MI_DT_PF>(a.dt, vdt, xs + (size_t)s, yr, yc, keep, hl, first, wave, lane);
+  dense_tail_apply_rf<R, RL, PF>(a.dt, vdt, xs + (size_t)s, yr, yc, keep, hl, first, wave, lane);
   for (int e = tid; e < k; e += nthr) xs[(size_t)s + e] = yr[e] + yc[e];
   __syncthreads();
 }
@@ -1004,10 +1027,10 @@ __device__ __forceinline__ void kkt_solve_lds(const KernelArgs &a, const TilePtr
 // the pass that builds the first right-hand side, x / z / y stored by the last iteration.  Only this workgroup touches
 // them in between and nobody reads them before check_kernel.  Same expressions in the same order: the results are
 // bitwise those of the streaming form.  A compile-time flag for the reason given at solve_vector.
-// RF (resident head of S^-1, with RS, one QP per tile, dense tail): the first MI_RF_R + MI_RF_RL steps of every wave's first
-// product task stay in registers and in LDS behind the resident state (KernelArgs::rf_off) from the call's first iteration
-// on (dense_tail_apply_rf).  A compile-time flag for the same reason.
-template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false, bool RF = false>
+// RF (resident head of S^-1, with RS, one QP per tile, dense tail; 0 = none, else the form RF_FORM_*): the first
+// rf_reg_steps(RF) + MI_RF_RL steps of every wave's first product task stay in registers and in LDS behind the resident state
+// (KernelArgs::rf_off) from the call's first iteration on (dense_tail_apply_rf).  Compile-time for the same reason.
+template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false, int RF = 0>
 __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, int n_iter) {
   static_assert(!RS || (!GX && !WIDE), "the resident state goes with the LDS solve vector");
   static_assert(!RF || (RS && BT == 1 && NT == 1024), "the resident head goes with the resident state of a 16-wave tile of one QP");
@@ -1036,9 +1059,9 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
   const double *const Q = RS ? X + (size_t)n * BT : p.q, *const RI = RS ? Y + (size_t)m * BT : p.rho_inv;
   const double *const RV = RS ? RI + (size_t)m * BT : p.rho_vec, *const LO = RS ? RV + (size_t)m * BT : p.l;
   const double *const UP = RS ? LO + (size_t)m * BT : p.u, *const DI = RS ? UP + (size_t)m * BT : p.dinv;
-  double keep[RF ? MI_RF_R : 1];
+  double keep[rf_reg_steps(RF)];
 #pragma unroll
-  for (int st = 0; st < (RF ? MI_RF_R : 1); st++) keep[st] = 0.0;
+  for (int st = 0; st < rf_reg_steps(RF); st++) keep[st] = 0.0;
   double *hl = nullptr;
   (void)keep; (void)hl;
   if constexpr (RF) hl = smem + a.rf_off + (size_t)(wave * MI_RF_RL) * 64 + lane;
@@ -1073,7 +1096,7 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
     // ---- E7
     if constexpr (RS) {                                       // kkt_solve_lds with D^-1 from LDS
       run_tri<BT, MI_PFV_NT(NT, GX), GX, 0, WIDE>(a.fwd, p.vfwd, xs, wave, lane);
-      if constexpr (RF) kkt_middle_rf<MI_RF_R, MI_RF_RL>(a, DI, p.vdt[0], xs, keep, hl, iter == 1, tid, nthr, wave, lane);
+      if constexpr (RF) kkt_middle_rf<rf_reg_steps(RF), MI_RF_RL, rf_ring_steps(RF)>(a, DI, p.vdt[0], xs, keep, hl, iter == 1, tid, nthr, wave, lane);
       else kkt_middle<BT, GX>(a, DI, p.vdt, p.act, xs, tid, nthr, wave, lane);
       run_tri<BT, MI_PFV_NT(NT, GX), GX, 0, WIDE>(a.bwd, p.vbwd, xs, wave, lane);
     } else {
@@ -1085,10 +1108,12 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
     //  are loaded before any of them is stored, else every trip costs a full memory round trip - 1.5 ms per iteration at
     //  config 5; U = 1 with the vector in LDS: same code as before)
     constexpr int U = GX ? 4 : 1;
+    int tid_i = tid;          // (RF: opaque for the reason given at kkt_middle_rf - here it is pinv + e)
+    if constexpr (RF != 0) asm volatile("" : "+v"(tid_i));
     // (dataflow form: the solution of row pe sits at df_bloc(pe); the new right-hand side goes to pe and the entries the
     //  forward sweep writes are armed - same thread, loads before stores, so an entry that is both is read first)
     uint32_t fl[U], xl[U];
-    for (int e0 = tid; e0 < n * BT; e0 += nthr * U) {
+    for (int e0 = tid_i; e0 < n * BT; e0 += nthr * U) {
       size_t pos[U]; double xt[U], xp[U], qv[U];
 #pragma unroll
       for (int u = 0; u < U; u++) { const int e = e0 + u * nthr < n * BT ? e0 + u * nthr : e0; pos[u] = (size_t)a.pinv[e / BT] * BT + b; }
@@ -1116,7 +1141,7 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
         }
       }
     }
-    for (int e0 = tid; e0 < m * BT; e0 += nthr * U) {
+    for (int e0 = tid_i; e0 < m * BT; e0 += nthr * U) {
       size_t pos[U]; double nu[U], zp[U], yv[U], ri[U], rv[U], lo[U], up[U];
 #pragma unroll
       for (int u = 0; u < U; u++) { const int e = e0 + u * nthr < m * BT ? e0 + u * nthr : e0; pos[u] = (size_t)a.pinv[n + e / BT] * BT + b; }
@@ -1152,7 +1177,7 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
     if constexpr (GX) wg_or_grid_barrier(mw); else __syncthreads();
   }
 }
-template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false, bool RF = false>
+template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false, int RF = 0>
 __global__ __launch_bounds__(NT) void iterate_kernel(KernelArgs a) {
   extern __shared__ double smem[];
   iterate_body<BT, NT, GX, WIDE, RS, RF>(a, smem, a.iter_end - a.iter_begin);
@@ -4045,7 +4070,7 @@ static bool grid_resident(const void *kern, const KernelArgs &a, int threads, si
          nb * n_cus >= a.mw_groups;
 }
 
-int rf_head_steps() { return MI_RF_R + MI_RF_RL; }
+int rf_head_steps(int form) { return form == RF_FORM_NONE ? 0 : rf_reg_steps(form) + MI_RF_RL; }
 int rf_lds_steps() { return MI_RF_RL; }
 hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st) {
   if (getenv("MI_OSQP_DEBUG_HIP")) fprintf(stderr, "[mi_osqp] launch_iterate: df %d wide %d xs_global %p BT %d tiles %d threads %d lds %zu groups %d bar %p\n", a.df, a.wide, (void *)a.xs_global, BT, tiles, threads, lds, a.mw_groups, (void *)a.mw_bar);
@@ -4063,7 +4088,9 @@ hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, s
     };
     if (a.rf_off) {     // resident head of S^-1 (lds covers its LDS part)
       if (BT != 1 || !a.dt.k || threads != 1024) return hipErrorInvalidValue;
-      return go(&iterate_kernel<1, 1024, false, false, true, true>);
+      if (a.rf_form == RF_FORM_LONG_HEAD) return go(&iterate_kernel<1, 1024, false, false, true, RF_FORM_LONG_HEAD>);
+      if (a.rf_form == RF_FORM_DEEP_RING) return go(&iterate_kernel<1, 1024, false, false, true, RF_FORM_DEEP_RING>);
+      return hipErrorInvalidValue;
     }
     return BT == 1 ? go(&iterate_kernel<1, 1024, false, false, true>) : go(&iterate_kernel<2, 1024, false, false, true>);
   }

@@ -31,6 +31,7 @@
 #include "host_core.hpp"
 
 using namespace miosqp;
+static_assert((int)kIterStreamed == RF_FORM_NONE && (int)kIterDeepRing == RF_FORM_DEEP_RING && (int)kIterLongHead == RF_FORM_LONG_HEAD, "iterate_form returns RF_FORM_*");
 
 static thread_local std::string g_last_error;
 
@@ -280,7 +281,8 @@ struct mi_osqp_batch {
   size_t lds_iter = 0;                        // LDS of the iterate / advance launches: lds + the resident state where it fits (rs_off != 0)
   int rs_off = 0;                             // KernelArgs::rs_off
   size_t lds_factor = 0;                      // LDS part of the resident head of S^-1, behind the resident state (iterate launches only)
-  int rf_off = 0, rf_steps = 0;               // KernelArgs::rf_off; steps per wave the head keeps (registers + LDS), 0 = streamed
+  int rf_off = 0, rf_steps = 0;               // KernelArgs::rf_off; steps per wave the head keeps (registers + LDS; of the long form unless the deep ring is forced), 0 = streamed
+  int64_t rf_launches[3] = {0, 0, 0};         // iterate launches since setup by form (RF_FORM_*; chunk iterates count one each)
   std::vector<QPNumeric> qp;
   bool host_bounds_stale = false;
   hipStream_t stream = nullptr;
@@ -468,6 +470,7 @@ static KernelArgs make_args(mi_osqp_batch *h) {
   a.cert_out = h->cert_out.p; a.cert_stride = (int)std::max<int64_t>(std::max<int64_t>(a.n, a.m), 1);
   a.xs_global = h->global_xs ? h->xs_global.p : nullptr; a.xs_len = (*h->anp).xs_total; a.wide = (*h->anp).wide ? 1 : 0;
   a.rs_off = h->rs_off; a.rf_off = h->rf_off;
+  a.rf_form = iterate_form(h->ntiles, h->rf_off != 0, h->tune);      // (solve_impl sets it per launch from the tiles still iterating)
   a.mw_groups = h->mw_groups; a.mw_bar = h->mw_bar.p; a.mw_scratch = h->mw_scratch.p;
   a.df = (*h->anp).df ? 1 : 0; a.df_shadow = (unsigned)(*h->anp).Next; a.rflag = h->rflag.p;
   {
@@ -953,13 +956,15 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
     }
   }
   // Resident head of S^-1 (iterate_body RF): a tile of ONE QP with the resident state and a dense tail keeps the first
-  // rf_head_steps() steps of every wave's first product task on chip across a segment - rf_lds_steps() of them in LDS behind
-  // the resident state where that fits the cap as well, the rest in registers (no LDS part, no head: the kernel has one form).
+  // rf_head_steps(form) steps of every wave's first product task on chip across a segment - rf_lds_steps() of them in LDS behind
+  // the resident state where that fits the cap as well, the rest in registers (no LDS part, no head).  The LDS part is the
+  // same for both forms of the head; which one a launch runs is decided launch by launch (host_core.hpp iterate_form).
   h->lds_factor = 0; h->rf_off = 0; h->rf_steps = 0;
   if (h->rs_off && BT == 1 && an.dt.k > 0 && !h->tune.stream_factor) {
     const size_t part = (size_t)(h->threads / 64) * rf_lds_steps() * 64 * sizeof(double);
     if (h->lds_iter + part <= lds_cap) {
-      h->rf_off = (int)(h->lds_iter / sizeof(double)); h->lds_factor = part; h->rf_steps = rf_head_steps();
+      h->rf_off = (int)(h->lds_iter / sizeof(double)); h->lds_factor = part;
+      h->rf_steps = rf_head_steps(h->tune.rf_form == kIterDeepRing ? RF_FORM_DEEP_RING : RF_FORM_LONG_HEAD);
     }
   }
   // ---- device arrays
@@ -1537,6 +1542,8 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
     const int nt = ch.tile_begin[c + 1] - ch.tile_begin[c];
     if (!nt) return 0;
     ai.tiles = h->tile_list.p + ch.tile_begin[c];
+    ai.rf_form = iterate_form(nt, h->rf_off != 0, h->tune);
+    h->rf_launches[ai.rf_form]++;
     HIPCHK(launch_iterate(ai, BT, nt, h->threads, h->lds_iter + h->lds_factor, st));
     return 0;
   };
@@ -1634,6 +1641,7 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
   h->last_device_s = h->last_refactor_s = 0.0;
   const int BT = h->BT, ntl = h->ntiles, nslots = ntl * BT;
   const Settings &S = h->st;
+  int iterating = ntl;        // tiles the next launch will actually iterate (the others leave at once): picks its form
   {     // QPs without a valid factor (isolated earlier) are kNonConvex from the start
     std::vector<int> bad;
     for (int q = 0; q < h->B; q++) if (h->failed[q]) bad.push_back(q);
@@ -1659,6 +1667,8 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
         if (!iterated) {
           HIPCHK(hipEventRecord(h->ev0, h->stream));
           if (h->mw_groups > 0) HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), h->stream));
+          a.rf_form = iterate_form(iterating, h->rf_off != 0, h->tune);
+          h->rf_launches[a.rf_form]++;
           HIPCHK(launch_iterate(a, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds_iter + h->lds_factor, h->stream));
           HIPCHK(hipEventRecord(h->ev1, h->stream));
         }
@@ -1726,6 +1736,8 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
         }
       }
       if (active.empty()) break;
+      iterating = 0;
+      for (size_t i = 0; i < active.size(); i++) iterating += !i || active[i] / BT != active[i - 1] / BT;
     }
     return MI_OSQP_OK;
   };
@@ -2016,6 +2028,8 @@ int mi_osqp_batch_get_stats(mi_osqp_batch *h, mi_osqp_stats *st) {
   *st = h->stats;
   st->pipelined_refactors = h->pipelined_refactors;
   st->refactor_lanes = h->refactor_lanes;
+  st->iterate_launches_deep_ring = h->rf_launches[RF_FORM_DEEP_RING];
+  st->iterate_launches_long_head = h->rf_launches[RF_FORM_LONG_HEAD];
   return MI_OSQP_OK;
 }
 
@@ -3853,6 +3867,15 @@ int mi_osqp_debug_refactor_lanes(int64_t n_flagged, const int64_t *flagged, int6
   *n_waits = (int64_t)rl.wait_chunk.size();
   std::copy(rl.wait_chunk.begin(), rl.wait_chunk.end(), wait_chunk);
   std::copy(rl.wait_for.begin(), rl.wait_for.end(), wait_for);
+  return MI_OSQP_OK;
+}
+int mi_osqp_debug_iterate_form(int64_t tiles, int64_t has_head, int64_t forced_form, int64_t long_min, int64_t *form) {
+  if (!form) return MI_OSQP_ERR_NULL;
+  if (tiles < 0 || tiles > INT32_MAX || forced_form < 0 || forced_form > 2 || long_min < -1 || long_min > INT32_MAX)
+    return MI_OSQP_ERR_INVALID_DATA;
+  Tuning t;
+  t.rf_form = (int)forced_form; t.rf_long_min = (int)long_min;
+  *form = iterate_form((int)tiles, has_head != 0, t);
   return MI_OSQP_OK;
 }
 int mi_osqp_get_stats(mi_osqp_solver *h, mi_osqp_stats *st) { return h ? mi_osqp_batch_get_stats(h->b, st) : MI_OSQP_ERR_NULL; }
