@@ -177,6 +177,7 @@ def ldl_solver(K, perm, tail=0):
         out = np.empty(N)
         out[perm] = np.concatenate([x1, x2])
         return out
+    solve.factor = (perm, h, L, d)                          # (factor_refs builds its third twin on this leading factor)
     return solve
 
 
