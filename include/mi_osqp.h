@@ -115,6 +115,7 @@ typedef struct {
   int64_t dense_tail_tasks, dense_tail_waves_used, dense_tail_wave_tasks_max;   /* deal of the dense-tail product: 64 x 64 block tasks, waves of a tile that own at least one, most tasks of one wave */
   int64_t refactor_lanes;   /* the most chunk lanes a pipelined rho-update point has run on since setup: streams that each run factor -> tail -> iterate of their chunks (1 = one refactorisation stream and one iterate stream; 0 = none pipelined yet) */
   int64_t iterate_launches_deep_ring, iterate_launches_long_head;   /* iterate launches since setup by the form of the resident head they ran (MI_OSQP_RF_FORM, MI_OSQP_RF_LONG_MIN): 16 steps resident and a product ring of 16, or resident_factor_steps (32) and a ring of 8; both 0 on a handle without a head */
+  int64_t runahead_regions, runahead_tiles, runahead_left, runahead_missed;   /* run-ahead since setup (switches, read at setup: MI_OSQP_RUNAHEAD = 0 / 1 off / on, MI_OSQP_RUNAHEAD_TILES = tiles of a group, default half the CUs, MI_OSQP_RUNAHEAD_MIN = active tiles below which no group is sent, default the CU count, MI_OSQP_RUNAHEAD_END = most segments of a chain, default up to the rho-update point after next): pipelined rho-update points that sent the active tiles furthest from convergence ahead as a chain of launches beside the region, without a host turn; tiles sent; members still active when their chain ended (they went on alone afterwards); QPs outside the groups still active after the segment that follows the region (late QPs the group did not hold) */
 } mi_osqp_stats;
 
 typedef struct mi_osqp_solver mi_osqp_solver; /* one QP  */
@@ -644,6 +645,13 @@ int mi_osqp_debug_refactor_lanes(int64_t n_flagged, const int64_t *flagged, int6
                                  int64_t chunk_qps, int64_t max_chunks, int64_t kbt, int64_t lanes, int64_t chunk0_first,
                                  int64_t scratch_slots, int64_t *n_lanes, int64_t *lane_of, int64_t *order, int64_t *order_begin,
                                  int64_t *scratch_begin, int64_t *n_waits, int64_t *wait_chunk, int64_t *wait_for);
+
+/* Host only: the run-ahead group of a rho-update point (MI_OSQP_RUNAHEAD; host_core.hpp runahead_group).  tiles[n_active] = the
+ * active tiles (no tile twice), pri_res / dua_res = their residuals (>= 0 or NaN) of the check that has just run, size = tiles
+ * of the group, min_active = no group when fewer tiles are active.  Out: *n_group and group[<= min(size, n_active)], in
+ * descending score pri / median(pri) + dua / median(dua), ties by ascending tile. */
+int mi_osqp_debug_runahead_group(int64_t n_active, const int64_t *tiles, const double *pri_res, const double *dua_res, int64_t size,
+                                 int64_t min_active, int64_t *n_group, int64_t *group);
 
 /* Host only: the form of the resident head of S^-1 one iterate launch takes (host_core.hpp iterate_form).  tiles = tiles the
  * launch iterates, has_head = the handle keeps a head, forced_form = MI_OSQP_RF_FORM (0 none, 1 deep ring, 2 long head),

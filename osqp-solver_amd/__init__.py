@@ -62,7 +62,9 @@ class Stats(C.Structure):
                 ("resident_factor_steps", C.c_int64), ("lds_bytes_factor", C.c_int64),
                 ("dense_tail_tasks", C.c_int64), ("dense_tail_waves_used", C.c_int64), ("dense_tail_wave_tasks_max", C.c_int64),
                 ("refactor_lanes", C.c_int64),
-                ("iterate_launches_deep_ring", C.c_int64), ("iterate_launches_long_head", C.c_int64)]
+                ("iterate_launches_deep_ring", C.c_int64), ("iterate_launches_long_head", C.c_int64),
+                ("runahead_regions", C.c_int64), ("runahead_tiles", C.c_int64), ("runahead_left", C.c_int64),
+                ("runahead_missed", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -202,6 +204,7 @@ def lib():
                                                    C.POINTER(Settings), C.c_int64, dp, dp, dp, C.POINTER(Stats)]
         L.mi_osqp_debug_refactor_chunks.argtypes = [C.c_int64, ip, C.c_int64, ip, C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip]
         L.mi_osqp_debug_refactor_lanes.argtypes = [C.c_int64, ip, C.c_int64, ip] + [C.c_int64] * 7 + [ip] * 8
+        L.mi_osqp_debug_runahead_group.argtypes = [C.c_int64, ip, dp, dp, C.c_int64, C.c_int64, ip, ip]
         L.mi_osqp_debug_iterate_form.argtypes = [C.c_int64] * 4 + [ip]
         L.mi_osqp_prefetch_analysis.argtypes = [C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip, C.c_int64]
         L.mi_osqp_debug_host_block_factor.argtypes = [C.c_int64, C.c_int64, ip, ip, dp, ip, ip, dp, dp, dp,
@@ -933,6 +936,19 @@ def debug_refactor_lanes(flagged, active, tile, chunk_qps, lanes, kbt=None, chun
     return dict(n_lanes=L, lane_of=lane_of[:k].tolist(), order=[order[ob[l]:ob[l + 1]].tolist() for l in range(L)],
                 scratch=[(int(sb[c]), (len(work[c]) + kbt - 1) // kbt * kbt) for c in range(k)],
                 waits=list(zip(wc[:nw.value].tolist(), wf[:nw.value].tolist())))
+
+
+def debug_runahead_group(tiles, pri_res, dua_res, size, min_active):
+    """Host-only: the run-ahead group of a rho-update point (MI_OSQP_RUNAHEAD).  tiles: the active tiles; pri_res / dua_res:
+    their residuals of the check that has just run; size: tiles of the group; min_active: no group when fewer tiles are
+    active.  Returns the group's tiles in descending score pri / median(pri) + dua / median(dua), ties by ascending tile."""
+    t, p, d = _i64(tiles), _f64(pri_res), _f64(dua_res)
+    if not (len(t) == len(p) == len(d)):
+        raise ValueError("tiles, pri_res and dua_res differ in length")
+    ng = C.c_int64()
+    out = np.zeros(max(1, len(t)), dtype=np.int64)
+    _chk(lib().mi_osqp_debug_runahead_group(len(t), _ip(t), _dp(p), _dp(d), size, min_active, C.byref(ng), _ip(out)), "debug_runahead_group")
+    return out[:ng.value].tolist()
 
 
 def debug_iterate_form(tiles, has_head=True, forced_form=0, long_min=-1):

@@ -86,9 +86,12 @@ struct KernelArgs {
   // per-QP entry points (continuous batching): sel[slot] = 0: the slot is not addressed by this launch, j + 1: it is, and
   // its input is row j of the launch's QP-major argument.  null = every QP, row = QP id.
   const int *sel;
-  // iterate launches over a list of tiles (the chunks of a pipelined refactorisation, solver.hip): workgroup j serves tile
-  // tiles[j].  null = the identity.
+  // iterate / check launches over a list of tiles (the chunks of a pipelined refactorisation, a run-ahead group, solver.hip):
+  // workgroup j serves tile tiles[j].  null = the identity.
   const int *tiles;
+  // check launches of a blocking solve that may send a group of QPs ahead (solver.hip "run-ahead"): [slot][2] = pri_res, dua_res
+  // of every QP that is still running behind this check.  null = not stored.
+  double *res;
 };
 
 // device block refactorisation (row E13); tables are host_core.hpp BlockFactor
@@ -258,6 +261,8 @@ hipError_t launch_fresh_slots(const KernelArgs &a, const int *slots, int nslots,
 hipError_t launch_set_rho_slots(const KernelArgs &a, const int *slots, const double *rho, double rho_all, int nslots, int BT, hipStream_t st);
 // work[0 .. nslots) = the slots whose rho changed (IS_NEED_REFACTOR = 1: paused, or finished at max_iter; any order), then -1
 hipError_t launch_worklist(const int *iscal, int *work, int nslots, int BT, hipStream_t st);
+// the same among the listed slots only: work[0 .. nlist) = those of slots[0 .. nlist) whose rho changed, in list order, then -1
+hipError_t launch_worklist_of(const int *iscal, const int *slots, int *work, int nlist, int BT, hipStream_t st);
 // paused slots: resume (flag 0) or, when the refactorisation lost the inertia (flag -1), kNonConvex at their own iteration count
 hipError_t launch_resume_flagged(const KernelArgs &a, int nslots, int BT, hipStream_t st);
 // dst[slot] = src[slot] for the listed slots: [slot][per] streams / [tile][len][BT] interleaved arrays
@@ -295,8 +300,9 @@ struct GompArgs {
 hipError_t launch_gomp_relinearise(const GompArgs &g, hipStream_t st);
 hipError_t launch_gather_status(const int *iscal, int32_t *status, int32_t *iters, int B, int BT, hipStream_t st);
 hipError_t launch_fail_slots(const KernelArgs &a, const int *slots, int nfail, int BT, int iter, hipStream_t st);
-// the same for every listed slot (slots[j] < 0: none) whose new factor lost its inertia (IS_NEED_REFACTOR < 0), decided on the device
-hipError_t launch_fail_flagged(const KernelArgs &a, const int *slots, int nslots, int BT, int iter, hipStream_t st);
+// the same for every listed slot (slots[j] < 0: none) whose new factor lost its inertia (IS_NEED_REFACTOR < 0), decided on the device;
+// mark != null: mark[slot] = 1 for every slot it fails
+hipError_t launch_fail_flagged(const KernelArgs &a, const int *slots, int nslots, int BT, int iter, hipStream_t st, int *mark = nullptr);
 hipError_t launch_bounds(const double *gl, const double *gu, double *l, double *u, const double *Esc,
                          const double *rho_vec, const double *dscal, int *changed, int B, int m, int BT,
                          int scaling, hipStream_t st);

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <numeric>
 #include <set>
 #include <chrono>
@@ -1041,6 +1042,10 @@ Tuning tuning_from_env() {
   if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNK_QPS")) t.pipeline_chunk_qps = std::max(0, atoi(e));
   if (const char *e = getenv("MI_OSQP_REFACTOR_LANES")) t.refactor_lanes = std::max(1, std::min(3, atoi(e)));
   if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNK0")) t.lanes_chunk0 = atoi(e) != 0;
+  if (const char *e = getenv("MI_OSQP_RUNAHEAD")) t.runahead = atoi(e) != 0;
+  if (const char *e = getenv("MI_OSQP_RUNAHEAD_TILES")) t.runahead_tiles = std::max(0, atoi(e));
+  if (const char *e = getenv("MI_OSQP_RUNAHEAD_MIN")) t.runahead_min = std::max(0, atoi(e));
+  if (const char *e = getenv("MI_OSQP_RUNAHEAD_END")) t.runahead_end = std::max(0, atoi(e));
   if (const char *e = getenv("MI_OSQP_RF_FORM")) { const int v = atoi(e); if (v == kIterDeepRing || v == kIterLongHead) t.rf_form = v; }
   if (const char *e = getenv("MI_OSQP_RF_LONG_MIN")) t.rf_long_min = std::max(0, atoi(e));
   AnalysisTuning &a = t.analysis;
@@ -1117,6 +1122,30 @@ RefactorLanes refactor_lanes(const RefactorChunks &ch, const std::vector<int> &f
     for (int d = 1; d < c; d++) if (need[d]) { rl.wait_chunk.push_back(c); rl.wait_for.push_back(d); }
   }
   return rl;
+}
+
+std::vector<int> runahead_group(const std::vector<int> &tiles, const std::vector<double> &pri, const std::vector<double> &dua, int size, int min_active) {
+  const size_t na = tiles.size();
+  if (!na || size <= 0 || na < (size_t)std::max(0, min_active) || pri.size() != na || dua.size() != na) return {};
+  const double inf = std::numeric_limits<double>::infinity();
+  auto scaled = [&](const std::vector<double> &r) {       // r / median(r)
+    std::vector<double> v(na);
+    for (size_t i = 0; i < na; i++) v[i] = std::isnan(r[i]) ? inf : r[i];
+    std::vector<double> s = v;
+    std::nth_element(s.begin(), s.begin() + na / 2, s.end());
+    const double med = s[na / 2];
+    for (size_t i = 0; i < na; i++) v[i] = v[i] == inf ? inf : med == inf ? 0.0 : med > 0.0 ? v[i] / med : v[i] > 0.0 ? inf : 0.0;
+    return v;
+  };
+  const std::vector<double> sp = scaled(pri), sd = scaled(dua);
+  std::vector<std::pair<double, int>> order(na);
+  for (size_t i = 0; i < na; i++) order[i] = {sp[i] + sd[i], tiles[i]};
+  std::sort(order.begin(), order.end(), [](const std::pair<double, int> &x, const std::pair<double, int> &y) {
+    return x.first > y.first || (x.first == y.first && x.second < y.second);
+  });
+  std::vector<int> group(std::min(na, (size_t)size));
+  for (size_t i = 0; i < group.size(); i++) group[i] = order[i].second;
+  return group;
 }
 
 int iterate_form(int tiles, bool has_head, const Tuning &t) {

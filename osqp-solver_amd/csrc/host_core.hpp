@@ -45,6 +45,7 @@ struct AnalysisTuning {            // what analyze() reads
     return dense_tail == o.dense_tail && ordering == o.ordering && nd_leaf == o.nd_leaf && relax == o.relax && serial == o.serial;
   }
 };
+constexpr bool kRunaheadDefault = true;      // (measured: DESIGN.md section 4, "Measurements (run-ahead)")
 struct Tuning {
   int tile = 0;                    // MI_OSQP_TILE: 1, 2 or 4 QPs per tile
   int threads = 0;                 // MI_OSQP_THREADS: threads per tile of the solve kernels (64 .. 1024)
@@ -67,6 +68,11 @@ struct Tuning {
                                    // both 0 (the measured default): the fewest even chunks of at most one QP per CU - 3 x 202 for 605 QPs
   int refactor_lanes = 0;          // MI_OSQP_REFACTOR_LANES: 1 .. 3 chunk lanes (refactor_lanes below); 1 = the two-stream form; 0 = the default
   int lanes_chunk0 = -1;           // MI_OSQP_REFACTOR_CHUNK0: 1 chunk 0 in front of the last lane, 0 behind the shortest lane; -1 = the default
+  // the QPs furthest from convergence at a pipelined rho-update point run ahead beside the region (runahead_group below)
+  bool runahead = kRunaheadDefault;  // MI_OSQP_RUNAHEAD=0 / 1: off / on
+  int runahead_tiles = 0;          // MI_OSQP_RUNAHEAD_TILES: tiles of the group (0 = the default, half the CUs)
+  int runahead_min = 0;            // MI_OSQP_RUNAHEAD_MIN: no group unless at least so many tiles are active (0 = the CU count)
+  int runahead_end = 0;            // MI_OSQP_RUNAHEAD_END: the chain runs at most so many segments (0 = to the rho-update point after next)
   // form of the resident head of S^-1 per iterate launch (iterate_form below)
   int rf_form = 0;                 // MI_OSQP_RF_FORM: 1 the deep ring, 2 the long head in every launch of the handle; 0 = by the threshold
   int rf_long_min = -1;            // MI_OSQP_RF_LONG_MIN: launches that iterate at least so many tiles take the long head (0 = every launch); -1 = the default, kRfLongMinDefault
@@ -117,7 +123,17 @@ struct RefactorLanes {
 };
 RefactorLanes refactor_lanes(const RefactorChunks &ch, const std::vector<int> &flagged, int bt, int kbt, int lanes, bool chunk0_first, int scratch_slots);
 
-// One pull-schedule: every target row t gets  xs[t] -= sum_k val[k] * xs[idx[k]]  (or xs[t] = sum, "store").
+// The run-ahead group of a rho-update point: the tiles (of one QP each) that are likely to need the most further iterations,
+// which then run their refactorisation and the segments after it as a chain of their own beside the pipelined region
+// (solver.hip "run-ahead").  tiles = the active tiles (any order, no tile twice), pri / dua = the residuals of the check that
+// has just run, entry by entry those of tiles[] - nothing else is looked at, in particular nothing an earlier solve left.
+// Score of a tile: pri / median(pri) + dua / median(dua), the medians (the upper one of an even count) over the active tiles,
+// so neither the units of the problem nor which of the two residuals lags decides.  NaN counts as +inf; with a zero median
+// a residual above it counts as +inf and one at it as 0.  Returns the min(size, active) tiles of the highest score in
+// descending score, ties by ascending tile; nothing when fewer than min_active tiles are active or size <= 0.
+std::vector<int> runahead_group(const std::vector<int> &tiles, const std::vector<double> &pri, const std::vector<double> &dua, int size, int min_active);
+
+// One pull-schedule: every target row t gets xs[t] -= sum_k val[k] * xs[idx[k]]  (or xs[t] = sum, "store").
 //
 // Work is organised as PHASES separated by workgroup barriers; in every phase each of the nw waves owns one
 // (possibly empty) contiguous range of wave-steps (64 lanes, one slot per lane).  A step (descriptor layout:

@@ -1195,7 +1195,7 @@ __device__ __forceinline__ int check_body(const KernelArgs &a, double *smem, int
   bool dfm = false;
   if constexpr (GX && BT == 1 && WIDE) dfm = a.df != 0 && a.mw_groups > 1;
   const Mw mw{a.mw_bar, dfm ? (unsigned)a.mw_groups : 1u};
-  const int tile = dfm ? 0 : blockIdx.x;
+  const int tile = dfm ? 0 : (a.tiles ? a.tiles[blockIdx.x] : (int)blockIdx.x);
   const int ltid = threadIdx.x, lwave = __builtin_amdgcn_readfirstlane(ltid >> 6), lnw = blockDim.x >> 6;
   const int tid = dfm ? blockIdx.x * blockDim.x + threadIdx.x : threadIdx.x, nthr = dfm ? blockDim.x * mw.G : blockDim.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nthr >> 6;
@@ -1419,6 +1419,8 @@ __device__ __forceinline__ int check_body(const KernelArgs &a, double *smem, int
     p.iscal[IS_RHO_UPDATES * BT + b] = rho_updates;
     if (!was_done) { p.iscal[IS_NEED_REFACTOR * BT + b] = need_refactor; p.iscal[IS_CUR * BT + b] = iter; }
     p.dscal[DS_RHO * BT + b] = rho;
+    // how far a QP that goes on is from its tolerances: what the host ranks the run-ahead group by (KernelArgs::res)
+    if (a.res && !done && qp >= 0) { a.res[2 * (size_t)qp] = pri_res; a.res[2 * (size_t)qp + 1] = dua_res; }
   }
   int ev = (just_done ? 1 : 0) | (need_refactor ? 2 : 0);
   if constexpr (BT > 1) ev = (__syncthreads_or(ev & 1) ? 1 : 0) | (__syncthreads_or(ev & 2) ? 2 : 0);
@@ -3244,18 +3246,18 @@ __device__ __forceinline__ void fail_one_slot(const KernelArgs &a, int slot, int
 }
 // fail_slots_kernel behind a refactorisation whose flags the host has not read: one workgroup per slot of its work list, of
 // which those whose new factor lost its inertia (IS_NEED_REFACTOR < 0) fail.  The flag goes back to 0, the status tells the host.
-__global__ void fail_flagged_kernel(KernelArgs a, const int *__restrict__ slots, int BT, int iter) {
+__global__ void fail_flagged_kernel(KernelArgs a, const int *__restrict__ slots, int BT, int iter, int *mark) {
   const int slot = slots[blockIdx.x];
   if (slot < 0) return;
   int *flag = a.iscal + ((size_t)slot / BT) * IS_COUNT * BT + IS_NEED_REFACTOR * BT + (size_t)slot % BT;
   if (*flag >= 0) return;
   fail_one_slot(a, slot, BT, iter, threadIdx.x, blockDim.x);
   __syncthreads();            // (every thread has read the flag)
-  if (threadIdx.x == 0) *flag = 0;
+  if (threadIdx.x == 0) { *flag = 0; if (mark) mark[slot] = 1; }
 }
-hipError_t launch_fail_flagged(const KernelArgs &a, const int *slots, int nslots, int BT, int iter, hipStream_t st) {
+hipError_t launch_fail_flagged(const KernelArgs &a, const int *slots, int nslots, int BT, int iter, hipStream_t st, int *mark) {
   if (nslots <= 0) return hipSuccess;
-  hipLaunchKernelGGL(fail_flagged_kernel, dim3(nslots), dim3(256), 0, st, a, slots, BT, iter);
+  hipLaunchKernelGGL(fail_flagged_kernel, dim3(nslots), dim3(256), 0, st, a, slots, BT, iter, mark);
   return hipGetLastError();
 }
 // Solve() entry of the listed QPs ([EXT] osqp_solve: status unsolved, iteration count 0; warm_start off: cold iterates).
@@ -3346,6 +3348,32 @@ __global__ __launch_bounds__(1024) void worklist_kernel(const int *__restrict__ 
 }
 hipError_t launch_worklist(const int *iscal, int *work, int nslots, int BT, hipStream_t st) {
   hipLaunchKernelGGL(worklist_kernel, dim3(1), dim3(1024), 0, st, iscal, work, nslots, BT);
+  return hipGetLastError();
+}
+// The same among a list of slots (the run-ahead group at a rho-update point inside its chain, solver.hip): the flagged ones of
+// slots[0 .. nlist) in list order - so the list, and with it every QP's place in the scratch, is the same in every run - then -1.
+// One workgroup: the flags of 1024 entries at a time, packed by thread 0.
+__global__ __launch_bounds__(1024) void worklist_of_kernel(const int *__restrict__ iscal, const int *__restrict__ slots, int *work, int nlist, int BT) {
+  __shared__ int s_flag[1024];
+  int cnt = 0;
+  for (int base = 0; base < nlist; base += 1024) {
+    const int j = base + (int)threadIdx.x;
+    int f = 0;
+    if (j < nlist) {
+      const int s = slots[j];
+      f = s >= 0 && iscal[(size_t)(s / BT) * IS_COUNT * BT + IS_NEED_REFACTOR * BT + s % BT] == 1;
+    }
+    s_flag[threadIdx.x] = f;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int k = 0; k < 1024 && base + k < nlist; k++) if (s_flag[k]) work[cnt++] = slots[base + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) for (int k = cnt; k < nlist; k++) work[k] = -1;
+}
+hipError_t launch_worklist_of(const int *iscal, const int *slots, int *work, int nlist, int BT, hipStream_t st) {
+  if (nlist <= 0) return hipSuccess;
+  hipLaunchKernelGGL(worklist_of_kernel, dim3(1), dim3(1024), 0, st, iscal, slots, work, nlist, BT);
   return hipGetLastError();
 }
 // After the refactorisations of the paused slots: flag 0 - the solve goes on with the next advance launch (pending mark 1);

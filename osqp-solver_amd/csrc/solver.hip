@@ -334,6 +334,14 @@ struct mi_osqp_batch {
   DevBuf<int> tile_list;                      // the active tiles chunk after chunk (KernelArgs::tiles)
   int64_t pipelined_refactors = 0;            // rho-update points of this handle that took the pipelined form
   int64_t refactor_lanes = 0;                 // the most chunk lanes one of them ran on (1 = the two-stream form)
+  // run-ahead (solve_impl): five lists of ntiles entries - the tiles of the main loop's launches, the group, the group's
+  // flagged slots, the device-built work list of the chain, the marks of the slots the chain failed - and the residuals of
+  // the running QPs (KernelArgs::res)
+  DevBuf<int> ra_list;
+  DevBuf<double> ra_res;
+  double *h_res = nullptr; int *h_mark = nullptr;      // pinned images of ra_res and of the marks
+  size_t h_res_cap = 0, h_mark_cap = 0;
+  int64_t ra_regions = 0, ra_tiles = 0, ra_left = 0, ra_missed = 0;      // mi_osqp_stats runahead_*
   double factor_ms_sum = 0.0, dense_ms_sum = 0.0;
   int64_t refactor_launches = 0, refactor_qps = 0, peak_qps = 0;
   double peak_factor_ms = 0.0, peak_tail_ms = 0.0;
@@ -412,6 +420,7 @@ struct mi_osqp_batch {
     if (evp1) (void)hipEventDestroy(evp1);
     hostpool::give(cont.h_done, cont.h_done_cap); hostpool::give(cont.h_pstat, cont.h_pstat_cap);
     hostpool::give(h_iscal, h_iscal_cap); hostpool::give(h_dscal, h_dscal_cap); hostpool::give(pin, pin_cap); hostpool::give(h_npos, h_npos_cap);
+    hostpool::give(h_res, h_res_cap); hostpool::give(h_mark, h_mark_cap);
     if (pipe_r) (void)hipStreamSynchronize(pipe_r);
     if (pipe_i) (void)hipStreamSynchronize(pipe_i);
     if (pipe_x) (void)hipStreamSynchronize(pipe_x);
@@ -1476,11 +1485,53 @@ static bool pipeline_applies(const mi_osqp_batch *h, int n_ref) {
   return h->tune.refactor_pipeline && n_ref > longer_than && h->mw_groups <= 0 && !h->global_xs && !(*h->anp).wide && !(*h->anp).df;
 }
 
+// ---- run-ahead ("Run-ahead"): the last few QPs of a batch need several segments more than everyone else,
+// and a lone tile's segment is a latency chain that leaves the other CUs idle.  At a pipelined rho-update point the tiles
+// furthest from convergence (host_core.hpp runahead_group, from the residuals the check has just stored: KernelArgs::res) leave
+// the region: their flagged slots leave its work list, their tiles its chunks.  They run as a chain on the solve stream - idle
+// until the join otherwise - beside the lanes and past them, without a host turn: factor -> tail -> fail_flagged of the
+// group's flagged slots,
+// then per segment iterate_kernel + check_kernel over the group's tile list and, at a rho-update point inside the chain,
+// worklist_of_kernel -> factor -> tail -> fail_flagged over a device-built list (grid = the group; a workgroup whose entry is
+// -1 leaves at once).  The chain ends at the rho-update point after next or at max_iter - without a refactorisation there -
+// and the waits for the lanes follow it.  (A stream of its own for the chain was measured first: a fifth stream of the
+// process shares a hardware queue with a lane, and the chain then waits for that lane's kernels - DESIGN.md section 4.)
+// Every QP sees the same kernels on the same data in the same order as without
+// run-ahead; only when it runs changes.  The scratch of the chain's refactorisations sits behind the region's in the scratch
+// buffers (wg_base): the region's flagged slots and the group's tiles are different QPs, so both fit.
+// One QP per tile and at most two chunk lanes only (with the chain three streams run side by side), once per solve.
+struct RunAhead {
+  bool open = false;                    // a chain is enqueued and the host has not read its flags yet
+  bool used = false;                    // this solve has sent a group ahead
+  int chk_threads = 0;                  // threads of the check launches (those of the solve's other checks)
+  std::vector<int> points;              // the ends of the chain's segments; back() = where the chain ends
+  std::vector<int> group, rest, work;   // the group's tiles in descending score; every other tile, ascending; the group's flagged slots
+  std::vector<int> ru0;                 // IS_RHO_UPDATES of the group's QPs in front of the chain
+};
+// the default of MI_OSQP_RUNAHEAD_TILES in quarters of the CU count (measured among 64, 128 and 192 tiles at the headline batch,
+// DESIGN.md section 4; half the CUs held every late QP of that batch in the oracle's residuals)
+constexpr int kRunaheadQuarters = 2;
+static bool runahead_applies(const mi_osqp_batch *h) {
+  const int lanes = h->tune.refactor_lanes > 0 ? h->tune.refactor_lanes : kDefaultLanes;
+  return h->tune.runahead && h->tune.refactor_pipeline && h->BT == 1 && lanes <= 2 && h->st.adaptive_rho && h->st.adaptive_rho_interval > 0 &&
+         h->mw_groups <= 0 && !h->global_xs && !(*h->anp).wide && !(*h->anp).df;
+}
+static int ensure_runahead_buffers(mi_osqp_batch *h) {
+  int rc;
+  if (!h->ra_list.p && (rc = h->ra_list.alloc((size_t)5 * h->ntiles))) return rc;
+  if (!h->ra_res.p && (rc = h->ra_res.alloc((size_t)2 * h->ntiles))) return rc;
+  if (!h->h_res) HIPCHK(hostpool::alloc((void **)&h->h_res, (size_t)2 * h->ntiles * sizeof(double), &h->h_res_cap));
+  if (!h->h_mark) HIPCHK(hostpool::alloc((void **)&h->h_mark, (size_t)h->ntiles * sizeof(int), &h->h_mark_cap));
+  return 0;
+}
+
 // Enqueues the refactorisation of the slots of `work`, iterations (a.iter_begin, a.iter_end] of the tiles that hold a slot of
 // `active` and, behind the join, the failure of the slots whose new factor has the wrong inertia (their iterate left them
 // alone, tile_ptrs) at iteration a.iter_begin.  Nothing is synchronised: the caller enqueues the check, reads the flags and
 // calls pipelined_region_finish.  Accounting: see mi_osqp_batch_last_solve_stats / DESIGN.md section 4.
-static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, const std::vector<int> &work, const std::vector<int> &active, PipeRegion *pr) {
+// ra != null: `work` and `active` are without the run-ahead group *ra, whose chain is enqueued beside the region.
+static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, const std::vector<int> &work, const std::vector<int> &active, PipeRegion *pr,
+                                      const RunAhead *ra = nullptr) {
   using streampool::kPipeChunks; using streampool::kPipeEvents; using streampool::kPipeLanes;
   const double t_begin = now_s();
   const int BT = h->BT, nq = (int)work.size();
@@ -1504,6 +1555,7 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
                                           h->ntiles * BT + 4);      // (what Lblk, Dl, dinv_scratch and dt_Sd hold: setup)
   const int L = rl.n_lanes;
   if (L > 2 && !h->pipe_x) HIPCHK(hipStreamCreateWithFlags(&h->pipe_x, hipStreamNonBlocking));
+  if (ra && (L > 2 || BT != 1)) { g_last_error = "run-ahead beside three chunk lanes / tiles of several QPs"; return MI_OSQP_ERR_INVALID_SETTINGS; }
   std::vector<int> &wl = pr->wl;
   std::vector<int> wl_begin(1, 0);
   wl.clear();
@@ -1517,6 +1569,16 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
   if (h->tile_list.n < ch.tiles.size() && (rc = h->tile_list.alloc((size_t)h->ntiles))) return rc;
   HIPCHK(hipMemcpyAsync(h->work.p, wl.data(), wl.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->tile_list.p, pr->tiles.data(), pr->tiles.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  // the lists of the run-ahead chain (mi_osqp_batch::ra_list; ensure_runahead_buffers has run)
+  const int ntl = h->ntiles, G = ra ? (int)ra->group.size() : 0, gw = ra ? (int)ra->work.size() : 0;
+  int *d_rest = h->ra_list.p, *d_group = d_rest + ntl, *d_gwork = d_rest + 2 * (size_t)ntl, *d_dwork = d_rest + 3 * (size_t)ntl, *d_mark = d_rest + 4 * (size_t)ntl;
+  if (ra) {
+    if (!h->ra_list.p || G <= 0 || G + (int)ra->rest.size() != ntl || gw > G || nq + G > ntl + 4) { g_last_error = "run-ahead: inconsistent lists"; return MI_OSQP_ERR_INVALID_SETTINGS; }
+    if (!ra->rest.empty()) HIPCHK(hipMemcpyAsync(d_rest, ra->rest.data(), ra->rest.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_group, ra->group.data(), (size_t)G * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (gw) HIPCHK(hipMemcpyAsync(d_gwork, ra->work.data(), (size_t)gw * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(d_mark, 0, (size_t)ntl * sizeof(int), h->stream));
+  }
   pr->host_s = now_s() - t_begin;
   HIPCHK(hipEventRecord(ev_fork, h->stream));
   FactorArgs fa = make_factor_args(h, 0);
@@ -1547,6 +1609,42 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
     HIPCHK(launch_iterate(ai, BT, nt, h->threads, h->lds_iter + h->lds_factor, st));
     return 0;
   };
+  // ---- the run-ahead chain on the solve stream, which has nothing else to do until the join: its first refactorisation and
+  // segment are enqueued in front of the region's launches (the chain is the longer path), the rest behind them and in front
+  // of the waits of the join
+  hipStream_t sx = h->stream;
+  KernelArgs ac = a;
+  ac.tiles = d_group; ac.res = nullptr; ac.info_at_end = 1;
+  FactorArgs fg = make_factor_args(h, 0);
+  fg.wg_base = nq;                      // behind the scratch of the region's whole work list (kbt = 1: a slot per workgroup)
+  auto chain_refactor = [&](const int *list, int n, int iter) -> int {
+    if (n <= 0) return 0;
+    fg.work = list;
+    HIPCHK(launch_factor(fg, 1, n, h->tune.factor_threads, sx));
+    if (tail) {
+      TailArgs da = make_tail_args(h, 1, list);
+      da.wg_base = nq;
+      HIPCHK(launch_tail(da, n, h->dt_lds_asm, h->dt_lds, sx));
+    }
+    HIPCHK(launch_fail_flagged(a, list, n, BT, iter, sx, d_mark));
+    return 0;
+  };
+  auto chain_segment = [&](size_t k) -> int {
+    ac.iter_begin = k ? ra->points[k - 1] : a.iter_begin; ac.iter_end = ra->points[k];
+    ac.rf_form = iterate_form(G, h->rf_off != 0, h->tune);
+    h->rf_launches[ac.rf_form]++;
+    HIPCHK(launch_iterate(ac, BT, G, h->threads, h->lds_iter + h->lds_factor, sx));
+    HIPCHK(launch_check(ac, BT, G, ra->chk_threads, h->lds, sx));
+    const int e = ra->points[k];
+    if (k + 1 < ra->points.size() && e % (int)h->st.adaptive_rho_interval == 0) {      // a rho-update point inside the chain
+      HIPCHK(launch_worklist_of(h->iscal.p, d_group, d_dwork, G, BT, sx));
+      return chain_refactor(d_dwork, G, e);
+    }
+    return 0;
+  };
+  if (ra) {
+    if ((rc = chain_refactor(d_gwork, gw, a.iter_begin)) || (rc = chain_segment(0))) return rc;
+  }
   pr->lane_last.assign(L, 0);
   if (L == 1) {
     HIPCHK(hipStreamWaitEvent(h->pipe_r, ev_fork, 0));
@@ -1562,7 +1660,6 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
     }
     // ---- join (stream I has waited for every chunk of R)
     HIPCHK(hipEventRecord(ev_lane(0), h->pipe_i));
-    HIPCHK(hipStreamWaitEvent(h->stream, ev_lane(0), 0));
   } else {
     hipStream_t lane[kPipeLanes] = {h->pipe_r, h->pipe_i, h->pipe_x};
     for (int l = 0; l < L; l++) HIPCHK(hipStreamWaitEvent(lane[l], ev_fork, 0));
@@ -1578,8 +1675,10 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
     }
     if (!chunk0_first && (rc = enqueue_iterate(0, lane[rl.lane_of[0]]))) return rc;
     // ---- join
-    for (int l = 0; l < L; l++) { HIPCHK(hipEventRecord(ev_lane(l), lane[l])); HIPCHK(hipStreamWaitEvent(h->stream, ev_lane(l), 0)); }
+    for (int l = 0; l < L; l++) HIPCHK(hipEventRecord(ev_lane(l), lane[l]));
   }
+  if (ra) for (size_t k = 1; k < ra->points.size(); k++) if ((rc = chain_segment(k))) return rc;      // the rest of the chain
+  for (int l = 0; l < L; l++) HIPCHK(hipStreamWaitEvent(h->stream, ev_lane(l), 0));
   HIPCHK(hipEventRecord(ev_join, h->stream));
   // a rho update that makes the factor lose its inertia ends THAT QP as kNonConvex ([EXT] osqp_solve: adapt_rho fails ->
   // OSQP_NON_CVX, break); every other QP of the batch goes on
@@ -1654,13 +1753,37 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
       seg_end = std::min<int64_t>(seg_end, (iter / S.adaptive_rho_interval + 1) * S.adaptive_rho_interval);
     return seg_end;
   };
+  // run-ahead (above pipelined_refactor_iterate): the checks of this solve store the residuals of the running QPs
+  const int ra_min = h->tune.runahead_min > 0 ? h->tune.runahead_min : h->n_cus;
+  if (runahead_applies(h) && ntl > 1 && ntl >= ra_min) {
+    if ((rc = ensure_runahead_buffers(h))) return rc;
+    a.res = h->ra_res.p;
+  }
+  auto is_rho_point = [&](int iter) { return S.adaptive_rho && S.adaptive_rho_interval > 0 && iter % S.adaptive_rho_interval == 0; };
   auto loop = [&]() -> int {
     int iter = 0;
     bool iterated = false;       // the segment's iterations have run already, pipelined with the refactorisation before them
     PipeRegion region;           // ... and this is that region, enqueued and not yet accounted for
-    while (true) {
-      const int seg_end = segment_end(iter);
-      a.iter_begin = iter; a.iter_end = seg_end; a.info_at_end = 1;
+    // run-ahead: the group whose chain is enqueued beside the region.  Behind the chain the launches serve the tiles of a list
+    // (d_tiles, n_launch of them) and the host looks at the slots that are not held: first everyone but the members the chain
+    // left - at its end, or finished there at max_iter with a rho update to refactor - then those alone (`left`, ascending).
+    RunAhead ra;
+    std::vector<char> held;
+    std::vector<int> left;
+    const int *d_tiles = nullptr;
+    int n_launch = ntl, res_iter = -1;
+    bool leftovers_phase = false;
+    auto check_threads = [&]() {
+      // The check of more 16-wave tiles than the CUs hold at once (two each) runs in 8-wave workgroups - four per CU, one round
+      // instead of two; the check schedule is walked stream by stream by however many waves there are, row by row in the
+      // same order (headline batch: 0.19 -> 0.11 ms per check, 31.8 -> 31.5 ms per step).
+      int chk_threads = h->mw_groups > 0 ? h->mw_threads : h->threads;
+      if (h->mw_groups <= 0 && h->threads == 1024 && ntl > 2 * h->n_cus) chk_threads = 512;
+      return chk_threads;
+    };
+    // ---- one segment on the device: iterations (iter, seg_end] unless a region has run them, the check, the flags to the host
+    auto device_turn = [&](int seg_end) -> int {
+      a.iter_begin = iter; a.iter_end = seg_end; a.info_at_end = 1; a.tiles = d_tiles;
       {
         std::unique_lock<std::mutex> spin_lock(spin_mutex(h->device), std::defer_lock);
         if (h->mw_groups > 0) spin_lock.lock();
@@ -1669,18 +1792,18 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
           if (h->mw_groups > 0) HIPCHK(hipMemsetAsync(h->mw_bar.p, 0, 4 * sizeof(uint32_t), h->stream));
           a.rf_form = iterate_form(iterating, h->rf_off != 0, h->tune);
           h->rf_launches[a.rf_form]++;
-          HIPCHK(launch_iterate(a, BT, ntl, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds_iter + h->lds_factor, h->stream));
+          HIPCHK(launch_iterate(a, BT, n_launch, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds_iter + h->lds_factor, h->stream));
           HIPCHK(hipEventRecord(h->ev1, h->stream));
         }
-        {
-          // The check of more 16-wave tiles than the CUs hold at once (two each) runs in 8-wave workgroups - four per CU, one round
-          // instead of two; the check schedule is walked stream by stream by however many waves there are, row by row in the
-          // same order (headline batch: 0.19 -> 0.11 ms per check, 31.8 -> 31.5 ms per step).
-          int chk_threads = h->mw_groups > 0 ? h->mw_threads : h->threads;
-          if (h->mw_groups <= 0 && h->threads == 1024 && ntl > 2 * h->n_cus) chk_threads = 512;
-          HIPCHK(launch_check(a, BT, ntl, chk_threads, h->lds, h->stream));
-        }
+        HIPCHK(launch_check(a, BT, n_launch, check_threads(), h->lds, h->stream));
         HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)ntl * IS_COUNT * BT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        // run-ahead: the residuals of the running QPs behind the check of a rho-update point (a group may be chosen from them);
+        // behind a chain the marks of the slots it failed
+        if (a.res && !ra.used && is_rho_point(seg_end) && seg_end < S.max_iter) {
+          HIPCHK(hipMemcpyAsync(h->h_res, h->ra_res.p, (size_t)2 * ntl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+          res_iter = seg_end;
+        }
+        if (ra.open) HIPCHK(hipMemcpyAsync(h->h_mark, h->ra_list.p + 4 * (size_t)ntl, (size_t)ntl * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
       }
       if ((rc = mw_barrier_ok(h))) {
@@ -1697,18 +1820,47 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
         h->last_device_s += ms * 1e-3; h->kernel_ms_sum += ms; h->kernel_launches++; h->last_launches++;
       } else if ((rc = pipelined_region_finish(h, &region))) return rc;
       iterated = false;
-      iter = seg_end;
+      if (ra.open) {
+        // Behind the chain: its members are finished or at the chain's end.  The refactorisations inside the chain are the
+        // rho updates the members have counted since, less those the chain's last check asked for (the host runs them, with
+        // the leftovers); the slots the chain failed are marked; who is left waits for the others to finish.
+        ra.open = false;
+        int64_t inner = 0, n_left = 0;
+        for (size_t i = 0; i < ra.group.size(); i++) {
+          const int t = ra.group[i];
+          const int *f = h->h_iscal + (size_t)t * IS_COUNT;
+          const bool flagged = f[IS_NEED_REFACTOR] == 1;
+          inner += f[IS_RHO_UPDATES] - ra.ru0[i] - (flagged ? 1 : 0);
+          if (h->h_mark[t]) h->failed[(size_t)t] = 1;
+          n_left += !f[IS_DONE];
+          if (!f[IS_DONE] || flagged) left.push_back(t);
+        }
+        std::sort(left.begin(), left.end());
+        h->last_refactors += inner; h->refactor_qps += (int64_t)ra.work.size() + inner;
+        h->ra_left += n_left;
+        if (left.empty()) { d_tiles = nullptr; n_launch = ntl; }
+        else { held.assign((size_t)nslots, 0); for (int t : left) held[(size_t)t] = 1; }
+      }
+      return 0;
+    };
+    // ---- the host's turn behind a check at iteration `iter`, from the flags in h_iscal: who goes on (*go_on: anybody), and
+    // row E13 on the device for the QPs whose rho changed - serially, or as a region pipelined with the next segment
+    auto host_turn = [&](bool *go_on) -> int {
+      *go_on = false;
       // QPs still iterating / asking for a refactorisation.  A QP that runs into max_iter at a rho-update iteration
       // has finished AND asks for its refactorisation: upstream adapts rho (and refactors) before it leaves the loop,
       // and the next Solve() of a warm-started solver continues from that factor.
       std::vector<int> active, work;
       for (int s = 0; s < h->B; s++) {
+        if (!held.empty() && held[(size_t)s]) continue;
         const int *t = h->h_iscal + (size_t)(s / BT) * IS_COUNT * BT;
         if (!t[IS_DONE * BT + s % BT]) active.push_back(s);
         if (t[IS_NEED_REFACTOR * BT + s % BT]) work.push_back(s);
       }
+      // run-ahead counter: who outside the group is still active after the segment that follows the region
+      if (ra.used && !leftovers_phase && ra.points.size() && iter == segment_end(ra.points[0])) h->ra_missed += (int64_t)active.size();
       const int n_ref = (int)work.size();
-      if (active.empty() && !n_ref) break;
+      if (active.empty() && !n_ref) return 0;
       // ---- row E13 on the device: rho vector, KKT assembly, block LDL', scatter into the schedules
       if (n_ref) {
         double tr = now_s();
@@ -1719,7 +1871,35 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
           // a long list: its chunks overlap with the next segment's iterations, chunk after chunk
           KernelArgs nx = a;
           nx.iter_begin = iter; nx.iter_end = segment_end(iter); nx.info_at_end = 1;
-          if ((rc2 = pipelined_refactor_iterate(h, nx, work, active, &region))) return rc2;
+          // run-ahead: the group among the active tiles, from the residuals this point's check stored; it goes ahead when the
+          // rest of the work list is still a pipelined one
+          std::vector<int> work_m, active_m;
+          if (a.res && !ra.used && res_iter == iter) {
+            std::vector<double> pri(active.size()), dua(active.size());
+            for (size_t i = 0; i < active.size(); i++) { pri[i] = h->h_res[2 * (size_t)active[i]]; dua[i] = h->h_res[2 * (size_t)active[i] + 1]; }
+            const int size = h->tune.runahead_tiles > 0 ? h->tune.runahead_tiles : std::max(1, h->n_cus * kRunaheadQuarters / 4);
+            std::vector<int> group = runahead_group(active, pri, dua, size, ra_min);
+            if (!group.empty() && group.size() < active.size()) {
+              std::vector<char> in((size_t)nslots, 0);
+              for (int t : group) in[(size_t)t] = 1;
+              for (int s : work) (in[(size_t)s] ? ra.work : work_m).push_back(s);
+              for (int s : active) if (!in[(size_t)s]) active_m.push_back(s);
+              if (pipeline_applies(h, (int)work_m.size())) {
+                for (int t = 0; t < ntl; t++) if (!in[(size_t)t]) ra.rest.push_back(t);
+                for (int t : group) ra.ru0.push_back(h->h_iscal[(size_t)t * IS_COUNT + IS_RHO_UPDATES]);
+                const int interval = (int)S.adaptive_rho_interval;
+                const int end = (int)std::min<int64_t>(S.max_iter, (int64_t)(iter / interval + 2) * interval);
+                for (int it = iter; it < end && (h->tune.runahead_end <= 0 || (int)ra.points.size() < h->tune.runahead_end);) ra.points.push_back(it = segment_end(it));
+                ra.group = std::move(group); ra.chk_threads = check_threads();
+                ra.used = ra.open = true;
+              } else ra.work.clear();
+            }
+          }
+          if (ra.open) {
+            if ((rc2 = pipelined_refactor_iterate(h, nx, work_m, active_m, &region, &ra))) return rc2;
+            d_tiles = h->ra_list.p; n_launch = (int)ra.rest.size();       // the region's check and what follows leave the group alone
+            h->ra_regions++; h->ra_tiles += (int64_t)ra.group.size();
+          } else if ((rc2 = pipelined_refactor_iterate(h, nx, work, active, &region))) return rc2;
           iterated = true;
           tr = now_s();         // (the region does its own accounting, and fails the QPs that lost their inertia on the device)
         } else if ((rc2 = device_refactor_slots(h, std::move(work), &bad))) return rc2;
@@ -1735,13 +1915,36 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
           active.erase(std::remove_if(active.begin(), active.end(), [&](int q) { return isbad[q] != 0; }), active.end());
         }
       }
-      if (active.empty()) break;
+      if (active.empty()) return 0;
       iterating = 0;
       for (size_t i = 0; i < active.size(); i++) iterating += !i || active[i] / BT != active[i - 1] / BT;
+      *go_on = true;
+      return 0;
+    };
+    while (true) {
+      const int seg_end = segment_end(iter);
+      if ((rc = device_turn(seg_end))) return rc;
+      iter = seg_end;
+      bool go_on = false;
+      if ((rc = host_turn(&go_on))) return rc;
+      if (go_on) continue;
+      // nobody is active any more: on with the members the chain left, alone, from the iteration their chain ended at - the
+      // flags the host holds are theirs still (nothing has touched them since the chain), so the host's turn comes first
+      if (leftovers_phase || left.empty()) break;
+      leftovers_phase = true;
+      held.assign((size_t)nslots, 1);
+      for (int t : left) held[(size_t)t] = 0;
+      HIPCHK(hipMemcpyAsync(h->ra_list.p, left.data(), left.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      d_tiles = h->ra_list.p; n_launch = (int)left.size();
+      a.tiles = d_tiles;
+      iter = ra.points.back();
+      if ((rc = host_turn(&go_on))) return rc;
+      if (!go_on) break;
     }
     return MI_OSQP_OK;
   };
   rc = loop();
+  a.tiles = nullptr; a.res = nullptr;
   if (rc) {
     if (h->pipe_r) (void)hipStreamSynchronize(h->pipe_r);
     if (h->pipe_i) (void)hipStreamSynchronize(h->pipe_i);
@@ -2030,6 +2233,8 @@ int mi_osqp_batch_get_stats(mi_osqp_batch *h, mi_osqp_stats *st) {
   st->refactor_lanes = h->refactor_lanes;
   st->iterate_launches_deep_ring = h->rf_launches[RF_FORM_DEEP_RING];
   st->iterate_launches_long_head = h->rf_launches[RF_FORM_LONG_HEAD];
+  st->runahead_regions = h->ra_regions; st->runahead_tiles = h->ra_tiles;
+  st->runahead_left = h->ra_left; st->runahead_missed = h->ra_missed;
   return MI_OSQP_OK;
 }
 
@@ -3867,6 +4072,26 @@ int mi_osqp_debug_refactor_lanes(int64_t n_flagged, const int64_t *flagged, int6
   *n_waits = (int64_t)rl.wait_chunk.size();
   std::copy(rl.wait_chunk.begin(), rl.wait_chunk.end(), wait_chunk);
   std::copy(rl.wait_for.begin(), rl.wait_for.end(), wait_for);
+  return MI_OSQP_OK;
+}
+int mi_osqp_debug_runahead_group(int64_t n_active, const int64_t *tiles, const double *pri_res, const double *dua_res, int64_t size,
+                                 int64_t min_active, int64_t *n_group, int64_t *group) {
+  if (!n_group || !group || (n_active > 0 && (!tiles || !pri_res || !dua_res))) return MI_OSQP_ERR_NULL;
+  if (n_active < 0 || n_active > INT32_MAX || size < 0 || size > INT32_MAX || min_active < 0 || min_active > INT32_MAX) return MI_OSQP_ERR_INVALID_DATA;
+  std::vector<int> t((size_t)n_active);
+  for (int64_t i = 0; i < n_active; i++) {
+    if (tiles[i] < 0 || tiles[i] > INT32_MAX || pri_res[i] < 0.0 || dua_res[i] < 0.0) return MI_OSQP_ERR_INVALID_DATA;
+    t[(size_t)i] = (int)tiles[i];
+  }
+  {
+    std::vector<int> sorted = t;
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return MI_OSQP_ERR_INVALID_DATA;
+  }
+  const std::vector<int> g = runahead_group(t, std::vector<double>(pri_res, pri_res + n_active), std::vector<double>(dua_res, dua_res + n_active),
+                                            (int)size, (int)min_active);
+  *n_group = (int64_t)g.size();
+  std::copy(g.begin(), g.end(), group);
   return MI_OSQP_OK;
 }
 int mi_osqp_debug_iterate_form(int64_t tiles, int64_t has_head, int64_t forced_form, int64_t long_min, int64_t *form) {

@@ -2,7 +2,8 @@
 
 usage: python scripts/region_timeline.py TRACE_DIR [LABEL]
 TRACE_DIR: what `rocprofv3 --kernel-trace --output-format csv -d TRACE_DIR -- python bench.py --steps 3 --warmup 1` wrote.
-Prints every kernel between the last two check_kernel launches that have a long refactorisation between them (more than 500
+Prints every kernel between the last two check_kernel launches of the solve loop (more than half the largest check grid: the
+checks of a run-ahead group's chain lie inside the region) that have a long refactorisation between them (more than 500
 factor_kernel workgroups: the check at iteration 100 and the one at 125 of the headline batch) with its stream or queue,
 workgroups, start, end and duration in us from the end of the first check, then the per-kernel totals of the whole run."""
 import csv
@@ -30,7 +31,10 @@ def main():
             stream = r.get("Stream_Id") or r.get("Queue_Id") or "?"
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"]), stream, grid // wg))
     rows.sort()
-    checks = [i for i, r in enumerate(rows) if r[2] == "check_kernel"]
+    # the checks of the solve loop: the full grid, or everyone but a run-ahead group (whose own checks, over the group's tiles
+    # only, sit inside the region)
+    full = max((r[4] for r in rows if r[2] == "check_kernel"), default=0)
+    checks = [i for i, r in enumerate(rows) if r[2] == "check_kernel" and 2 * r[4] > full]
     region = None
     for a, b in zip(checks, checks[1:]):
         if sum(r[4] for r in rows[a + 1:b] if r[2] == "factor_kernel") > 500:
