@@ -116,6 +116,7 @@ typedef struct {
   int64_t refactor_lanes;   /* the most chunk lanes a pipelined rho-update point has run on since setup: streams that each run factor -> tail -> iterate of their chunks (1 = one refactorisation stream and one iterate stream; 0 = none pipelined yet) */
   int64_t iterate_launches_deep_ring, iterate_launches_long_head;   /* iterate launches since setup by the form of the resident head they ran (MI_OSQP_RF_FORM, MI_OSQP_RF_LONG_MIN): 16 steps resident and a product ring of 16, or resident_factor_steps (32) and a ring of 8; both 0 on a handle without a head */
   int64_t runahead_regions, runahead_tiles, runahead_left, runahead_missed;   /* run-ahead since setup (switches, read at setup: MI_OSQP_RUNAHEAD = 0 / 1 off / on, MI_OSQP_RUNAHEAD_TILES = tiles of a group, default half the CUs, MI_OSQP_RUNAHEAD_MIN = active tiles below which no group is sent, default the CU count, MI_OSQP_RUNAHEAD_END = most segments of a chain, default up to the rho-update point after next): pipelined rho-update points that sent the active tiles furthest from convergence ahead as a chain of launches beside the region, without a host turn; tiles sent; members still active when their chain ended (they went on alone afterwards); QPs outside the groups still active after the segment that follows the region (late QPs the group did not hold) */
+  int64_t region_priority, region_lane_checks, region_chunks;   /* the last pipelined rho-update point (0 before the first; switches read at setup): the stream priorities it ran with, MI_OSQP_REGION_PRIORITY - 0 every stream alike, 1 the chunk lanes at the least priority of the device, 2 the run-ahead chain on a stream of its own at the greatest, -1 asked for 1 or 2 where that priority is the one every stream has, so nothing changed; 1 when every lane failed and checked its own chunks and only the flag copy followed the join (MI_OSQP_LANE_CHECKS, one-QP tiles); its refactorisation chunks (default size: mi_osqp_debug_region_chunks) */
 } mi_osqp_stats;
 
 typedef struct mi_osqp_solver mi_osqp_solver; /* one QP  */
@@ -633,6 +634,13 @@ int mi_osqp_debug_host_block_factor(int64_t n, int64_t m,
 int mi_osqp_debug_refactor_chunks(int64_t n_flagged, const int64_t *flagged, int64_t n_active, const int64_t *active, int64_t tile,
                                   int64_t chunk_qps, int64_t max_chunks, int64_t *n_chunks, int64_t *work_begin, int64_t *tiles,
                                   int64_t *tile_begin);
+
+/* Host only: the default chunk size of a pipelined region (neither MI_OSQP_REFACTOR_CHUNKS nor MI_OSQP_REFACTOR_CHUNK_QPS set;
+ * host_core.hpp region_chunk_qps).  nq = flagged slots of the region's work list, gw = flagged slots of the run-ahead chain
+ * that refactors beside it (0 without run-ahead), n_cus = CUs.  Out: *chunk_qps = ceil(nq / n_even) with rounds =
+ * ceil((nq + gw) / n_cus) and n_even = rounds (gw = 0) or 2 rounds - 1 (gw > 0) even chunks, at most 8 and at most nq of
+ * them, and *n_chunks = the refactorisation chunks that gives, ceil(nq / chunk_qps) (0 for nq = 0). */
+int mi_osqp_debug_region_chunks(int64_t nq, int64_t gw, int64_t n_cus, int64_t *chunk_qps, int64_t *n_chunks);
 
 /* Host only: the chunk lanes of those chunks (MI_OSQP_REFACTOR_LANES; solver.hip "pipelined refactorisation").  kbt = slots
  * per workgroup of the refactorisation kernels, lanes = 1 .. 3, chunk0_first = chunk 0 in front of the last lane instead of

@@ -64,7 +64,8 @@ class Stats(C.Structure):
                 ("refactor_lanes", C.c_int64),
                 ("iterate_launches_deep_ring", C.c_int64), ("iterate_launches_long_head", C.c_int64),
                 ("runahead_regions", C.c_int64), ("runahead_tiles", C.c_int64), ("runahead_left", C.c_int64),
-                ("runahead_missed", C.c_int64)]
+                ("runahead_missed", C.c_int64),
+                ("region_priority", C.c_int64), ("region_lane_checks", C.c_int64), ("region_chunks", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -205,6 +206,7 @@ def lib():
         L.mi_osqp_debug_refactor_chunks.argtypes = [C.c_int64, ip, C.c_int64, ip, C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip]
         L.mi_osqp_debug_refactor_lanes.argtypes = [C.c_int64, ip, C.c_int64, ip] + [C.c_int64] * 7 + [ip] * 8
         L.mi_osqp_debug_runahead_group.argtypes = [C.c_int64, ip, dp, dp, C.c_int64, C.c_int64, ip, ip]
+        L.mi_osqp_debug_region_chunks.argtypes = [C.c_int64] * 3 + [ip] * 2
         L.mi_osqp_debug_iterate_form.argtypes = [C.c_int64] * 4 + [ip]
         L.mi_osqp_prefetch_analysis.argtypes = [C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip, C.c_int64]
         L.mi_osqp_debug_host_block_factor.argtypes = [C.c_int64, C.c_int64, ip, ip, dp, ip, ip, dp, dp, dp,
@@ -936,6 +938,14 @@ def debug_refactor_lanes(flagged, active, tile, chunk_qps, lanes, kbt=None, chun
     return dict(n_lanes=L, lane_of=lane_of[:k].tolist(), order=[order[ob[l]:ob[l + 1]].tolist() for l in range(L)],
                 scratch=[(int(sb[c]), (len(work[c]) + kbt - 1) // kbt * kbt) for c in range(k)],
                 waits=list(zip(wc[:nw.value].tolist(), wf[:nw.value].tolist())))
+
+
+def debug_region_chunks(nq, gw, n_cus):
+    """Host-only: the default chunks of a pipelined region of nq flagged QPs beside a run-ahead chain of gw flagged QPs (0:
+    no chain) on n_cus CUs.  Returns (QPs per chunk, refactorisation chunks)."""
+    q, k = C.c_int64(), C.c_int64()
+    _chk(lib().mi_osqp_debug_region_chunks(nq, gw, n_cus, C.byref(q), C.byref(k)), "debug_region_chunks")
+    return int(q.value), int(k.value)
 
 
 def debug_runahead_group(tiles, pri_res, dua_res, size, min_active):

@@ -1042,6 +1042,8 @@ Tuning tuning_from_env() {
   if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNK_QPS")) t.pipeline_chunk_qps = std::max(0, atoi(e));
   if (const char *e = getenv("MI_OSQP_REFACTOR_LANES")) t.refactor_lanes = std::max(1, std::min(3, atoi(e)));
   if (const char *e = getenv("MI_OSQP_REFACTOR_CHUNK0")) t.lanes_chunk0 = atoi(e) != 0;
+  if (const char *e = getenv("MI_OSQP_REGION_PRIORITY")) t.region_priority = std::max(0, std::min(2, atoi(e)));
+  if (const char *e = getenv("MI_OSQP_LANE_CHECKS")) t.lane_checks = atoi(e) != 0;
   if (const char *e = getenv("MI_OSQP_RUNAHEAD")) t.runahead = atoi(e) != 0;
   if (const char *e = getenv("MI_OSQP_RUNAHEAD_TILES")) t.runahead_tiles = std::max(0, atoi(e));
   if (const char *e = getenv("MI_OSQP_RUNAHEAD_MIN")) t.runahead_min = std::max(0, atoi(e));
@@ -1083,6 +1085,16 @@ RefactorChunks refactor_chunks(const std::vector<int> &flagged, const std::vecto
   for (const auto &p : tc) { rc.tiles.push_back(p.second); rc.tile_begin[(size_t)p.first + 1]++; }
   for (int c = 0; c < rc.n_chunks; c++) rc.tile_begin[(size_t)c + 1] += rc.tile_begin[c];
   return rc;
+}
+
+int region_chunk_qps(int nq, int gw, int n_cus, int max_chunks) {
+  nq = std::max(0, nq); gw = std::max(0, gw); n_cus = std::max(1, n_cus);
+  const int64_t rounds = ((int64_t)nq + gw + n_cus - 1) / n_cus;
+  // beside a chain: twice the rounds less one (its group holds half the CUs, and an odd count leaves the lane that also
+  // iterates chunk 0 one chunk fewer than the other)
+  const int64_t want = gw > 0 ? 2 * rounds - 1 : rounds;
+  const int n_even = (int)std::max<int64_t>(1, std::min<int64_t>(want, std::min(std::max(1, max_chunks), std::max(1, nq))));
+  return (int)std::max<int64_t>(1, ((int64_t)nq + n_even - 1) / n_even);
 }
 
 RefactorLanes refactor_lanes(const RefactorChunks &ch, const std::vector<int> &flagged, int bt, int kbt, int lanes, bool chunk0_first, int scratch_slots) {

@@ -46,6 +46,8 @@ struct AnalysisTuning {            // what analyze() reads
   }
 };
 constexpr bool kRunaheadDefault = true;      // (measured: DESIGN.md section 4, "Measurements (run-ahead)")
+constexpr int kRegionPriorityDefault = 0;
+constexpr bool kLaneChecksDefault = false;
 struct Tuning {
   int tile = 0;                    // MI_OSQP_TILE: 1, 2 or 4 QPs per tile
   int threads = 0;                 // MI_OSQP_THREADS: threads per tile of the solve kernels (64 .. 1024)
@@ -68,6 +70,9 @@ struct Tuning {
                                    // both 0 (the measured default): the fewest even chunks of at most one QP per CU - 3 x 202 for 605 QPs
   int refactor_lanes = 0;          // MI_OSQP_REFACTOR_LANES: 1 .. 3 chunk lanes (refactor_lanes below); 1 = the two-stream form; 0 = the default
   int lanes_chunk0 = -1;           // MI_OSQP_REFACTOR_CHUNK0: 1 chunk 0 in front of the last lane, 0 behind the shortest lane; -1 = the default
+  // the region beside a run-ahead chain (solver.hip "pipelined refactorisation"; measured: DESIGN.md section 4, "Measurements (region balance)")
+  int region_priority = kRegionPriorityDefault;      // MI_OSQP_REGION_PRIORITY: 0 every stream alike, 1 the lanes at the least stream priority, 2 the chain on a stream of the greatest
+  bool lane_checks = kLaneChecksDefault;             // MI_OSQP_LANE_CHECKS=0 / 1: every lane fails and checks its own chunks (one-QP tiles), nothing but the flag copy behind the join
   // the QPs furthest from convergence at a pipelined rho-update point run ahead beside the region (runahead_group below)
   bool runahead = kRunaheadDefault;  // MI_OSQP_RUNAHEAD=0 / 1: off / on
   int runahead_tiles = 0;          // MI_OSQP_RUNAHEAD_TILES: tiles of the group (0 = the default, half the CUs)
@@ -104,6 +109,16 @@ struct RefactorChunks {
   std::vector<int> tile_begin;     // n_chunks + 1: chunk c iterates tiles[tile_begin[c] .. tile_begin[c + 1])
 };
 RefactorChunks refactor_chunks(const std::vector<int> &flagged, const std::vector<int> &active, int bt, int chunk_qps, int max_chunks);
+
+// The default chunk size of a pipelined region (neither MI_OSQP_REFACTOR_CHUNKS nor _CHUNK_QPS set): nq flagged slots in the
+// region's work list, gw flagged slots of the run-ahead chain that refactors beside it (0 without run-ahead), n_cus CUs.
+// The refactorisation kernels run one workgroup per QP, and the chain's gw workgroups take CUs in the same first round as the
+// region's first chunks, so the rounds are counted over both: rounds = ceil((nq + gw) / n_cus).  gw = 0: n_even = rounds, the
+// fewest even chunks of at most one QP per CU.  gw > 0: n_even = 2 rounds - 1 - the chain's group (by default half the CUs)
+// keeps its CUs for the whole region, so a lane's round is half as long, and with an odd count the lane that also iterates
+// chunk 0 refactors one chunk fewer than the other (even counts measured 0.7 - 0.9 ms slower, DESIGN.md section 4,
+// "Measurements (region balance)").  At most max_chunks and at most nq chunks; returns ceil(nq / n_even), never less than 1.
+int region_chunk_qps(int nq, int gw, int n_cus, int max_chunks);
 
 // Chunk lanes of a pipelined refactorisation: a lane is a stream that runs the chain factor -> tail -> iterate of its chunks one
 // after the other.  Chunk c >= 1 goes to lane (c - 1) % n_lanes; chunk 0 (tiles without a flagged slot: an iterate only) goes

@@ -192,12 +192,15 @@ static hipError_t alloc(void **p, size_t bytes, size_t *cap) {
 namespace streampool {
 constexpr int kPipeChunks = 8;                      // refactorisation chunks of a pipelined region, at most
 constexpr int kPipeLanes = 3;                       // chunk lanes, at most: with the solve stream four streams, the hardware queues a process gets by default
-constexpr int kPipeEvents = 3 + 3 * kPipeChunks + kPipeLanes;    // fork, begin / end of the iterates, (begin, factor done, tail done) per chunk, end of every lane
-struct Bundle { int dev; hipStream_t stream; hipEvent_t ev[5]; hipStream_t pipe_r, pipe_i, pipe_x; hipEvent_t pipe_ev[kPipeEvents]; };
+constexpr int kPipeEvents = 3 + 3 * kPipeChunks + kPipeLanes + 1;    // fork, begin / end of the iterates, (begin, factor done, tail done) per chunk, end of every lane, end of the chain's stream
+// lane_prio: the stream priority pipe_r / pipe_i / pipe_x were created with (a stream keeps it for life; MI_OSQP_REGION_PRIORITY
+// = 1 asks for the least one) - a handle that wants another destroys them and creates its own (setup).  pipe_c, the
+// stream of the run-ahead chain under MI_OSQP_REGION_PRIORITY = 2, is only ever created at the greatest priority.
+struct Bundle { int dev; hipStream_t stream; hipEvent_t ev[5]; hipStream_t pipe_r, pipe_i, pipe_x; hipEvent_t pipe_ev[kPipeEvents]; int lane_prio; hipStream_t pipe_c; };
 static void destroy(const Bundle &b) {
   for (hipEvent_t e : b.ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : b.pipe_ev) if (e) (void)hipEventDestroy(e);
-  for (hipStream_t st : {b.stream, b.pipe_r, b.pipe_i, b.pipe_x}) if (st) (void)hipStreamDestroy(st);
+  for (hipStream_t st : {b.stream, b.pipe_r, b.pipe_i, b.pipe_x, b.pipe_c}) if (st) (void)hipStreamDestroy(st);
 }
 static std::mutex mu;
 static std::vector<Bundle> idle;
@@ -331,6 +334,12 @@ struct mi_osqp_batch {
   // with chunk lanes the three are lanes 0, 1, 2 (pipe_x is only ever the third lane)
   hipStream_t pipe_r = nullptr, pipe_i = nullptr, pipe_x = nullptr;
   hipEvent_t pipe_ev[streampool::kPipeEvents] = {};
+  // MI_OSQP_REGION_PRIORITY (setup): the form in effect (0 where the device reports one stream priority only), the priority
+  // the lanes are created with, the chain's stream of form 2 (created with the first region that runs ahead)
+  int prio_form = 0, lane_prio = 0, chain_prio = 0;
+  bool prio_inert = false;
+  hipStream_t pipe_c = nullptr;
+  int64_t region_priority = 0, region_lane_checks = 0, region_chunks = 0;      // mi_osqp_stats region_*: the last region
   DevBuf<int> tile_list;                      // the active tiles chunk after chunk (KernelArgs::tiles)
   int64_t pipelined_refactors = 0;            // rho-update points of this handle that took the pipelined form
   int64_t refactor_lanes = 0;                 // the most chunk lanes one of them ran on (1 = the two-stream form)
@@ -424,7 +433,8 @@ struct mi_osqp_batch {
     if (pipe_r) (void)hipStreamSynchronize(pipe_r);
     if (pipe_i) (void)hipStreamSynchronize(pipe_i);
     if (pipe_x) (void)hipStreamSynchronize(pipe_x);
-    streampool::Bundle sb{device, stream, {ev0, ev1, evf0, evf1, evf2}, pipe_r, pipe_i, pipe_x, {}};
+    if (pipe_c) (void)hipStreamSynchronize(pipe_c);
+    streampool::Bundle sb{device, stream, {ev0, ev1, evf0, evf1, evf2}, pipe_r, pipe_i, pipe_x, {}, lane_prio, pipe_c};
     for (int k = 0; k < streampool::kPipeEvents; k++) sb.pipe_ev[k] = pipe_ev[k];
     if (stream && ev0 && ev1 && evf0 && evf1 && evf2) streampool::give(sb);
     else streampool::destroy(sb);
@@ -938,9 +948,10 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { g_last_error = std::string("device is not gfx950: ") + prop.gcnArchName; return MI_OSQP_ERR_DEVICE; }
   {
     streampool::Bundle sb;
-    if (streampool::take(h->device, sb)) {
+    const bool pooled = streampool::take(h->device, sb);
+    if (pooled) {
       h->stream = sb.stream; h->ev0 = sb.ev[0]; h->ev1 = sb.ev[1]; h->evf0 = sb.ev[2]; h->evf1 = sb.ev[3]; h->evf2 = sb.ev[4];
-      h->pipe_r = sb.pipe_r; h->pipe_i = sb.pipe_i; h->pipe_x = sb.pipe_x;
+      h->pipe_r = sb.pipe_r; h->pipe_i = sb.pipe_i; h->pipe_x = sb.pipe_x; h->pipe_c = sb.pipe_c;
       for (int k = 0; k < streampool::kPipeEvents; k++) h->pipe_ev[k] = sb.pipe_ev[k];
     }
     else {
@@ -948,6 +959,18 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
       HIPCHK(hipEventCreate(&h->ev0)); HIPCHK(hipEventCreate(&h->ev1));
       HIPCHK(hipEventCreate(&h->evf0)); HIPCHK(hipEventCreate(&h->evf1)); HIPCHK(hipEventCreate(&h->evf2));
     }
+    // MI_OSQP_REGION_PRIORITY: numerically greater = less urgent; a stream created without a priority has 0.  A form whose
+    // priority is that of every other stream changes nothing and counts as not asked for (mi_osqp_stats region_priority -1).
+    int least = 0, greatest = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    const int asked = h->tune.region_priority;
+    h->prio_inert = (asked == 1 && least == 0) || (asked == 2 && greatest == 0);
+    h->prio_form = h->prio_inert ? 0 : asked;
+    h->lane_prio = h->prio_form == 1 ? least : 0;
+    h->chain_prio = greatest;
+    // pooled lanes of another priority (idle: their handle synchronised them before it gave them back) are not handed on
+    if (pooled && sb.lane_prio != h->lane_prio)
+      for (hipStream_t *st : {&h->pipe_r, &h->pipe_i, &h->pipe_x}) if (*st) { (void)hipStreamDestroy(*st); *st = nullptr; }
   }
   h->BT = BT; h->ntiles = (int)((B + BT - 1) / BT);
   h->lds = h->global_xs ? lds_bytes(0, BT, h->threads) : lds_bytes(an.Next + 2 * an.dt.k, BT, h->threads);
@@ -1472,6 +1495,8 @@ struct PipeRegion {
   bool open = false;
   int iter = 0, n_chunks = 0, n_lanes = 1;
   bool tail = false;
+  int chk_threads = 0;                // in: threads of the solve loop's check launches (the lanes' own checks take the same)
+  bool lane_checks = false;           // the lanes have failed and checked their own chunks: no check_kernel launch behind the join
   double host_s = 0.0;                // host time up to the fork
   std::vector<int> work, wl, tiles;   // the flagged slots; the lists the copies read
   std::vector<int> lane_last;         // per lane: its last refactorisation chunk (0: none)
@@ -1536,16 +1561,25 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
   const double t_begin = now_s();
   const int BT = h->BT, nq = (int)work.size();
   int rc;
-  if (!h->pipe_r) HIPCHK(hipStreamCreateWithFlags(&h->pipe_r, hipStreamNonBlocking));
-  if (!h->pipe_i) HIPCHK(hipStreamCreateWithFlags(&h->pipe_i, hipStreamNonBlocking));
+  // a lane of the handle's lane priority (MI_OSQP_REGION_PRIORITY = 1: the least one - wherever a CU frees up, the workgroups
+  // of the chain on the solve stream go first)
+  auto lane_stream = [&](hipStream_t *st) -> int {
+    if (*st) return 0;
+    if (h->lane_prio != 0) HIPCHK(hipStreamCreateWithPriority(st, hipStreamNonBlocking, h->lane_prio));
+    else HIPCHK(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+    return 0;
+  };
+  if ((rc = lane_stream(&h->pipe_r)) || (rc = lane_stream(&h->pipe_i))) return rc;
   for (int k = 0; k < kPipeEvents; k++) if (!h->pipe_ev[k]) HIPCHK(hipEventCreate(&h->pipe_ev[k]));
-  hipEvent_t ev_fork = h->pipe_ev[0], ev_i0 = h->pipe_ev[1], ev_join = h->pipe_ev[2];
+  hipEvent_t ev_fork = h->pipe_ev[0], ev_i0 = h->pipe_ev[1], ev_join = h->pipe_ev[2], ev_chain = h->pipe_ev[kPipeEvents - 1];
   auto ev_chunk = [&](int c, int k) { return h->pipe_ev[3 + 3 * (c - 1) + k]; };      // chunk c >= 1; k = 0 begin, 1 factor done, 2 tail done
   auto ev_lane = [&](int l) { return h->pipe_ev[3 + 3 * kPipeChunks + l]; };          // end of lane l (one lane: of stream I)
-  // default: the fewest even chunks that are one round of one-workgroup-per-QP kernels each (headline batch, 605 QPs on 256 CUs:
-  // 3 x 202 beat 2 x 303, 4 x 152, 6 x 101 and 256 + 256 + 93)
-  int n_even = h->tune.pipeline_chunks > 0 ? h->tune.pipeline_chunks : (nq + h->n_cus - 1) / h->n_cus;
-  int chunk_qps = (nq + n_even - 1) / n_even;
+  // default (host_core.hpp region_chunk_qps): the fewest even chunks that are one round of one-workgroup-per-QP kernels each,
+  // the chain's refactorisation counted with them (headline batch, 605 QPs on 256 CUs: 3 x 202 beat 2 x 303, 4 x 152, 6 x 101
+  // and 256 + 256 + 93; 496 QPs beside a chain of 107: DESIGN.md section 4)
+  const int cus = h->tune.assume_cus > 0 ? std::min(h->n_cus, h->tune.assume_cus) : h->n_cus;
+  int chunk_qps = region_chunk_qps(nq, ra ? (int)ra->work.size() : 0, cus, kPipeChunks);
+  if (h->tune.pipeline_chunks > 0) chunk_qps = (nq + h->tune.pipeline_chunks - 1) / h->tune.pipeline_chunks;
   if (h->tune.pipeline_chunks <= 0 && h->tune.pipeline_chunk_qps > 0) chunk_qps = h->tune.pipeline_chunk_qps;
   const RefactorChunks ch = refactor_chunks(work, active, BT, chunk_qps, kPipeChunks);
   // the work list chunk after chunk, each packed kbt slots per workgroup (as device_refactor_slots packs the whole list)
@@ -1554,8 +1588,14 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
   const RefactorLanes rl = refactor_lanes(ch, work, BT, kbt, std::min(lanes_asked, kPipeLanes), h->tune.lanes_chunk0 < 0 ? kDefaultChunk0First : h->tune.lanes_chunk0 != 0,
                                           h->ntiles * BT + 4);      // (what Lblk, Dl, dinv_scratch and dt_Sd hold: setup)
   const int L = rl.n_lanes;
-  if (L > 2 && !h->pipe_x) HIPCHK(hipStreamCreateWithFlags(&h->pipe_x, hipStreamNonBlocking));
+  if (L > 2 && (rc = lane_stream(&h->pipe_x))) return rc;
   if (ra && (L > 2 || BT != 1)) { g_last_error = "run-ahead beside three chunk lanes / tiles of several QPs"; return MI_OSQP_ERR_INVALID_SETTINGS; }
+  // MI_OSQP_REGION_PRIORITY = 2: the chain on a stream of its own at the greatest priority
+  const bool chain_high = ra && h->prio_form == 2;
+  if (chain_high && !h->pipe_c) HIPCHK(hipStreamCreateWithPriority(&h->pipe_c, hipStreamNonBlocking, h->chain_prio));
+  // MI_OSQP_LANE_CHECKS (one-QP tiles): behind the tail of a chunk fail_flagged_kernel over that chunk's list, behind its
+  // iterate check_kernel over its tiles - the order of the chain below - and only the flag copy behind the join
+  const bool lane_checks = h->tune.lane_checks && BT == 1;
   std::vector<int> &wl = pr->wl;
   std::vector<int> wl_begin(1, 0);
   wl.clear();
@@ -1596,6 +1636,8 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
       da.wg_base = base;
       HIPCHK(launch_tail(da, slots, h->dt_lds_asm, h->dt_lds, st));
     }
+    // (in front of the event: whoever waits for this chunk's factors iterates its tiles, and a failed slot is finished by then)
+    if (lane_checks) HIPCHK(launch_fail_flagged(a, wc, slots, BT, a.iter_begin, st));
     HIPCHK(hipEventRecord(ev_chunk(c, 2), st));
     return 0;
   };
@@ -1607,12 +1649,16 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
     ai.rf_form = iterate_form(nt, h->rf_off != 0, h->tune);
     h->rf_launches[ai.rf_form]++;
     HIPCHK(launch_iterate(ai, BT, nt, h->threads, h->lds_iter + h->lds_factor, st));
+    // the solve loop's check of this segment (device_turn: the same arguments, thread count included), over this chunk's tiles
+    if (lane_checks) HIPCHK(launch_check(ai, BT, nt, pr->chk_threads, h->lds, st));
     return 0;
   };
   // ---- the run-ahead chain on the solve stream, which has nothing else to do until the join: its first refactorisation and
   // segment are enqueued in front of the region's launches (the chain is the longer path), the rest behind them and in front
   // of the waits of the join
-  hipStream_t sx = h->stream;
+  // (MI_OSQP_REGION_PRIORITY = 2: on pipe_c, forked like a lane behind the list copies and joined with the lanes)
+  hipStream_t sx = chain_high ? h->pipe_c : h->stream;
+  if (chain_high) HIPCHK(hipStreamWaitEvent(sx, ev_fork, 0));
   KernelArgs ac = a;
   ac.tiles = d_group; ac.res = nullptr; ac.info_at_end = 1;
   FactorArgs fg = make_factor_args(h, 0);
@@ -1678,13 +1724,16 @@ static int pipelined_refactor_iterate(mi_osqp_batch *h, const KernelArgs &a, con
     for (int l = 0; l < L; l++) HIPCHK(hipEventRecord(ev_lane(l), lane[l]));
   }
   if (ra) for (size_t k = 1; k < ra->points.size(); k++) if ((rc = chain_segment(k))) return rc;      // the rest of the chain
+  if (chain_high) { HIPCHK(hipEventRecord(ev_chain, sx)); HIPCHK(hipStreamWaitEvent(h->stream, ev_chain, 0)); }
   for (int l = 0; l < L; l++) HIPCHK(hipStreamWaitEvent(h->stream, ev_lane(l), 0));
   HIPCHK(hipEventRecord(ev_join, h->stream));
   // a rho update that makes the factor lose its inertia ends THAT QP as kNonConvex ([EXT] osqp_solve: adapt_rho fails ->
   // OSQP_NON_CVX, break); every other QP of the batch goes on
-  HIPCHK(launch_fail_flagged(a, h->work.p, (int)wl.size(), BT, a.iter_begin, h->stream));
-  pr->open = true; pr->iter = a.iter_begin; pr->n_chunks = ch.n_chunks; pr->n_lanes = L; pr->tail = tail;
+  if (!lane_checks) HIPCHK(launch_fail_flagged(a, h->work.p, (int)wl.size(), BT, a.iter_begin, h->stream));
+  pr->open = true; pr->iter = a.iter_begin; pr->n_chunks = ch.n_chunks; pr->n_lanes = L; pr->tail = tail; pr->lane_checks = lane_checks;
   h->refactor_lanes = std::max<int64_t>(h->refactor_lanes, L);
+  h->region_priority = h->prio_inert ? -1 : h->prio_form;
+  h->region_lane_checks = lane_checks; h->region_chunks = ch.n_chunks - 1;
   return 0;
 }
 
@@ -1713,6 +1762,8 @@ static int pipelined_region_finish(mi_osqp_batch *h, PipeRegion *pr) {
   // the first chunk's tail on at the latest, chunk 0 from the fork on - of the whole region
   if (pr->n_lanes == 1) HIPCHK(hipEventElapsedTime(&i_ms, ev_i0, h->pipe_ev[3 + 3 * kPipeChunks])); else i_ms = w_ms;
   // refactor_s: up to the last tail event; device_s: what remained exposed of the iterate, up to the join - together the wall time
+  // (lane checks: the tail event of a chunk lies behind its fail_flagged_kernel, and the lanes' checks lie in front of the join -
+  // the segment's check, which the other form launches behind the join and nobody accounts for, is part of device_s)
   const double wall = pr->host_s + 1e-3 * std::max(w_ms, r_ms), ref_s = pr->host_s + 1e-3 * r_ms;
   h->last_refactor_s += ref_s; h->last_device_s += wall - ref_s;
   h->kernel_ms_sum += i_ms; h->kernel_launches++; h->last_launches++;
@@ -1795,7 +1846,8 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
           HIPCHK(launch_iterate(a, BT, n_launch, h->mw_groups > 0 ? h->mw_threads : h->threads, h->lds_iter + h->lds_factor, h->stream));
           HIPCHK(hipEventRecord(h->ev1, h->stream));
         }
-        HIPCHK(launch_check(a, BT, n_launch, check_threads(), h->lds, h->stream));
+        // (a region whose lanes checked their own chunks has run this check already, tile list by tile list)
+        if (!(iterated && region.open && region.lane_checks)) HIPCHK(launch_check(a, BT, n_launch, check_threads(), h->lds, h->stream));
         HIPCHK(hipMemcpyAsync(h->h_iscal, h->iscal.p, (size_t)ntl * IS_COUNT * BT * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         // run-ahead: the residuals of the running QPs behind the check of a rho-update point (a group may be chosen from them);
         // behind a chain the marks of the slots it failed
@@ -1874,6 +1926,7 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
           // run-ahead: the group among the active tiles, from the residuals this point's check stored; it goes ahead when the
           // rest of the work list is still a pipelined one
           std::vector<int> work_m, active_m;
+          region.chk_threads = check_threads();
           if (a.res && !ra.used && res_iter == iter) {
             std::vector<double> pri(active.size()), dua(active.size());
             for (size_t i = 0; i < active.size(); i++) { pri[i] = h->h_res[2 * (size_t)active[i]]; dua[i] = h->h_res[2 * (size_t)active[i] + 1]; }
@@ -1949,6 +2002,7 @@ static int solve_impl(mi_osqp_batch *h, double *d_x_out, hipStream_t user_stream
     if (h->pipe_r) (void)hipStreamSynchronize(h->pipe_r);
     if (h->pipe_i) (void)hipStreamSynchronize(h->pipe_i);
     if (h->pipe_x) (void)hipStreamSynchronize(h->pipe_x);
+    if (h->pipe_c) (void)hipStreamSynchronize(h->pipe_c);
     (void)hipStreamSynchronize(h->stream);
     return rc;
   }
@@ -2235,6 +2289,7 @@ int mi_osqp_batch_get_stats(mi_osqp_batch *h, mi_osqp_stats *st) {
   st->iterate_launches_long_head = h->rf_launches[RF_FORM_LONG_HEAD];
   st->runahead_regions = h->ra_regions; st->runahead_tiles = h->ra_tiles;
   st->runahead_left = h->ra_left; st->runahead_missed = h->ra_missed;
+  st->region_priority = h->region_priority; st->region_lane_checks = h->region_lane_checks; st->region_chunks = h->region_chunks;
   return MI_OSQP_OK;
 }
 
@@ -4048,6 +4103,13 @@ int mi_osqp_debug_refactor_chunks(int64_t n_flagged, const int64_t *flagged, int
   std::copy(ch.work_begin.begin(), ch.work_begin.end(), work_begin);
   std::copy(ch.tiles.begin(), ch.tiles.end(), tiles);
   std::copy(ch.tile_begin.begin(), ch.tile_begin.end(), tile_begin);
+  return MI_OSQP_OK;
+}
+int mi_osqp_debug_region_chunks(int64_t nq, int64_t gw, int64_t n_cus, int64_t *chunk_qps, int64_t *n_chunks) {
+  if (!chunk_qps || !n_chunks) return MI_OSQP_ERR_NULL;
+  if (nq < 0 || nq > INT32_MAX || gw < 0 || gw > INT32_MAX || n_cus < 1 || n_cus > INT32_MAX) return MI_OSQP_ERR_INVALID_DATA;
+  const int q = region_chunk_qps((int)nq, (int)gw, (int)n_cus, streampool::kPipeChunks);
+  *chunk_qps = q; *n_chunks = (nq + q - 1) / q;
   return MI_OSQP_OK;
 }
 int mi_osqp_debug_refactor_lanes(int64_t n_flagged, const int64_t *flagged, int64_t n_active, const int64_t *active, int64_t tile,
