@@ -521,6 +521,34 @@ int mi_gomp_scene_create_world(mi_gomp_scene **out, mi_osqp_batch *h, int64_t di
                                const mi_gomp_chain *chain, int64_t n_balls, const mi_gomp_ball *balls,
                                int64_t n_lines, const mi_gomp_line *lines, int64_t n_capsules, const mi_gomp_capsule *capsules,
                                const double *con_lo, const double *con_hi);
+/* A cuboid obstacle: an oriented box with centre `centre`, orthonormal axes u_0, u_1, u_2 (the rows of `axes`, u_k =
+ * axes[3 k .. 3 k + 2] in world coordinates; a left-handed frame describes the same set and is accepted) and half extents
+ * half[k] >= 0 along them (0: a plate, a bar, a point), swept by a sphere of radius `radius` (0: the sharp box); host twin:
+ * CuboidObstacle in include/mi_osqp/gomp.hpp.  (Not the "three box rows of a gripper ball": those are the work-space limits
+ * con_lo / con_hi.)  For a ball with centre p = fk(q_w), radius r and position Jacobian J, in this order of operations:
+ *   d_k = p_k - centre_k;  y_k = u_k0 d_0 + u_k1 d_1 + u_k2 d_2  (p in the cuboid's frame);
+ *   c_k = min(half_k, max(-half_k, y_k))  (the closest point of the box);  v_k = y_k - c_k;  out = sqrt(v_0^2 + v_1^2 + v_2^2);
+ *   out > 1e-12 (outside: face, edge or corner region):  sd = out,  nl_k = v_k / out;
+ *   otherwise (inside or on the surface: leave through the nearest face):  slack_k = half_k - |c_k|,  k* = the smallest k
+ *     with slack_k = min(slack),  sd = -slack_k*,  nl = e_k* times (c_k* < 0 ? -1 : +1)  (so -0.0 and 0 give +1);
+ *   n_i = nl_0 u_0i + nl_1 u_1i + nl_2 u_2i  (back to the world);  reach = radius + r;  clearance s = sd - reach.
+ * The row of (ball, waypoint, cuboid) holds g_j = n_x J[x][j] + n_y J[y][j] + n_z J[z][j] in the columns of q_w, whether it
+ * is active or not.  It is active when s < margin: l = (reach - sd) + sum_j g_j q_w[j], u = +1e30; otherwise l = -1e30,
+ * u = +1e30.  A trajectory is accepted only if s >= -1e-3 for every ball, waypoint and cuboid.  `margin` has the capsule's
+ * meaning; as there, no neighbouring waypoint is looked at. */
+typedef struct { double centre[3]; double axes[9]; double half[3]; double radius; double margin; } mi_gomp_cuboid;   /* 136 bytes */
+/* mi_gomp_scene_create_world with cuboids besides the lines and capsules.  Inside the block of a (ball, waypoint) pair the
+ * rows are: the three work-space rows of a gripper ball, the lines, the capsules, then the cuboids in the order given, so the
+ * constraint matrix must hold waypoints * sum over the balls of ((gripper ? 3 : 0) + n_lines + n_capsules + n_cuboids) rows
+ * from the first 3-D row on.  n_cuboids == 0: exactly mi_gomp_scene_create_world.  Refused on the host, before any device
+ * call, with *out = NULL, the handle usable and the reason in mi_osqp_last_error() naming the cuboid's index: n_cuboids > 0
+ * without cuboids (MI_OSQP_ERR_NULL); n_cuboids < 0, a cuboid field that is not finite, a negative half extent, radius or
+ * margin, axes with |u_i . u_j - delta_ij| > 1e-9 for some i, j, a constraint matrix that does not hold the rows
+ * (MI_OSQP_ERR_INVALID_DATA). */
+int mi_gomp_scene_create_cuboids(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints,
+                                 const mi_gomp_chain *chain, int64_t n_balls, const mi_gomp_ball *balls,
+                                 int64_t n_lines, const mi_gomp_line *lines, int64_t n_capsules, const mi_gomp_capsule *capsules,
+                                 int64_t n_cuboids, const mi_gomp_cuboid *cuboids, const double *con_lo, const double *con_hi);
 void mi_gomp_scene_free(mi_gomp_scene *sc);          /* before mi_osqp_batch_free of its handle; one scene per handle */
 /* While a scene exists, mi_osqp_batch_reinit_some / _update_A_bounds_some of its handle also keep the QPs' raw constraint
  * data (as ConstraintBuilder::build() produced it) in the scene, so nothing extra is needed when a trajectory enters the

@@ -7,6 +7,7 @@
 //   triDiagonalMatrix        [REF] src/utils.h:33-42,50-64,72-96
 //   ConstraintBuilder<N>     [REF] src/constraints/constraint-builder.h:18-283
 //   CapsuleObstacle          not in the reference: a segment swept by a sphere (posts, pipes, other robots' links; a == b: a sphere)
+//   CuboidObstacle           not in the reference: an oriented box, optionally rounded (bin walls and floors, table tops, shelves)
 //   GOMPSolver<N>            [REF] src/gomp-solver.h:13-201
 //
 // Same names, argument meaning, row layout and control flow as the reference (the known-answer
@@ -209,26 +210,93 @@ inline bool capsulesClear(const std::vector<CapsuleObstacle> &capsules, const Po
   return res;
 }
 
+// ------------------------------------------------------------- cuboid obstacles (not in the reference)
+// An oriented box with centre `centre`, orthonormal axes (the rows of `axes`, world coordinates) and half extents `half`
+// along them, swept by a sphere of radius `radius` (mi_gomp_cuboid is its device twin, include/mi_osqp.h has the formulas in
+// the order both sides compute them).  Outside, a ball is pushed along the unit vector from the closest point of the box -
+// a face, an edge or a corner; inside or on the surface it leaves through the nearest face (the lowest axis on a tie).  Not
+// the work-space box of the gripper balls: that is con_3d.
+class CuboidObstacle {
+ public:
+  using Axes = std::array<double, 9>;
+  CuboidObstacle(const Point &centre_, const Point &half_, double radius_ = 0.0, double margin_ = 0.0)
+      : CuboidObstacle(centre_, Axes{1, 0, 0, 0, 1, 0, 0, 0, 1}, half_, radius_, margin_) {}
+  static CuboidObstacle oriented(const Point &centre, const Axes &axes, const Point &half, double radius = 0.0, double margin = 0.0) {
+    return CuboidObstacle(centre, axes, half, radius, margin);
+  }
+  Point centre;
+  Axes axes;                                                // axes[3 k + i]: component i of axis k
+  Point half;
+  double radius, margin;
+  // the signed distance of P from the sharp box and the unit normal at P, in world coordinates
+  struct Probe { double sd; Point n; };
+  Probe probe(const Point &P) const {
+    const Point d{P[0] - centre[0], P[1] - centre[1], P[2] - centre[2]};
+    Point y, c, v;
+    for (size_t k = 0; k < 3; ++k) {
+      y[k] = axes[3 * k] * d[0] + axes[3 * k + 1] * d[1] + axes[3 * k + 2] * d[2];
+      c[k] = std::fmin(half[k], std::fmax(-half[k], y[k]));
+      v[k] = y[k] - c[k];
+    }
+    const double out = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    Point nl{0.0, 0.0, 0.0};
+    double sd;
+    if (out > 1e-12) {
+      sd = out;
+      for (size_t k = 0; k < 3; ++k) nl[k] = v[k] / out;
+    } else {
+      size_t ks = 0;
+      double slack = half[0] - std::fabs(c[0]);
+      for (size_t k = 1; k < 3; ++k) if (half[k] - std::fabs(c[k]) < slack) { slack = half[k] - std::fabs(c[k]); ks = k; }
+      sd = -slack;
+      nl[ks] = c[ks] < 0.0 ? -1.0 : 1.0;
+    }
+    Probe r{sd, {}};
+    for (size_t i = 0; i < 3; ++i) r.n[i] = nl[0] * axes[i] + nl[1] * axes[3 + i] + nl[2] * axes[6 + i];
+    return r;
+  }
+  double signedDistance(const Point &P) const { return probe(P).sd; }
+  Point normal(const Point &P) const { return probe(P).n; }
+  double clearance(const Point &P, const RobotBall &ball) const { return probe(P).sd - (radius + ball.radius); }
+  bool operator==(const CuboidObstacle &o) const { return centre == o.centre && axes == o.axes && half == o.half && radius == o.radius && margin == o.margin; }
+
+ private:
+  CuboidObstacle(const Point &centre_, const Axes &axes_, const Point &half_, double radius_, double margin_)
+      : centre(centre_), axes(axes_), half(half_), radius(radius_), margin(margin_) {
+    assert(half[0] >= 0.0 && half[1] >= 0.0 && half[2] >= 0.0 && radius >= 0.0 && margin >= 0.0);
+    for (size_t i = 0; i < 3; ++i)
+      for (size_t j = i; j < 3; ++j)
+        assert(std::fabs(axes[3 * i] * axes[3 * j] + axes[3 * i + 1] * axes[3 * j + 1] + axes[3 * i + 2] * axes[3 * j + 2] - (i == j ? 1.0 : 0.0)) <= 1e-9);
+  }
+};
+// the cuboid part of isSolutionOK, for one ball at one waypoint (shared by the three drivers)
+inline bool cuboidsClear(const std::vector<CuboidObstacle> &cuboids, const Point &P, const RobotBall &ball) {
+  bool res = true;
+  for (const CuboidObstacle &cub : cuboids) if (!(cub.clearance(P, ball) >= -ERROR)) res = false;
+  return res;
+}
+
 // ------------------------------------------------------------- constraint-builder.h
 // Rows: (W-1)*D velocity<->position links, then per variable boxes (positions W*D, velocities
-// (W-1)*D, accelerations (W-2)*D), then D*W*(3 + (|obstacles| + |capsules|)*|balls|) rows for the linearised
+// (W-1)*D, accelerations (W-2)*D), then D*W*(3 + (|obstacles| + |capsules| + |cuboids|)*|balls|) rows for the linearised
 // end-effector / obstacle constraints (allocated even when unused: bounds +-INF).
 template <size_t N_DIM>
 class ConstraintBuilder {
   using OptPair = std::pair<std::optional<double>, std::optional<double>>;
 
  public:
-  ConstraintBuilder(size_t waypoints, std::vector<RobotBall> m, std::vector<HorizontalLine> obstacles, std::vector<CapsuleObstacle> capsules = {})
-      : W_(waypoints), balls_(std::move(m)), lines_(std::move(obstacles)), capsules_(std::move(capsules)) {
-    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size())));
-    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size()) * balls_.size())); up_.reserve(lo_.capacity());
+  ConstraintBuilder(size_t waypoints, std::vector<RobotBall> m, std::vector<HorizontalLine> obstacles, std::vector<CapsuleObstacle> capsules = {},
+                    std::vector<CuboidObstacle> cuboids = {})
+      : W_(waypoints), balls_(std::move(m)), lines_(std::move(obstacles)), capsules_(std::move(capsules)), cuboids_(std::move(cuboids)) {
+    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size() + cuboids_.size())));
+    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size())); up_.reserve(lo_.capacity());
     for (size_t t = 0; t + 1 < W_; ++t)                      // v_t - q_{t+1} + q_t = 0
       for (size_t j = 0; j < N_DIM; ++j) {
         lo_.push_back(-INF); up_.push_back(INF);
         put(lo_.size() - 1, {{nthVelocity(t) + j, 1.0}, {nthPos(t + 1) + j, -1.0}, {nthPos(t) + j, 1.0}}, {0.0, 0.0});
       }
     user_off_ = lo_.size();
-    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size()) * balls_.size()));
+    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size()));
     lo_.resize(user_off_ + extra, -INF);
     up_.resize(user_off_ + extra, INF);
   }
@@ -281,6 +349,7 @@ class ConstraintBuilder {
           }
         }
         for (const CapsuleObstacle &cap : capsules_) capsuleRow(row++, ball, cap, p, J, q, w);
+        for (const CuboidObstacle &cub : cuboids_) cuboidRow(row++, ball, cub, p, J, q, w);
       }
     }
     return *this;
@@ -294,7 +363,7 @@ class ConstraintBuilder {
     for (const RobotBall &ball : balls_)
       for (size_t w = 0; w < W_; ++w) {
         if (ball.is_gripper) for (Axis axis : XYZ_AXES) axisRow(row++, ball, axis, J, w, -INF, INF);
-        for (size_t k = 0; k < lines_.size() + capsules_.size(); ++k) axisRow(row++, ball, Z, J, w, -INF, INF);
+        for (size_t k = 0; k < lines_.size() + capsules_.size() + cuboids_.size(); ++k) axisRow(row++, ball, Z, J, w, -INF, INF);
       }
     return *this;
   }
@@ -322,6 +391,7 @@ class ConstraintBuilder {
   std::vector<RobotBall> balls_;
   std::vector<HorizontalLine> lines_;
   std::vector<CapsuleObstacle> capsules_;
+  std::vector<CuboidObstacle> cuboids_;
   // (col, row) -> value, last write wins ([REF] constraint-builder.h:129).  A write log that is sorted into CSC
   // order and de-duplicated on demand: the builder runs once per trajectory, segment and re-linearisation,
   // and a std::map made it the bottleneck of the batched driver.
@@ -411,6 +481,21 @@ class ConstraintBuilder {
     lo_[row] = dist - reach < cap.margin ? (reach - dist) + gq : -INF;
     up_[row] = INF;
   }
+  // n' J with n the cuboid's normal at p (CuboidObstacle::probe), written whether the row is active or not; active within
+  // `margin` of the surface: (R + r) - sd + (n' J) q <= (n' J) x, the ball's radius is part of the bound
+  void cuboidRow(size_t row, const RobotBall &ball, const CuboidObstacle &cub, const Point &p, const std::array<double, 3 * N_DIM> &J,
+                 const Vec<N_DIM> &q, size_t waypoint) {
+    const auto [sd, nrm] = cub.probe(p);
+    const double reach = cub.radius + ball.radius;
+    double gq = 0.0;
+    for (size_t j = 0; j < N_DIM; ++j) {
+      const double g = nrm[0] * J[0 * N_DIM + j] + nrm[1] * J[1 * N_DIM + j] + nrm[2] * J[2 * N_DIM + j];
+      set(nthPos(waypoint) + j, row, g);
+      gq += g * q[j];
+    }
+    lo_[row] = sd - reach < cub.margin ? (reach - sd) + gq : -INF;
+    up_[row] = INF;
+  }
 };
 
 // ------------------------------------------------------------------- gomp-solver.h
@@ -455,6 +540,7 @@ class GOMPSolver {
     }
     for (int i = SEGMENTS; i >= 1; --i) {
       const size_t waypoints = max_waypoints * i / SEGMENTS;
+      if (waypoints < 4) break;                              // (max_waypoints < 40: the last horizons are too short for the end conditions)
       QPVector warm_start(waypoints * N_DIM * 2);
       // same slicing as the reference, including its quirk for i < SEGMENTS (the "velocity" half is
       // taken at offset W*D of the previous, longer solution)
@@ -495,6 +581,8 @@ class GOMPSolver {
   bool prefetch_patterns = true;
   // Not in the reference: capsule / sphere obstacles besides the lines; set before run()
   std::vector<CapsuleObstacle> capsules;
+  // Not in the reference either: cuboid obstacles (oriented boxes); set before run()
+  std::vector<CuboidObstacle> cuboids;
   // (tests) the acceptance test that ends the SQP loop
   bool acceptable(const QPVector &q_trajectory) const { return isSolutionOK(q_trajectory); }
 
@@ -523,7 +611,7 @@ class GOMPSolver {
   }
   ConstraintBuilder<N_DIM> jointSpaceRows(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
     assert(waypoints >= 4);
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -552,6 +640,7 @@ class GOMPSolver {
         for (const HorizontalLine &line : obstacles)
           if (line.hasCollision(w, xyz, ball) && !line.isAbove(p, ball)) res = false;
         if (!capsulesClear(capsules, p, ball)) res = false;
+        if (!cuboidsClear(cuboids, p, ball)) res = false;
       }
     }
     return res;
@@ -594,6 +683,7 @@ class BatchGOMPSolver {
     }
     for (int i = SEGMENTS; i >= 1; --i) {
       const size_t waypoints = max_waypoints * i / SEGMENTS;
+      if (waypoints < 4) break;                                // (max_waypoints < 40: the last horizons are too short for the end conditions)
       std::vector<size_t> ids;                                 // batch slot -> trajectory
       for (size_t b = 0; b < B; ++b) if (alive[b]) ids.push_back(b);
       if (ids.empty()) break;
@@ -681,6 +771,7 @@ class BatchGOMPSolver {
   int batch_solves = 0;
   bool reuse_solvers = true;      // keep the per-segment solvers across run() calls (see run())
   std::vector<CapsuleObstacle> capsules;      // capsule / sphere obstacles besides the lines; set before run()
+  std::vector<CuboidObstacle> cuboids;        // cuboid obstacles (oriented boxes); set before run()
   int solver_reuses = 0;          // how often a kept solver was re-initialised instead of a new one being built
   // where the wall time of the last run() went: building constraints, QP setup (analysis + upload + factorisation),
   // batched solves, feasibility checks + re-linearisation + update
@@ -714,7 +805,7 @@ class BatchGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -743,6 +834,7 @@ class BatchGOMPSolver {
         for (const HorizontalLine &line : obstacles)
           if (line.hasCollision(w, xyz, ball) && !line.isAbove(p, ball)) res = false;
         if (!capsulesClear(capsules, p, ball)) res = false;
+        if (!cuboidsClear(cuboids, p, ball)) res = false;
       }
     }
     return res;
@@ -776,9 +868,10 @@ class ContinuousGOMPSolver {
     const size_t B = starts.size();
     assert(ends.size() == B && B > 0);
     starts_ = &starts; ends_ = &ends;
-    if (!(capsules == scene_capsules_)) {                    // the kept scenes hold the capsules of the run that made them
+    if (!(capsules == scene_capsules_ && cuboids == scene_cuboids_)) {   // the kept scenes hold the capsules and cuboids of the run that made them
       for (Stage &st : stages_) if (st.scene) { mi_gomp_scene_free(st.scene); st.scene = nullptr; }
       scene_capsules_ = capsules;
+      scene_cuboids_ = cuboids;
     }
     traj_.clear(); traj_.resize(B);
     segments_run.assign(B, 0); qp_solves.assign(B, 0); qp_updates.assign(B, 0);
@@ -823,6 +916,9 @@ class ContinuousGOMPSolver {
   // Capsule / sphere obstacles besides the lines; set before run().  On the device path they go into the scene
   // (mi_gomp_scene_create_world).
   std::vector<CapsuleObstacle> capsules;
+  // Cuboid obstacles (oriented boxes, optionally rounded); set before run().  On the device path they go into the scene
+  // (mi_gomp_scene_create_cuboids).
+  std::vector<CuboidObstacle> cuboids;
   int pipeline_depth = 1;              // 2: a stage enqueues its next advance before it looks at the previous one's results
   int segments_per_advance = 4;        // a launch runs on until a QP of the stage finishes, at most that many segments
   // per stage: {waypoints, advances, seconds admitting, waiting for the device, processing finished QPs, idle}
@@ -865,6 +961,7 @@ class ContinuousGOMPSolver {
   std::vector<Traj> traj_;
   std::array<Stage, SEGMENTS> stages_;
   std::vector<CapsuleObstacle> scene_capsules_;
+  std::vector<CuboidObstacle> scene_cuboids_;
   const std::vector<Ctrl<N_DIM>> *starts_ = nullptr, *ends_ = nullptr;
   std::atomic<size_t> finished_{0};
   std::atomic<bool> failed_{false};
@@ -874,6 +971,7 @@ class ContinuousGOMPSolver {
   void stageLoop(int s, size_t B) {
     Stage &st = stages_[(size_t)s];
     const size_t W = st.waypoints;
+    if (W < 4) return;                               // (max_waypoints < 40: too short for the end conditions; nothing is sent here, see process())
     const QPMatrixSparse P = triDiagonalMatrix(2, -1, (int)(N_DIM * 2 * W), (int)(W * N_DIM), (int)N_DIM);
     const ConstraintBuilder<N_DIM> tmpl = jointSpaceTemplate((*starts_)[0], (*ends_)[0], W);
     int in_flight = 0;                               // advances enqueued and not polled
@@ -974,7 +1072,18 @@ class ContinuousGOMPSolver {
       g.radius = c.radius; g.margin = c.margin;
       caps.push_back(g);
     }
-    const int rc = !caps.empty() ? mi_gomp_scene_create_world(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+    std::vector<mi_gomp_cuboid> cubs;
+    for (const CuboidObstacle &c : cuboids) {
+      mi_gomp_cuboid g{};
+      for (int k = 0; k < 3; ++k) { g.centre[k] = c.centre[k]; g.half[k] = c.half[k]; }
+      for (int k = 0; k < 9; ++k) g.axes[k] = c.axes[k];
+      g.radius = c.radius; g.margin = c.margin;
+      cubs.push_back(g);
+    }
+    const int rc = !cubs.empty() ? mi_gomp_scene_create_cuboids(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+                                                                (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(),
+                                                                (int64_t)cubs.size(), cubs.data(), lo, hi)
+                   : !caps.empty() ? mi_gomp_scene_create_world(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
                                                               (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(), lo, hi)
                    : dh_chain ? mi_gomp_scene_create_chain(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, &*dh_chain, (int64_t)balls.size(),
                                                          balls.data(), (int64_t)lines.size(), lines.data(), lo, hi)
@@ -1039,7 +1148,7 @@ class ContinuousGOMPSolver {
       Traj &T = traj_[b];
       ++segments_run[b];
       if (T.seg_code == ExitCode::kOptimal) { T.last_code = ExitCode::kOptimal; T.last_solution = T.seg_solution; }
-      if (s + 1 < SEGMENTS) {
+      if (s + 1 < SEGMENTS && stages_[(size_t)s + 1].waypoints >= 4) {
         Stage &nx = stages_[(size_t)s + 1];
         { std::lock_guard<std::mutex> lk(nx.mu); nx.inbox.push_back(b); }
         nx.cv.notify_one();
@@ -1058,7 +1167,7 @@ class ContinuousGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -1087,6 +1196,7 @@ class ContinuousGOMPSolver {
         for (const HorizontalLine &line : obstacles)
           if (line.hasCollision(w, xyz, ball) && !line.isAbove(p, ball)) res = false;
         if (!capsulesClear(capsules, p, ball)) res = false;
+        if (!cuboidsClear(cuboids, p, ball)) res = false;
       }
     }
     return res;

@@ -3780,7 +3780,8 @@ hipError_t launch_ruiz(const RuizArgs &a, hipStream_t st) {
 // line's vertical plane at that waypoint (HorizontalLine::hasCollision: close to it, or on opposite sides of it from a
 // neighbouring waypoint), a dummy row otherwise - and the trajectory is accepted when every ball respects the box and is above
 // (below) the lines it collides with.  Every (ball, capsule) pair gets one row after the lines' (see the loop over g.caps) and
-// must keep a clearance of -1e-3 or more.  One workgroup per trajectory, one thread per (ball, waypoint).
+// must keep a clearance of -1e-3 or more; every (ball, cuboid) pair one row after the capsules', by the same rule.  One
+// workgroup per trajectory, one thread per (ball, waypoint).
 __device__ __forceinline__ void ur5e_point(const double *q, int frame, double *p, double *J /* 3 x 6 row-major */) {
   const double a[6] = {0.0, -0.425, -0.3922, 0.0, 0.0, 0.0}, d[6] = {0.1625, 0.0, 0.0, 0.1333, 0.0997, 0.0996};
   const double alpha[6] = {1.5707963267948966, 0.0, 0.0, 1.5707963267948966, -1.5707963267948966, 0.0};
@@ -3882,7 +3883,7 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
   extern __shared__ double smem[];                 // xyz[n_balls][W][3]
   __shared__ int s_ok;
   const int jq = blockIdx.x, qp = g.ids[jq], tid = threadIdx.x;
-  const int D = g.dims, W = g.W, NB = g.n_balls, NL = g.n_lines, NC = g.n_caps;
+  const int D = g.dims, W = g.W, NB = g.n_balls, NL = g.n_lines, NC = g.n_caps, NX = g.n_cuboids;
   const double *traj = g.traj + (size_t)jq * g.n;
   if (tid == 0) s_ok = 1;
   double p[3] = {0, 0, 0}, J[3 * MI_GOMP_MAXD], q[MI_GOMP_MAXD];
@@ -3915,8 +3916,8 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
     for (int ax = 0; ax < 3; ax++) { double sacc = 0.0; for (int j = 0; j < D; j++) sacc += J[ax * D + j] * q[j]; Jq[ax] = sacc; }
     // this pair's first row: the balls before it (all their waypoints), then the waypoints before it of this ball
     int row = g.row0;
-    for (int b2 = 0; b2 < bi; b2++) row += W * ((g.balls[b2].is_gripper ? 3 : 0) + NL + NC);
-    row += w * ((ball.is_gripper ? 3 : 0) + NL + NC);
+    for (int b2 = 0; b2 < bi; b2++) row += W * ((g.balls[b2].is_gripper ? 3 : 0) + NL + NC + NX);
+    row += w * ((ball.is_gripper ? 3 : 0) + NL + NC + NX);
     auto put = [&](int r, int axis, double low, double upp) {
       if (!wr) return;
       const int *ai = g.aidx + (size_t)(r - g.row0) * D;
@@ -3969,6 +3970,45 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
         gq += gj * q[j];
       }
       g.l[(size_t)qp * g.m + row] = s < cp.margin ? (reach - dist) + gq : -MI_INFTY;
+      g.u[(size_t)qp * g.m + row] = MI_INFTY;
+    }
+    // cuboids (CuboidObstacle of gomp.hpp, formulas at mi_gomp_cuboid): the ball's centre in the box's frame, clamped to the
+    // half extents; outside, the normal is the unit vector from the closest point of the box; inside or on the surface it is
+    // the axis of the nearest face (the lowest axis on a tie), signed by the side.  That axis differs from lane to lane, so it
+    // is a pair of selects, never an index (an indexed array would live in scratch); the cuboid is uniform, its loads scalar.
+    for (int xi = 0; xi < NX; xi++, row++) {
+      const GompCuboidDev &cb = g.cuboids[xi];
+      const double d0 = p[0] - cb.o[0], d1 = p[1] - cb.o[1], d2 = p[2] - cb.o[2];
+      const double y0 = cb.u[0] * d0 + cb.u[1] * d1 + cb.u[2] * d2;
+      const double y1 = cb.u[3] * d0 + cb.u[4] * d1 + cb.u[5] * d2;
+      const double y2 = cb.u[6] * d0 + cb.u[7] * d1 + cb.u[8] * d2;
+      const double c0 = fmin(cb.h[0], fmax(-cb.h[0], y0)), c1 = fmin(cb.h[1], fmax(-cb.h[1], y1)), c2 = fmin(cb.h[2], fmax(-cb.h[2], y2));
+      const double v0 = y0 - c0, v1 = y1 - c1, v2 = y2 - c2;
+      const double out = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+      const bool outside = out > 1e-12;
+      const double k0 = cb.h[0] - fabs(c0), k1 = cb.h[1] - fabs(c1), k2 = cb.h[2] - fabs(c2);
+      const bool pick1 = k1 < k0;
+      const double k01 = pick1 ? k1 : k0;
+      const bool pick2 = k2 < k01;
+      const double sd = outside ? out : -(pick2 ? k2 : k01);
+      const double reach = cb.R + ball.radius;
+      const double s = sd - reach;
+      if (!(s >= -1e-3)) ok = 0;
+      if (!wr) continue;
+      const double nl0 = outside ? v0 / out : (pick1 || pick2 ? 0.0 : (c0 < 0.0 ? -1.0 : 1.0));
+      const double nl1 = outside ? v1 / out : (pick1 && !pick2 ? (c1 < 0.0 ? -1.0 : 1.0) : 0.0);
+      const double nl2 = outside ? v2 / out : (pick2 ? (c2 < 0.0 ? -1.0 : 1.0) : 0.0);
+      const double n0 = nl0 * cb.u[0] + nl1 * cb.u[3] + nl2 * cb.u[6];
+      const double n1 = nl0 * cb.u[1] + nl1 * cb.u[4] + nl2 * cb.u[7];
+      const double n2 = nl0 * cb.u[2] + nl1 * cb.u[5] + nl2 * cb.u[8];
+      const int *ai = g.aidx + (size_t)(row - g.row0) * D;
+      double gq = 0.0;
+      for (int j = 0; j < D; j++) {
+        const double gj = n0 * J[0 * D + j] + n1 * J[1 * D + j] + n2 * J[2 * D + j];
+        g.A[(size_t)qp * g.nnzA + ai[j]] = gj;                                               // written for inactive rows too
+        gq += gj * q[j];
+      }
+      g.l[(size_t)qp * g.m + row] = s < cb.margin ? (reach - sd) + gq : -MI_INFTY;
       g.u[(size_t)qp * g.m + row] = MI_INFTY;
     }
   }
