@@ -65,7 +65,8 @@ class Stats(C.Structure):
                 ("iterate_launches_deep_ring", C.c_int64), ("iterate_launches_long_head", C.c_int64),
                 ("runahead_regions", C.c_int64), ("runahead_tiles", C.c_int64), ("runahead_left", C.c_int64),
                 ("runahead_missed", C.c_int64),
-                ("region_priority", C.c_int64), ("region_lane_checks", C.c_int64), ("region_chunks", C.c_int64)]
+                ("region_priority", C.c_int64), ("region_lane_checks", C.c_int64), ("region_chunks", C.c_int64),
+                ("ring_early", C.c_int64), ("resident_index_words", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -208,6 +209,7 @@ def lib():
         L.mi_osqp_debug_runahead_group.argtypes = [C.c_int64, ip, dp, dp, C.c_int64, C.c_int64, ip, ip]
         L.mi_osqp_debug_region_chunks.argtypes = [C.c_int64] * 3 + [ip] * 2
         L.mi_osqp_debug_iterate_form.argtypes = [C.c_int64] * 4 + [ip]
+        L.mi_osqp_debug_index_words_fit.argtypes = [C.c_int64] * 6 + [ip] * 3
         L.mi_osqp_prefetch_analysis.argtypes = [C.c_int64, C.c_int64, C.c_int64, ip, ip, ip, ip, C.c_int64]
         L.mi_osqp_debug_host_block_factor.argtypes = [C.c_int64, C.c_int64, ip, ip, dp, ip, ip, dp, dp, dp,
                                                       C.POINTER(Settings), dp, dp, ip]
@@ -968,6 +970,16 @@ def debug_iterate_form(tiles, has_head=True, forced_form=0, long_min=-1):
     form = C.c_int64()
     _chk(lib().mi_osqp_debug_iterate_form(tiles, int(bool(has_head)), forced_form, long_min, C.byref(form)), "debug_iterate_form")
     return int(form.value)
+
+
+def debug_index_words_fit(n, m, tile=1, threads=1024, resident_state=True, lds_vector=True):
+    """Host-only: whether the resident iterate of a handle keeps its index words (each thread's entries of pinv and xloc) in
+    registers (host_core.hpp index_words_fit; stats()["resident_index_words"]).  Returns (fit, xloc trips a thread may
+    have, pinv trips per row kind a thread may have)."""
+    fit, xt, pt = C.c_int64(), C.c_int64(), C.c_int64()
+    _chk(lib().mi_osqp_debug_index_words_fit(int(bool(resident_state)), int(bool(lds_vector)), tile, threads, n, m,
+                                             C.byref(fit), C.byref(xt), C.byref(pt)), "debug_index_words_fit")
+    return bool(fit.value), int(xt.value), int(pt.value)
 
 
 def debug_host_block_factor(P, A, l, u, **settings):

@@ -1050,6 +1050,8 @@ Tuning tuning_from_env() {
   if (const char *e = getenv("MI_OSQP_RUNAHEAD_END")) t.runahead_end = std::max(0, atoi(e));
   if (const char *e = getenv("MI_OSQP_RF_FORM")) { const int v = atoi(e); if (v == kIterDeepRing || v == kIterLongHead) t.rf_form = v; }
   if (const char *e = getenv("MI_OSQP_RF_LONG_MIN")) t.rf_long_min = std::max(0, atoi(e));
+  if (const char *e = getenv("MI_OSQP_INDEX_LOADS")) t.index_loads = atoi(e) != 0;
+  if (const char *e = getenv("MI_OSQP_RING_EARLY")) t.ring_early = atoi(e) != 0;
   AnalysisTuning &a = t.analysis;
   if (const char *e = getenv("MI_OSQP_DENSE_TAIL")) a.dense_tail = atoi(e);
   if (const char *e = getenv("MI_OSQP_ORDERING")) a.ordering = e[0];
@@ -1165,6 +1167,12 @@ int iterate_form(int tiles, bool has_head, const Tuning &t) {
   if (t.rf_form == kIterDeepRing || t.rf_form == kIterLongHead) return t.rf_form;
   const int long_min = t.rf_long_min >= 0 ? t.rf_long_min : kRfLongMinDefault;
   return tiles > 0 && tiles >= long_min ? kIterLongHead : kIterDeepRing;       // (a launch without a tile does nothing in either form)
+}
+
+bool index_words_fit(bool resident_state, bool lds_vector, int bt, int threads, int64_t n, int64_t m) {
+  if (!resident_state || !lds_vector || bt < 1 || threads < 64 || n < 1 || m < 0) return false;
+  const int64_t xcap = (int64_t)MI_IX_XLOC_TRIPS * threads, pcap = (int64_t)MI_IX_PINV_TRIPS * threads;
+  return (n + m) * bt <= xcap && n * bt <= pcap && m * bt <= pcap;
 }
 
 // --------------------------------------------------------------------- analyze

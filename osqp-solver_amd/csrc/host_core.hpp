@@ -48,6 +48,7 @@ struct AnalysisTuning {            // what analyze() reads
 constexpr bool kRunaheadDefault = true;      // (measured: DESIGN.md section 4, "Measurements (run-ahead)")
 constexpr int kRegionPriorityDefault = 0;
 constexpr bool kLaneChecksDefault = false;
+constexpr bool kRingEarlyDefault = false;      // (measured: DESIGN.md section 4, "Measurements (index words in registers)")
 struct Tuning {
   int tile = 0;                    // MI_OSQP_TILE: 1, 2 or 4 QPs per tile
   int threads = 0;                 // MI_OSQP_THREADS: threads per tile of the solve kernels (64 .. 1024)
@@ -81,9 +82,19 @@ struct Tuning {
   // form of the resident head of S^-1 per iterate launch (iterate_form below)
   int rf_form = 0;                 // MI_OSQP_RF_FORM: 1 the deep ring, 2 the long head in every launch of the handle; 0 = by the threshold
   int rf_long_min = -1;            // MI_OSQP_RF_LONG_MIN: launches that iterate at least so many tiles take the long head (0 = every launch); -1 = the default, kRfLongMinDefault
+  bool index_loads = false;        // MI_OSQP_INDEX_LOADS=1: the resident iterate loads its words of pinv and xloc in every iteration even where they fit registers (index_words_fit below)
+  bool ring_early = kRingEarlyDefault;      // MI_OSQP_RING_EARLY=0 / 1: with the index words in registers (one QP per tile), every sweep's first ring revolution is issued under the LDS pass in front of it
   AnalysisTuning analysis;
 };
 Tuning tuning_from_env();
+
+// Index words of the resident iterate in registers (kernels.hip iterate_body IX): a thread of a tile walks the same entries
+// e = tid + j * threads of xloc (the D^-1 pass, N * bt entries) and of pinv (the vector step: n * bt entries of the x rows,
+// m * bt of the z / y rows) in every iteration, so it may load them once per launch and keep them - if the handle keeps the
+// resident state (which implies the LDS solve vector: the words are 16-bit LDS positions) and no thread has more trips than
+// the registers set aside for them hold: N * bt <= MI_IX_XLOC_TRIPS * threads and n * bt, m * bt <= MI_IX_PINV_TRIPS * threads
+// (sched_format.h; the headline shape at 1024 threads: two trips of xloc, one of each kind of pinv, two VGPRs).
+bool index_words_fit(bool resident_state, bool lds_vector, int bt, int threads, int64_t n, int64_t m);
 
 // Form of the S^-1 product of one iterate launch of a handle with the resident head (kernels.hip dense_tail_apply_rf; the
 // values are device_types.h RF_FORM_*).  tiles = the tiles the launch will actually iterate (finished tiles of the grid leave

@@ -28,3 +28,9 @@
 // value-source codes of a slot (Schedule::src and the maps derived from it)
 #define MI_SRC_ZERO (-1)
 #define MI_SRC_ONE (-2)
+// Index words of the resident iterate in registers (kernels.hip iterate_body IX, host_core.hpp index_words_fit): the most
+// trips of the D^-1 pass (entries e = tid + j * threads of xloc) and of either loop of the vector step (entries of pinv,
+// the x rows and the z / y rows) a thread may have.  16-bit LDS positions, two to a VGPR: MI_IX_XLOC_TRIPS / 2 +
+// MI_IX_PINV_TRIPS registers per thread for a whole call.
+#define MI_IX_XLOC_TRIPS 2
+#define MI_IX_PINV_TRIPS 1
