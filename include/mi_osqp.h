@@ -117,7 +117,6 @@ typedef struct {
   int64_t iterate_launches_deep_ring, iterate_launches_long_head;   /* iterate launches since setup by the form of the resident head they ran (MI_OSQP_RF_FORM, MI_OSQP_RF_LONG_MIN): 16 steps resident and a product ring of 16, or resident_factor_steps (32) and a ring of 8; both 0 on a handle without a head */
   int64_t runahead_regions, runahead_tiles, runahead_left, runahead_missed;   /* run-ahead since setup (switches, read at setup: MI_OSQP_RUNAHEAD = 0 / 1 off / on, MI_OSQP_RUNAHEAD_TILES = tiles of a group, default half the CUs, MI_OSQP_RUNAHEAD_MIN = active tiles below which no group is sent, default the CU count, MI_OSQP_RUNAHEAD_END = most segments of a chain, default up to the rho-update point after next): pipelined rho-update points that sent the active tiles furthest from convergence ahead as a chain of launches beside the region, without a host turn; tiles sent; members still active when their chain ended (they went on alone afterwards); QPs outside the groups still active after the segment that follows the region (late QPs the group did not hold) */
   int64_t region_priority, region_lane_checks, region_chunks;   /* the last pipelined rho-update point (0 before the first; switches read at setup): the stream priorities it ran with, MI_OSQP_REGION_PRIORITY - 0 every stream alike, 1 the chunk lanes at the least priority of the device, 2 the run-ahead chain on a stream of its own at the greatest, -1 asked for 1 or 2 where that priority is the one every stream has, so nothing changed; 1 when every lane failed and checked its own chunks and only the flag copy followed the join (MI_OSQP_LANE_CHECKS, one-QP tiles); its refactorisation chunks (default size: mi_osqp_debug_region_chunks) */
-  int64_t ring_early;   /* 1: the resident iterate with its index words in registers (one QP per tile) issues every sweep's first ring revolution under the LDS pass in front of the sweep (MI_OSQP_RING_EARLY=1, read at setup; off by default); 0: every sweep fills its own ring */
   int64_t resident_index_words;   /* 1: every thread of the resident iterate keeps its entries of the permutation tables (pinv, xloc) in registers across a launch, so the passes between the sweeps load nothing; 0: they are loaded in every iteration (no resident state, more entries per thread than the registers set aside hold - mi_osqp_debug_index_words_fit - or MI_OSQP_INDEX_LOADS=1, read at setup) */
 } mi_osqp_stats;
 

@@ -66,7 +66,7 @@ class Stats(C.Structure):
                 ("runahead_regions", C.c_int64), ("runahead_tiles", C.c_int64), ("runahead_left", C.c_int64),
                 ("runahead_missed", C.c_int64),
                 ("region_priority", C.c_int64), ("region_lane_checks", C.c_int64), ("region_chunks", C.c_int64),
-                ("ring_early", C.c_int64), ("resident_index_words", C.c_int64)]
+                ("resident_index_words", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

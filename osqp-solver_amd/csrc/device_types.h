@@ -67,7 +67,6 @@ struct KernelArgs {
   int rf_off;                           // iterate launches: LDS offset (in doubles) of the LDS part of the resident head of S^-1 (iterate_body RF), 0 = streamed
   int rf_form;                          // with rf_off: the form of the head this launch runs (RF_FORM_DEEP_RING, RF_FORM_LONG_HEAD); every launch reloads its head, so launches of one solve may differ
   int ix;                               // with rs_off: every thread keeps its entries of pinv and xloc in registers for the whole call (iterate_body IX; host_core.hpp index_words_fit), 0 = loaded in every iteration
-  int re;                               // with ix, one QP per tile: every sweep's first ring revolution is issued under the LDS pass in front of it (iterate_body RE; MI_OSQP_RING_EARLY)
   int wide;                             // 32-bit gather / row indices (Schedule::idxw64): vectors of 65 535 entries and more; needs xs_global, BT = 1
   // settings (row S)
   double sigma, alpha, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, rho_tolerance;

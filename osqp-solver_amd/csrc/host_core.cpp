@@ -1051,7 +1051,6 @@ Tuning tuning_from_env() {
   if (const char *e = getenv("MI_OSQP_RF_FORM")) { const int v = atoi(e); if (v == kIterDeepRing || v == kIterLongHead) t.rf_form = v; }
   if (const char *e = getenv("MI_OSQP_RF_LONG_MIN")) t.rf_long_min = std::max(0, atoi(e));
   if (const char *e = getenv("MI_OSQP_INDEX_LOADS")) t.index_loads = atoi(e) != 0;
-  if (const char *e = getenv("MI_OSQP_RING_EARLY")) t.ring_early = atoi(e) != 0;
   AnalysisTuning &a = t.analysis;
   if (const char *e = getenv("MI_OSQP_DENSE_TAIL")) a.dense_tail = atoi(e);
   if (const char *e = getenv("MI_OSQP_ORDERING")) a.ordering = e[0];

@@ -48,7 +48,6 @@ struct AnalysisTuning {            // what analyze() reads
 constexpr bool kRunaheadDefault = true;      // (measured: DESIGN.md section 4, "Measurements (run-ahead)")
 constexpr int kRegionPriorityDefault = 0;
 constexpr bool kLaneChecksDefault = false;
-constexpr bool kRingEarlyDefault = false;      // (measured: DESIGN.md section 4, "Measurements (index words in registers)")
 struct Tuning {
   int tile = 0;                    // MI_OSQP_TILE: 1, 2 or 4 QPs per tile
   int threads = 0;                 // MI_OSQP_THREADS: threads per tile of the solve kernels (64 .. 1024)
@@ -83,7 +82,6 @@ struct Tuning {
   int rf_form = 0;                 // MI_OSQP_RF_FORM: 1 the deep ring, 2 the long head in every launch of the handle; 0 = by the threshold
   int rf_long_min = -1;            // MI_OSQP_RF_LONG_MIN: launches that iterate at least so many tiles take the long head (0 = every launch); -1 = the default, kRfLongMinDefault
   bool index_loads = false;        // MI_OSQP_INDEX_LOADS=1: the resident iterate loads its words of pinv and xloc in every iteration even where they fit registers (index_words_fit below)
-  bool ring_early = kRingEarlyDefault;      // MI_OSQP_RING_EARLY=0 / 1: with the index words in registers (one QP per tile), every sweep's first ring revolution is issued under the LDS pass in front of it
   AnalysisTuning analysis;
 };
 Tuning tuning_from_env();

@@ -278,45 +278,26 @@ __device__ __forceinline__ uint32_t load_desc(const ValSrc<BT> &vs, uint32_t pos
   return pos + (uint32_t)lane < end ? d : MI_D_NOOP;
 }
 
-// The first revolution of a ring, issued ahead of its sweep (run_stream PRE): the loads of run_stream's first trip, in its order.
-template <int BT, int PF, bool WIDE>
-__device__ __forceinline__ void ring_start(const ValSrc<BT> &vs, uint32_t begin, uint32_t end, int lane, Ring<BT, PF> &r) {
-  r.desc = load_desc(vs, begin, end, lane);
-#pragma unroll
-  for (int st = 0; st < PF; st++) {
-    r.gr[st] = 0u;
-    load_step<BT, WIDE>(vs, begin + (uint32_t)st, lane, r.v[st], r.gi[st], r.gr[st]);
-  }
-}
-
 // Walk the stream [begin, end) of this wave, then pass `tail` more barriers.
 //   SUB  = true : triangular solves (xs[row] -= sum, or xs[row] = sum on store steps); false: out[row] = sum (SpMV)
 //   BAR  = the schedule has barriers (GX: full __syncthreads, the vector is in global memory)
 //   TR   = debug instantiations: 1: lane 0 logs the shader clock before / after every barrier into
 //          tr[(ordinal of the barrier * nw + wave) * 2 + {0, 1}]; 2: also the time spent waiting for ring slots
-//   PRE  = the ring arrives filled: ring_start issued the first revolution (steps begin .. begin + PF - 1 and their
-//          descriptor word) earlier, under the LDS pass in front of the sweep (iterate_body RE)
-template <int BT, int PF, bool SUB, bool BAR, bool GX, int TR = 0, bool WIDE = false, bool PRE = false>
+template <int BT, int PF, bool SUB, bool BAR, bool GX, int TR = 0, bool WIDE = false>
 __device__ __forceinline__ void run_stream(const ValSrc<BT> &vs, uint32_t begin, uint32_t end, uint32_t tail, double *xs,
                                            double *out, int lane, uint32_t *tr = nullptr, int wave = 0, int nw = 0,
-                                           uint32_t *tw = nullptr, const Ring<BT, PF> *pre = nullptr) {
+                                           uint32_t *tw = nullptr) {
   double *base = SUB ? xs : out;
   // The ring starts empty (all no-ops) and the first revolution only fills it: there is no separate prologue
   // whose load order the compiler could permute -- with one, the wait counts of the loop (merged over both
   // entries) collapse to nearly vmcnt(0) and the ring drains at every step.
-  // (PRE is such a prologue, issued in the loop's own order - descriptor word, then index word and value of every step -
-  //  with nothing but LDS traffic and LDS-only barriers between it and the loop; its ISA is in profiles/r12.)
   Ring<BT, PF> r;
-  if constexpr (PRE) {
-    r = *pre;
-  } else {
-    r.desc = MI_D_NOOP;
+  r.desc = MI_D_NOOP;
 #pragma unroll
-    for (int st = 0; st < PF; st++) {
-      r.gi[st] = 0u; r.gr[st] = 0u;
+  for (int st = 0; st < PF; st++) {
+    r.gi[st] = 0u; r.gr[st] = 0u;
 #pragma unroll
-      for (int b = 0; b < BT; b++) r.v[st][b] = 0.0;
-    }
+    for (int b = 0; b < BT; b++) r.v[st][b] = 0.0;
   }
   constexpr uint32_t NONE = WIDE ? 0xFFFFFFFFu : 0xFFFFu;
   static_assert(PF % (MI_D_LOOKAHEAD + 1) == 0, "the gather slots must line up across ring revolutions");
@@ -334,7 +315,7 @@ __device__ __forceinline__ void run_stream(const ValSrc<BT> &vs, uint32_t begin,
     if constexpr (GX) __syncthreads(); else lds_barrier();
     if constexpr (TR) { if (lane == 0) tr[((size_t)nbar_seen * nw + wave) * 2 + 1] = (uint32_t)__builtin_amdgcn_s_memtime(); nbar_seen++; }
   };
-  for (uint32_t npos = PRE ? begin + PF : begin; npos < end + PF; npos += PF) {   // this revolution runs steps npos - PF + st, loads npos + st
+  for (uint32_t npos = begin; npos < end + PF; npos += PF) {   // this revolution runs steps npos - PF + st, loads npos + st
     const uint32_t dnext = load_desc(vs, npos, end, lane);     // older than every refill below
 #pragma unroll
     for (int st = 0; st < PF; st++) {
@@ -583,18 +564,6 @@ __device__ __forceinline__ void run_tri(const SchedDev &s, const ValSrc<BT> &val
   const uint32_t begin = lp[wave], end = lp[(size_t)s.n_levels * s.nw + wave], tail = as_const(s.tail_bar)[wave];
   if constexpr (GX && TR == 0 && BT <= 2) run_stream_gx<BT, MI_GX_PF, MI_GX_LA, WIDE>(vals, begin, end, tail, xs, lane);     // (BT = 4: registers)
   else run_stream<BT, PF, true, true, GX, TR, WIDE>(vals, begin, end, tail, xs, nullptr, lane, tr, wave, s.nw, tw);
-}
-// The same in two halves (LDS vector): tri_start issues the ring's first revolution, tri_finish runs the sweep from it.
-template <int BT, int PF>
-__device__ __forceinline__ void tri_start(const SchedDev &s, const ValSrc<BT> &vals, int wave, int lane, Ring<BT, PF> &r) {
-  mi_cptr lp = as_const(s.lvl_pos);
-  ring_start<BT, PF, false>(vals, lp[wave], lp[(size_t)s.n_levels * s.nw + wave], lane, r);
-}
-template <int BT, int PF>
-__device__ __forceinline__ void tri_finish(const SchedDev &s, const ValSrc<BT> &vals, double *xs, int wave, int lane, const Ring<BT, PF> &r) {
-  mi_cptr lp = as_const(s.lvl_pos);
-  const uint32_t begin = lp[wave], end = lp[(size_t)s.n_levels * s.nw + wave], tail = as_const(s.tail_bar)[wave];
-  run_stream<BT, PF, true, true, false, 0, false, true>(vals, begin, end, tail, xs, nullptr, lane, nullptr, wave, s.nw, nullptr, &r);
 }
 
 // SpMV with the same streams: levels [l0, l1) of the check schedule (independent rows, no barriers)
@@ -853,10 +822,9 @@ __device__ __forceinline__ void dense_tail_apply(const DenseTailDev &dt, const m
 // register steps / ring depth of form RF (RF_FORM_DEEP_RING, RF_FORM_LONG_HEAD; 1 / MI_RF_PF_DEEP without a head)
 __host__ __device__ constexpr int rf_reg_steps(int RF) { return RF == RF_FORM_LONG_HEAD ? MI_RF_R_LONG : RF == RF_FORM_DEEP_RING ? MI_RF_R_DEEP : 1; }
 __host__ __device__ constexpr int rf_ring_steps(int RF) { return RF == RF_FORM_LONG_HEAD ? MI_RF_PF_LONG : MI_RF_PF_DEEP; }
-struct NoEarly { __device__ __forceinline__ void operator()() const {} };      // (`early` of the forms without an early ring)
-template <int R, int RL, int PF, class F = NoEarly>
+template <int R, int RL, int PF>
 __device__ __forceinline__ void dense_tail_apply_rf(const DenseTailDev &dt, const mi_rsrc &vals, const double *xt, double *yr, double *yc,
-                                                    double (&keep)[R], double *hl, bool first, int wave, int lane, F early = F{}) {
+                                                    double (&keep)[R], double *hl, bool first, int wave, int lane) {
   constexpr int H = R + RL;
   static_assert(H % PF == 0 && H <= 32 && RL <= PF, "the head is whole ring revolutions inside the shortest task");
   mi_cptr tk = as_const(dt.task);
@@ -932,7 +900,6 @@ __device__ __forceinline__ void dense_tail_apply_rf(const DenseTailDev &dt, cons
       if (left == 0) flush();
     }
   }
-  early();      // (iterate_body RE: the backward sweep's first ring revolution - the product has issued its last load, rv is dead)
   for (uint32_t nb = as_const(dt.tail_bar)[wave]; nb; nb--) lds_barrier();
 }
 
@@ -951,19 +918,22 @@ __device__ __forceinline__ uint32_t ix_pos(uint32_t w, bool high) { return high 
 // they live through the sweeps and the product: 128 VGPRs and 16 of them spilled in the long-head form (profiles/r12).
 __device__ __forceinline__ int ix_opaque(int tid) { asm volatile("" : "+v"(tid)); return tid; }
 
+// One entry of the D^-1 pass in front of the dense-tail product: a row before the tail is scaled where the sweeps keep it
+// (pos(), asked for only then), a tail row goes to yr scaled by its diagonal of S^-1 (dinv of a tail row) and clears yc
+template <int BT, class P>
+__device__ __forceinline__ void dinv_tail_entry(double *xs, double *yr, double *yc, const double *dinv, int e, int s, P pos) {
+  if (e / BT < s) xs[pos()] *= dinv[e];
+  else { yr[e - s * BT] = dinv[e] * xs[e]; yc[e - s * BT] = 0.0; }
+}
+
 // what happens between the forward and the backward sweep: D^-1 on the rows before the dense tail, S^-1 on the tail
-// RE (iterate_body RE, with IX): `early` issues the first ring revolution of the backward sweep - under the D^-1 pass where
-// there is no dense tail, else once the product is through, under the yr + yc pass; the passes touch LDS only, so their
-// barriers are LDS-only barriers there (a __syncthreads() would wait for the ring it has just started).
-template <int BT, bool GX, bool IX = false, bool RE = false, class F = NoEarly>
+template <int BT, bool GX, bool IX = false>
 __device__ __forceinline__ void kkt_middle(const KernelArgs &a, const double *dinv, const mi_rsrc (&vdt)[BT], int act, double *xs,
-                                           int tid, int nthr, int wave, int lane, const IxWords &ix = IxWords{}, F early = F{}) {
+                                           int tid, int nthr, int wave, int lane, const IxWords &ix = IxWords{}) {
   static_assert(!IX || !GX, "the index words are LDS positions");
-  static_assert(!RE || IX, "an index load behind the early ring would wait for all of it");
   if (!a.dt.k) {
     const int tot = a.N * BT;
     if constexpr (IX) {
-      if constexpr (RE) early();
       const int t0 = ix_opaque(tid);
 #pragma unroll
       for (int j = 0; j < MI_IX_XLOC_TRIPS; j++) {
@@ -982,7 +952,7 @@ __device__ __forceinline__ void kkt_middle(const KernelArgs &a, const double *di
         for (int u = 0; u < U; u++) if (e0 + u * nthr < tot) xs[pos[u]] = v[u] * dv[u];
       }
     }
-    if constexpr (RE) lds_barrier(); else __syncthreads();
+    __syncthreads();
     return;
   }
   if constexpr (!GX) {
@@ -993,17 +963,11 @@ __device__ __forceinline__ void kkt_middle(const KernelArgs &a, const double *di
 #pragma unroll
       for (int j = 0; j < MI_IX_XLOC_TRIPS; j++) {
         const int e = t0 + j * nthr;
-        if (e < a.N * BT) {
-          if (e / BT < s) xs[ix_pos(ix.x[j / 2], j & 1)] *= dinv[e];
-          else { yr[e - s * BT] = dinv[e] * xs[e]; yc[e - s * BT] = 0.0; }
-        }
+        if (e < a.N * BT) dinv_tail_entry<BT>(xs, yr, yc, dinv, e, s, [&]() { return ix_pos(ix.x[j / 2], j & 1); });
       }
     } else {
-      for (int e = tid; e < a.N * BT; e += nthr) {
-        const int i = e / BT;
-        if (i < s) xs[(size_t)a.xloc[i] * BT + e % BT] *= dinv[e];
-        else { yr[e - s * BT] = dinv[e] * xs[e]; yc[e - s * BT] = 0.0; }          // dinv of a tail row = diagonal of S^-1
-      }
+      for (int e = tid; e < a.N * BT; e += nthr)
+        dinv_tail_entry<BT>(xs, yr, yc, dinv, e, s, [&]() { return (size_t)a.xloc[e / BT] * BT + e % BT; });
     }
     __syncthreads();
     if constexpr (BT == 1) {
@@ -1018,19 +982,15 @@ __device__ __forceinline__ void kkt_middle(const KernelArgs &a, const double *di
         dense_tail_apply<BT, BT, MI_DT_PF>(a.dt, vdt, 0, xs + (size_t)s * BT, yr, yc, wave, lane);
       }
     }
-    if constexpr (RE) early();
     for (int e = tid; e < k * BT; e += nthr) xs[(size_t)s * BT + e] = yr[e] + yc[e];
-    if constexpr (RE) lds_barrier(); else __syncthreads();
+    __syncthreads();
   }
 }
 
 // kkt_middle of the resident iterate with the resident head of S^-1 (one QP per tile, LDS vector, dense tail)
-// (RE: `early` goes into the product, which calls it when it has issued its last load - in front of its tail barriers)
-template <int R, int RL, int PF, bool IX = false, bool RE = false, class F = NoEarly>
+template <int R, int RL, int PF, bool IX = false>
 __device__ __forceinline__ void kkt_middle_rf(const KernelArgs &a, const double *dinv, const mi_rsrc &vdt, double *xs, double (&keep)[R],
-                                              double *hl, bool first, int tid, int nthr, int wave, int lane, const IxWords &ix = IxWords{},
-                                              F early = F{}) {
-  static_assert(!RE || IX, "an index load behind the early ring would wait for all of it");
+                                              double *hl, bool first, int tid, int nthr, int wave, int lane, const IxWords &ix = IxWords{}) {
   const int s = a.dt.s, k = a.dt.k;
   double *yr = xs + (size_t)a.xs_len, *yc = yr + (size_t)k;
   if constexpr (IX) {       // (positions from registers, D^-1 from LDS)
@@ -1038,25 +998,19 @@ __device__ __forceinline__ void kkt_middle_rf(const KernelArgs &a, const double 
 #pragma unroll
     for (int j = 0; j < MI_IX_XLOC_TRIPS; j++) {
       const int e = t0 + j * nthr;
-      if (e < a.N) {
-        if (e < s) xs[ix_pos(ix.x[j / 2], j & 1)] *= dinv[e];
-        else { yr[e - s] = dinv[e] * xs[e]; yc[e - s] = 0.0; }
-      }
+      if (e < a.N) dinv_tail_entry<1>(xs, yr, yc, dinv, e, s, [&]() { return ix_pos(ix.x[j / 2], j & 1); });
     }
   } else {
     // (the first row opaque: xloc + e and dinv + e are then formed here in every iteration - hoisted out of the iteration loop
     //  they hold two VGPR pairs through the sweeps and the product, which is what spilled at R = 24)
     int e0 = tid;
     asm volatile("" : "+v"(e0));
-    for (int e = e0; e < a.N; e += nthr) {
-      if (e < s) xs[(size_t)a.xloc[e]] *= dinv[e];
-      else { yr[e - s] = dinv[e] * xs[e]; yc[e - s] = 0.0; }
-    }
+    for (int e = e0; e < a.N; e += nthr) dinv_tail_entry<1>(xs, yr, yc, dinv, e, s, [&]() { return (size_t)a.xloc[e]; });
   }
   __syncthreads();
-  dense_tail_apply_rf<R, RL, PF>(a.dt, vdt, xs + (size_t)s, yr, yc, keep, hl, first, wave, lane, early);
+  dense_tail_apply_rf<R, RL, PF>(a.dt, vdt, xs + (size_t)s, yr, yc, keep, hl, first, wave, lane);
   for (int e = tid; e < k; e += nthr) xs[(size_t)s + e] = yr[e] + yc[e];
-  if constexpr (RE) lds_barrier(); else __syncthreads();
+  __syncthreads();
 }
 
 // K solve on the LDS vector: fwd levels, D^-1, bwd levels (row E7)
@@ -1109,6 +1063,20 @@ __device__ __forceinline__ void kkt_solve_lds(const KernelArgs &a, const TilePtr
   run_tri<BT, PF, GX, 0, WIDE>(a.bwd, p.vbwd, xs, wave, lane);
 }
 
+// The vector step of one entry (rows E8-E10): the one source of its arithmetic for every form of iterate_body.
+//   x_step:  x+ = alpha * xt + (1 - alpha) * x
+//   zy_step: zt = z + rho^-1 * (nu - y), relaxed with alpha, projected onto [l, u]; dy = rho * (relaxed - projected)
+struct ZyStep { double zn, yn, dy; };
+__device__ __forceinline__ double x_step(double xt, double xp, double alpha) { return alpha * xt + (1.0 - alpha) * xp; }
+__device__ __forceinline__ ZyStep zy_step(double nu, double zp, double yv, double ri, double rv, double lo, double up, double alpha) {
+  double zt = zp - ri * yv;
+  zt += ri * nu;
+  const double zr = alpha * zt + (1.0 - alpha) * zp;
+  const double zn = fmin(fmax(zr + ri * yv, lo), up);
+  const double dy = rv * (zr - zn);
+  return {zn, yv + dy, dy};
+}
+
 // E6-E10 for iterations (iter_begin, iter_end] of one tile.  Lean on purpose: the
 // residual / termination / rho logic lives in check_kernel, so this kernel needs
 // little beyond the register ring of the step streams.
@@ -1125,16 +1093,10 @@ __device__ __forceinline__ void kkt_solve_lds(const KernelArgs &a, const TilePtr
 // them (IxWords); the D^-1 pass and the vector step then issue no global load at all - what is left between the sweeps is
 // the stores of the last iteration.  For handles whose trip counts fit the caps (host_core.hpp index_words_fit); every other
 // handle, and MI_OSQP_INDEX_LOADS=1, keeps the loading form.  Compile-time like RS / RF: the loading form is untouched.
-// RE (rings started early, with IX, one QP per tile; MI_OSQP_RING_EARLY=1): every sweep's first ring revolution is issued
-// under the LDS pass in front of it instead of by the sweep itself, whose 16 waves would wait for it together - the forward
-// sweep's before the vector step of the iteration before (before the E6 pass for the first), the backward sweep's when the
-// product has issued its last load.  The ring arrives filled (run_stream PRE); the barriers behind the passes that cover it
-// are LDS-only barriers.  The same loads in all, only earlier (the last iteration starts no ring: no sweep follows it).
-template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false, int RF = 0, bool IX = false, bool RE = false>
+template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false, int RF = 0, bool IX = false>
 __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, int n_iter) {
   static_assert(!RS || (!GX && !WIDE), "the resident state goes with the LDS solve vector");
   static_assert(!IX || RS, "the index words in registers go with the resident state");
-  static_assert(!RE || (IX && BT == 1), "the early rings go with the index words in registers of a tile of one QP");
   static_assert(!RF || (RS && BT == 1 && NT == 1024), "the resident head goes with the resident state of a 16-wave tile of one QP");
   // multi-workgroup mode (global vector, one QP): the grid is ONE tile; thread / wave numbers run over the grid and the
   // barriers between phases are grid barriers
@@ -1184,10 +1146,6 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
       ix.p[j] = wx | (wz << 16);
     }
   }
-  constexpr int PFS = MI_PFV_NT(NT, GX);      // ring depth of the sweeps
-  Ring<BT, PFS> rfw, rbw;                      // RE: the rings of the forward / backward sweep, started ahead of them
-  (void)rfw; (void)rbw;
-  if constexpr (RE) tri_start<BT, PFS>(a.fwd, p.vfwd, wave, lane, rfw);
   // ---- E6 of the first iteration: rhs into the permuted solve vector
   for (int e = tid; e < N * BT; e += nthr) {
     const int i = e / BT;
@@ -1217,14 +1175,7 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
     const bool do_info = a.info_at_end && iter == n_iter;     // delta_x / delta_y are only needed by check_kernel
     const bool last = iter == n_iter;                         // (resident state: x, z, y go back to global memory)
     // ---- E7
-    if constexpr (RE) {                                       // the same with both rings started ahead of their sweeps
-      auto early = [&]() { tri_start<BT, PFS>(a.bwd, p.vbwd, wave, lane, rbw); };
-      tri_finish<BT, PFS>(a.fwd, p.vfwd, xs, wave, lane, rfw);
-      if constexpr (RF) kkt_middle_rf<rf_reg_steps(RF), MI_RF_RL, rf_ring_steps(RF), true, true>(a, DI, p.vdt[0], xs, keep, hl, iter == 1, tid, nthr, wave, lane, ix, early);
-      else kkt_middle<BT, false, true, true>(a, DI, p.vdt, p.act, xs, tid, nthr, wave, lane, ix, early);
-      tri_finish<BT, PFS>(a.bwd, p.vbwd, xs, wave, lane, rbw);
-      if (!last) tri_start<BT, PFS>(a.fwd, p.vfwd, wave, lane, rfw);      // under the vector step below
-    } else if constexpr (RS) {                                // kkt_solve_lds with D^-1 from LDS
+    if constexpr (RS) {                                      // kkt_solve_lds with D^-1 from LDS
       run_tri<BT, MI_PFV_NT(NT, GX), GX, 0, WIDE>(a.fwd, p.vfwd, xs, wave, lane);
       if constexpr (RF) kkt_middle_rf<rf_reg_steps(RF), MI_RF_RL, rf_ring_steps(RF), IX>(a, DI, p.vdt[0], xs, keep, hl, iter == 1, tid, nthr, wave, lane, ix);
       else kkt_middle<BT, GX, IX>(a, DI, p.vdt, p.act, xs, tid, nthr, wave, lane, ix);
@@ -1242,7 +1193,7 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
         if (e < n * BT) {
           const uint32_t pos = ix_pos(ix.p[j], false);
           const double xt = xs[pos], xp = X[e], qv = Q[e];
-          double xn = alpha * xt + (1.0 - alpha) * xp;
+          double xn = x_step(xt, xp, alpha);
           if (!done) {
             X[e] = xn;
             if (last) p.x[e] = xn;
@@ -1257,16 +1208,12 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
         if (e < m * BT) {
           const uint32_t pos = ix_pos(ix.p[j], true);
           const double nu = xs[pos], zp = Z[e], yv = Y[e], ri = RI[e], rv = RV[e], lo = LO[e], up = UP[e];
-          double zt = zp - ri * yv;
-          zt += ri * nu;
-          const double zr = alpha * zt + (1.0 - alpha) * zp;
-          double zn = fmin(fmax(zr + ri * yv, lo), up);
-          const double dyv = rv * (zr - zn);
-          double yn = yv + dyv;
+          const ZyStep st = zy_step(nu, zp, yv, ri, rv, lo, up, alpha);
+          double zn = st.zn, yn = st.yn;
           if (!done) {
             Z[e] = zn; Y[e] = yn;
             if (last) { p.z[e] = zn; p.y[e] = yn; }
-            if (do_info) p.dy[e] = dyv;
+            if (do_info) p.dy[e] = st.dy;
           } else { zn = zp; yn = yv; }
           xs[pos] = zn - ri * yn;
         }
@@ -1298,7 +1245,7 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
       for (int u = 0; u < U; u++) {
         const int e = e0 + u * nthr;
         if (e < n * BT) {
-          double xn = alpha * xt[u] + (1.0 - alpha) * xp[u];
+          double xn = x_step(xt[u], xp[u], alpha);
           if (!done) {
             X[e] = xn;
             if constexpr (RS) { if (last) p.x[e] = xn; }
@@ -1326,31 +1273,25 @@ __device__ __forceinline__ void iterate_body(const KernelArgs &a, double *smem, 
       for (int u = 0; u < U; u++) {
         const int e = e0 + u * nthr;
         if (e < m * BT) {
-          double zt = zp[u] - ri[u] * yv[u];
-          zt += ri[u] * nu[u];
-          const double zr = alpha * zt + (1.0 - alpha) * zp[u];
-          double zn = fmin(fmax(zr + ri[u] * yv[u], lo[u]), up[u]);
-          const double dyv = rv[u] * (zr - zn);
-          double yn = yv[u] + dyv;
+          const ZyStep st = zy_step(nu[u], zp[u], yv[u], ri[u], rv[u], lo[u], up[u], alpha);
+          double zn = st.zn, yn = st.yn;
           if (!done) {
             Z[e] = zn; Y[e] = yn;
             if constexpr (RS) { if (last) { p.z[e] = zn; p.y[e] = yn; } }
-            if (do_info) p.dy[e] = dyv;
+            if (do_info) p.dy[e] = st.dy;
           } else { zn = zp[u]; yn = yv[u]; }
           if (df) { st_sc1(xs + pos[u], zn - ri[u] * yn); df_arm_fwd(xs, (uint32_t)pos[u], fl[u], xl[u], sh); }
           else xs[pos[u]] = zn - ri[u] * yn;
         }
       }
     }
-    if constexpr (GX) wg_or_grid_barrier(mw);
-    else if constexpr (RE) lds_barrier();       // (the next right-hand side is LDS traffic; the forward ring stays in flight)
-    else __syncthreads();
+    if constexpr (GX) wg_or_grid_barrier(mw); else __syncthreads();
   }
 }
-template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false, int RF = 0, bool IX = false, bool RE = false>
+template <int BT, int NT, bool GX, bool WIDE = false, bool RS = false, int RF = 0, bool IX = false>
 __global__ __launch_bounds__(NT) void iterate_kernel(KernelArgs a) {
   extern __shared__ double smem[];
-  iterate_body<BT, NT, GX, WIDE, RS, RF, IX, RE>(a, smem, a.iter_end - a.iter_begin);
+  iterate_body<BT, NT, GX, WIDE, RS, RF, IX>(a, smem, a.iter_end - a.iter_begin);
 }
 
 // E11-E14 after a segment of n_iter iterations: residuals, termination and infeasibility tests, rho estimate / update
@@ -4317,7 +4258,7 @@ hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, s
   if (a.df && debug_drop_group("iterate") && tiles > 1) tiles--;       // fault injection: a workgroup of the grid never shows up
 #endif
   if (a.rs_off) {       // resident state (lds covers it): the 16-wave tiles that have their CU to themselves
-    if (a.xs_global || a.wide || a.df || threads <= 512 || threads > 1024 || BT > 2 || (a.re && (!a.ix || BT != 1))) return hipErrorInvalidValue;
+    if (a.xs_global || a.wide || a.df || threads <= 512 || threads > 1024 || BT > 2) return hipErrorInvalidValue;
     auto go = [&](auto kern) -> hipError_t {
       hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
       if (e != hipSuccess) return e;
@@ -4326,20 +4267,16 @@ hipError_t launch_iterate(const KernelArgs &a, int BT, int tiles, int threads, s
     };
     if (a.rf_off) {     // resident head of S^-1 (lds covers its LDS part)
       if (BT != 1 || !a.dt.k || threads != 1024) return hipErrorInvalidValue;
-      // (early rings: the deep ring only.  The long head has no registers for a second live ring - 128 VGPRs, 16 of them
-      //  spilled, 52 B of scratch, profiles/r12/code_object.txt - so its launches keep filling their rings in the sweeps.)
-      if (a.re && a.rf_form == RF_FORM_DEEP_RING) return go(&iterate_kernel<1, 1024, false, false, true, RF_FORM_DEEP_RING, true, true>);
       if (a.rf_form == RF_FORM_LONG_HEAD)
         return a.ix ? go(&iterate_kernel<1, 1024, false, false, true, RF_FORM_LONG_HEAD, true>) : go(&iterate_kernel<1, 1024, false, false, true, RF_FORM_LONG_HEAD>);
       if (a.rf_form == RF_FORM_DEEP_RING)
         return a.ix ? go(&iterate_kernel<1, 1024, false, false, true, RF_FORM_DEEP_RING, true>) : go(&iterate_kernel<1, 1024, false, false, true, RF_FORM_DEEP_RING>);
       return hipErrorInvalidValue;
     }
-    if (a.re) return go(&iterate_kernel<1, 1024, false, false, true, 0, true, true>);
     if (a.ix) return BT == 1 ? go(&iterate_kernel<1, 1024, false, false, true, 0, true>) : go(&iterate_kernel<2, 1024, false, false, true, 0, true>);
     return BT == 1 ? go(&iterate_kernel<1, 1024, false, false, true>) : go(&iterate_kernel<2, 1024, false, false, true>);
   }
-  if (a.rf_off || a.ix || a.re) return hipErrorInvalidValue;
+  if (a.rf_off || a.ix) return hipErrorInvalidValue;
   MI_DISPATCH(iterate_kernel, a);
 }
 hipError_t launch_check(const KernelArgs &a, int BT, int tiles, int threads, size_t lds, hipStream_t st) {

@@ -286,7 +286,6 @@ struct mi_osqp_batch {
   int rs_off = 0;                             // KernelArgs::rs_off
   size_t lds_factor = 0;                      // LDS part of the resident head of S^-1, behind the resident state (iterate launches only)
   int rf_off = 0, rf_steps = 0;               // KernelArgs::rf_off; steps per wave the head keeps (registers + LDS; of the long form unless the deep ring is forced), 0 = streamed
-  int re = 0;                                 // KernelArgs::re: they also start the sweeps' rings early (MI_OSQP_RING_EARLY)
   int ix = 0;                                 // KernelArgs::ix: the iterate launches keep their index words in registers (index_words_fit, MI_OSQP_INDEX_LOADS)
   int64_t rf_launches[3] = {0, 0, 0};         // iterate launches since setup by form (RF_FORM_*; chunk iterates count one each)
   std::vector<QPNumeric> qp;
@@ -491,7 +490,7 @@ static KernelArgs make_args(mi_osqp_batch *h) {
   a.x_out = h->x_out.p; a.y_out = h->y_out.p;
   a.cert_out = h->cert_out.p; a.cert_stride = (int)std::max<int64_t>(std::max<int64_t>(a.n, a.m), 1);
   a.xs_global = h->global_xs ? h->xs_global.p : nullptr; a.xs_len = (*h->anp).xs_total; a.wide = (*h->anp).wide ? 1 : 0;
-  a.rs_off = h->rs_off; a.rf_off = h->rf_off; a.ix = h->ix; a.re = h->re;
+  a.rs_off = h->rs_off; a.rf_off = h->rf_off; a.ix = h->ix;
   a.rf_form = iterate_form(h->ntiles, h->rf_off != 0, h->tune);      // (solve_impl sets it per launch from the tiles still iterating)
   a.mw_groups = h->mw_groups; a.mw_bar = h->mw_bar.p; a.mw_scratch = h->mw_scratch.p;
   a.df = (*h->anp).df ? 1 : 0; a.df_shadow = (unsigned)(*h->anp).Next; a.rflag = h->rflag.p;
@@ -1005,10 +1004,6 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
   // Index words of the resident iterate (iterate_body IX): every thread keeps its entries of pinv and xloc in registers across
   // a launch where their number fits the caps, so that the passes between the sweeps load nothing.
   h->ix = !h->tune.index_loads && index_words_fit(h->rs_off != 0, !h->global_xs, BT, h->threads, n, m) ? 1 : 0;
-  // Early rings (iterate_body RE: the sweeps' rings started under the LDS passes in front of them) on top of that, for tiles of
-  // one QP whose every launch has the registers for it: no resident head, or the deep ring forced (MI_OSQP_RF_FORM=1) - the
-  // long head spills with a second live ring (profiles/r12/code_object.txt).
-  h->re = h->ix && BT == 1 && h->tune.ring_early && (!h->rf_off || h->tune.rf_form == kIterDeepRing) ? 1 : 0;
   // ---- device arrays
   size_t T = (size_t)h->ntiles * BT;
   if ((rc = h->fwd.upload(an.fwd)) || (rc = h->bwd.upload(an.bwd)) || (rc = h->chk.upload(an.chk))) return rc;
@@ -1227,7 +1222,7 @@ static int batch_setup_impl(mi_osqp_batch *h, int64_t B, int64_t n, int64_t m, c
   s.solve_groups = h->mw_groups; s.solve_group_threads = h->mw_groups > 0 ? h->mw_threads : 0;
   s.resident_state = h->rs_off ? 1 : 0; s.lds_bytes_iterate = (int64_t)h->lds_iter;
   s.resident_factor_steps = h->rf_steps; s.lds_bytes_factor = (int64_t)h->lds_factor;
-  s.ring_early = h->re; s.resident_index_words = h->ix;
+  s.resident_index_words = h->ix;
   dense_tail_deal_stats(an.dt, s);
   if (getenv("MI_OSQP_DEBUG_TIMING"))
     fprintf(stderr, "[mi_osqp] setup B=%d N=%d: analysis+alloc %.1f ms (analysis %.1f), numeric %.1f ms, upload %.1f ms, rest %.1f ms\n", (int)B, an.N,

@@ -1,14 +1,12 @@
-"""GPU (-m gpu): the index words of the resident iterate in registers and its rings started early (DESIGN.md section 3,
-"Index words in registers").
+"""GPU (-m gpu): the index words of the resident iterate in registers ("Index words in registers").
 
 A tile that keeps its ADMM state in LDS walks the same entries of pinv and xloc in every iteration; where a thread's trips
 fit the caps (host_core.hpp index_words_fit) it loads them once per launch and keeps them, so that the D^-1 pass and the
 vector step issue no global load.  MI_OSQP_INDEX_LOADS=1 (read at setup) keeps the form that loads them in every iteration.
-On top of the registers, MI_OSQP_RING_EARLY=1 (read at setup, one QP per tile) issues every sweep's first ring revolution
-under the LDS pass in front of the sweep.  Same expressions on the same operands in the same order, so every case builds the
-solver once per form - loads, registers, registers + early rings - and asks for:
+The vector step has one source for both forms (kernels.hip x_step / zy_step), so every case builds the solver once per form
+- loads, registers, registers with the deep ring of the resident head forced (MI_OSQP_RF_FORM=1) - and asks for:
   * the three forms agree BIT FOR BIT in x, y, the iteration counts, the exit codes and the rho updates;
-  * the register form and the early-ring form meet the oracle by the project's usual criteria (tests/test_gpu_parity.py):
+  * the register form and the deep-ring form meet the oracle by the project's usual criteria (tests/test_gpu_parity.py):
     same exit code, same iteration count, x within 1e-6 (identical outputs: one comparison serves both)."""
 import numpy as np
 import pytest
@@ -22,10 +20,9 @@ TOL_X = 1e-6
 ST2EXIT = {1: 0, -3: 1, -4: 2, 2: 3, 3: 4, 4: 5, -2: 6, -7: 9, -10: 10}
 SMALL = dict(n=96, mg=64, nnz_per_row=6)
 MID = dict(n=256, mg=128, nnz_per_row=6)
-# (early rings go with the deep ring of the resident head: the long head has no registers for them - DESIGN.md section 3;
-#  the two forms of the head are bitwise equal, tests/test_gpu_head_forms.py)
-FORMS = {"loads": {"MI_OSQP_INDEX_LOADS": "1"}, "registers": {}, "early": {"MI_OSQP_RING_EARLY": "1", "MI_OSQP_RF_FORM": "1"}}
-SWITCHES = ("MI_OSQP_INDEX_LOADS", "MI_OSQP_RING_EARLY", "MI_OSQP_STREAM_FACTOR", "MI_OSQP_STREAM_STATE", "MI_OSQP_DENSE_TAIL", "MI_OSQP_TILE", "MI_OSQP_RF_FORM")
+# (the two forms of the head are bitwise equal, tests/test_gpu_head_forms.py)
+FORMS = {"loads": {"MI_OSQP_INDEX_LOADS": "1"}, "registers": {}, "deep": {"MI_OSQP_RF_FORM": "1"}}
+SWITCHES = ("MI_OSQP_INDEX_LOADS", "MI_OSQP_STREAM_FACTOR", "MI_OSQP_STREAM_STATE", "MI_OSQP_DENSE_TAIL", "MI_OSQP_TILE", "MI_OSQP_RF_FORM")
 
 
 def _solver(pr, **kw):
@@ -35,29 +32,28 @@ def _solver(pr, **kw):
 def _both_forms(monkeypatch, pr, run, env=None, expect_registers=True, **kw):
     """run(solver) -> list of (info, x, y), once per form; returns (the register form's list, its stats) after the bitwise
     comparison of all three forms.  expect_registers = False: a handle whose index words do not fit - every run takes the
-    loading form, without early rings."""
+    loading form."""
     out, stats = {}, {}
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
     for k, v in (env or {}).items():
         monkeypatch.setenv(k, v)
     for form in FORMS:
-        for k in ("MI_OSQP_INDEX_LOADS", "MI_OSQP_RING_EARLY", "MI_OSQP_RF_FORM"):
+        for k in ("MI_OSQP_INDEX_LOADS", "MI_OSQP_RF_FORM"):
             monkeypatch.delenv(k, raising=False)
         for k, v in {**(env or {}), **FORMS[form]}.items():
             monkeypatch.setenv(k, v)
         s = _solver(pr, **kw)
         st = stats[form] = s.stats()
         print(form, {k: st[k] for k in ("tile", "threads_per_block", "n", "m", "dense_tail_rows", "resident_state",
-                                        "resident_factor_steps", "resident_index_words", "ring_early")})
+                                        "resident_factor_steps", "resident_index_words")})
         fit = M.debug_index_words_fit(st["n"], st["m"], tile=st["tile"], threads=st["threads_per_block"],
                                       resident_state=st["resident_state"] == 1)[0]
         assert st["resident_index_words"] == (1 if form != "loads" and fit else 0), (form, fit, st)
-        assert st["ring_early"] == (1 if form == "early" and fit and st["tile"] == 1 else 0), (form, fit, st)
         if form != "loads":
             assert st["resident_state"] == 1 and fit == expect_registers, (fit, st)
         out[form] = run(s)
-    for form in ("registers", "early"):
+    for form in ("registers", "deep"):
         assert len(out["loads"]) == len(out[form])
         for k, ((i0, x0, y0), (i1, x1, y1)) in enumerate(zip(out["loads"], out[form])):
             assert [i.iter for i in i0] == [i.iter for i in i1], (form, k)
@@ -209,17 +205,3 @@ def test_resident_state_whose_trips_exceed_the_cap_keeps_loading(monkeypatch):
     ((info, x, y),), st = _both_forms(monkeypatch, pr, lambda s: [_solve(s)], expect_registers=False)
     assert st["resident_state"] == 1 and st["resident_index_words"] == 0 and st["m"] > st["threads_per_block"]
     _all_meet_oracle(pr, B, info, x)
-
-
-def test_early_rings_are_not_taken_beside_the_long_head(monkeypatch):
-    """MI_OSQP_RING_EARLY=1 alone on a handle with a resident head: its launches run the long head, which has no registers
-    for a second live ring, so the handle reports ring_early = 0; with the deep ring forced it reports 1."""
-    pr = PR.random_box_qp(2)
-    for k in SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("MI_OSQP_RING_EARLY", "1")
-    st = _solver(pr).stats()
-    assert st["resident_factor_steps"] > 0 and st["resident_index_words"] == 1 and st["ring_early"] == 0, st
-    monkeypatch.setenv("MI_OSQP_RF_FORM", "1")
-    st = _solver(pr).stats()
-    assert st["resident_factor_steps"] > 0 and st["resident_index_words"] == 1 and st["ring_early"] == 1, st
