@@ -550,6 +550,29 @@ int mi_gomp_scene_create_cuboids(mi_gomp_scene **out, mi_osqp_batch *h, int64_t 
                                  const mi_gomp_chain *chain, int64_t n_balls, const mi_gomp_ball *balls,
                                  int64_t n_lines, const mi_gomp_line *lines, int64_t n_capsules, const mi_gomp_capsule *capsules,
                                  int64_t n_cuboids, const mi_gomp_cuboid *cuboids, const double *con_lo, const double *con_hi);
+/* A self-collision pair: balls a and b of the scene (indices into `balls`) must stay apart; host twin: BallPair in
+ * include/mi_osqp/gomp.hpp.  At waypoint w, with p_a, p_b the two centres, J_a, J_b the 3 x D position Jacobians and r_a, r_b
+ * the radii, in this order of operations:
+ *   v = p_a - p_b;  dist = sqrt(v_x^2 + v_y^2 + v_z^2);
+ *   dist > 1e-12:  n = v / dist;  otherwise n = (0, 0, 1);
+ *   reach = r_a + r_b;  clearance s = dist - reach;
+ *   g_j = (n_x Ja[x][j] + n_y Ja[y][j] + n_z Ja[z][j]) - (n_x Jb[x][j] + n_y Jb[y][j] + n_z Jb[z][j]).
+ * The row of (pair, waypoint) holds g_j in the columns of q_w, whether it is active or not.  It is active when s < margin:
+ * l = (reach - dist) + sum_j g_j q_w[j], u = +1e30; otherwise l = -1e30, u = +1e30.  A trajectory is accepted only if
+ * s >= -1e-3 at every (pair, waypoint).  Both radii are part of the bound, as for capsules; nothing is added on top. */
+typedef struct { int32_t a, b; double margin; } mi_gomp_pair;   /* 16 bytes */
+/* mi_gomp_scene_create_cuboids with ball pairs besides.  The pair rows follow the block of the last ball and waypoint,
+ * pair-major: the row of (pair k, waypoint w) is the first 3-D row + the rows of all ball blocks + k waypoints + w, so the
+ * constraint matrix must hold waypoints * n_pairs rows more.  n_pairs == 0: exactly mi_gomp_scene_create_cuboids.  Refused on
+ * the host, before any device call, with *out = NULL, the handle usable and the reason in mi_osqp_last_error() naming the
+ * pair's index: n_pairs > 0 without pairs (MI_OSQP_ERR_NULL); n_pairs < 0, a margin that is not finite or negative, a or b
+ * outside 0 .. n_balls - 1, a == b, two MI_GOMP_MODEL_DH_CHAIN balls of one frame (their distance is constant and the row all
+ * zeros), a constraint matrix that does not hold the rows (MI_OSQP_ERR_INVALID_DATA). */
+int mi_gomp_scene_create_pairs(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints,
+                               const mi_gomp_chain *chain, int64_t n_balls, const mi_gomp_ball *balls,
+                               int64_t n_lines, const mi_gomp_line *lines, int64_t n_capsules, const mi_gomp_capsule *capsules,
+                               int64_t n_cuboids, const mi_gomp_cuboid *cuboids, int64_t n_pairs, const mi_gomp_pair *pairs,
+                               const double *con_lo, const double *con_hi);
 void mi_gomp_scene_free(mi_gomp_scene *sc);          /* before mi_osqp_batch_free of its handle; one scene per handle */
 /* While a scene exists, mi_osqp_batch_reinit_some / _update_A_bounds_some of its handle also keep the QPs' raw constraint
  * data (as ConstraintBuilder::build() produced it) in the scene, so nothing extra is needed when a trajectory enters the

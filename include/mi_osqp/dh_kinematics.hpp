@@ -10,11 +10,13 @@
 //   miosqp_ref::dhBall(chain, frame, c, radius, grip)   a RobotBall whose callbacks call it and which names the device model,
 //                                                       so ContinuousGOMPSolver (device_assembly, dh_chain = chain) can
 //                                                       re-linearise on the GPU
+//   miosqp_ref::dhSelfPairs(balls, gap, margin)         the self-collision pairs of such balls: frames at least `gap` apart
 #pragma once
 
 #include <array>
 #include <cmath>
 #include <tuple>
+#include <vector>
 
 #include "../mi_osqp.h"
 #include "gomp.hpp"
@@ -74,6 +76,21 @@ inline RobotBall dhBall(const mi_gomp_chain &chain, int frame, const std::array<
   RobotBall b(std::move(fk), std::move(jac), radius, is_gripper);
   b.withBuiltin(MI_GOMP_MODEL_DH_CHAIN, {(double)frame, c[0], c[1], c[2]});
   return b;
+}
+
+// The usual "skip adjacent links" rule of a self-collision model: every pair (i, j), i < j, of dhBall balls of `balls` whose
+// frames are at least `min_frame_gap` apart, in that order, with `margin`.  Balls of other models are left out.  (Two balls of
+// one frame keep their distance whatever the joints do: a gap below 1 is taken as 1.)
+inline std::vector<BallPair> dhSelfPairs(const std::vector<RobotBall> &balls, int min_frame_gap = 2, double margin = 0.0) {
+  std::vector<BallPair> pairs;
+  const int gap = min_frame_gap < 1 ? 1 : min_frame_gap;
+  for (size_t i = 0; i < balls.size(); ++i)
+    for (size_t j = i + 1; j < balls.size(); ++j) {
+      if (balls[i].builtin_model != MI_GOMP_MODEL_DH_CHAIN || balls[j].builtin_model != MI_GOMP_MODEL_DH_CHAIN) continue;
+      const int fi = (int)balls[i].builtin_param[0], fj = (int)balls[j].builtin_param[0];
+      if ((fi > fj ? fi - fj : fj - fi) >= gap) pairs.push_back(BallPair{i, j, margin});
+    }
+  return pairs;
 }
 
 }  // namespace miosqp_ref

@@ -8,6 +8,7 @@
 //   ConstraintBuilder<N>     [REF] src/constraints/constraint-builder.h:18-283
 //   CapsuleObstacle          not in the reference: a segment swept by a sphere (posts, pipes, other robots' links; a == b: a sphere)
 //   CuboidObstacle           not in the reference: an oriented box, optionally rounded (bin walls and floors, table tops, shelves)
+//   BallPair                 not in the reference: two balls of the robot that must stay apart (self-collision)
 //   GOMPSolver<N>            [REF] src/gomp-solver.h:13-201
 //
 // Same names, argument meaning, row layout and control flow as the reference (the known-answer
@@ -276,27 +277,65 @@ inline bool cuboidsClear(const std::vector<CuboidObstacle> &cuboids, const Point
   return res;
 }
 
+// ------------------------------------------------------------- ball pairs: self-collision (not in the reference)
+// Balls a and b of the planner's ball list must keep |p_a - p_b| - (r_a + r_b) >= 0 (mi_gomp_pair is its device twin,
+// include/mi_osqp.h has the formulas).  The row of a (pair, waypoint) is the linearisation of that clearance in the joints,
+// n' (J_a - J_b) with n the unit vector from b to a, and becomes active `margin` away from contact.
+struct BallPair {
+  size_t a, b;
+  double margin = 0.0;
+  bool operator==(const BallPair &o) const { return a == o.a && b == o.b && margin == o.margin; }
+};
+// |p_a - p_b| - (r_a + r_b) of a pair; xyz_w[3 i .. 3 i + 2]: the centre of ball i at one waypoint
+inline double pairClearance(const BallPair &pr, const std::vector<double> &xyz_w, const std::vector<RobotBall> &balls) {
+  const double v0 = xyz_w[3 * pr.a] - xyz_w[3 * pr.b], v1 = xyz_w[3 * pr.a + 1] - xyz_w[3 * pr.b + 1], v2 = xyz_w[3 * pr.a + 2] - xyz_w[3 * pr.b + 2];
+  return std::sqrt(v0 * v0 + v1 * v1 + v2 * v2) - (balls[pr.a].radius + balls[pr.b].radius);
+}
+// the pair part of isSolutionOK at one waypoint (shared by the three drivers)
+inline bool pairsClear(const std::vector<BallPair> &pairs, const std::vector<double> &xyz_w, const std::vector<RobotBall> &balls) {
+  bool res = true;
+  for (const BallPair &pr : pairs) if (!(pairClearance(pr, xyz_w, balls) >= -ERROR)) res = false;
+  return res;
+}
+// pairsClear at every waypoint of a joint trajectory (positions in the first half of the vector)
+template <size_t N>
+bool pairsClearAlong(const std::vector<BallPair> &pairs, const std::vector<RobotBall> &balls, const QPVector &trajectory) {
+  if (pairs.empty()) return true;
+  bool res = true;
+  std::vector<double> xyz_w(3 * balls.size());
+  for (size_t w = 0; w < trajectory.size() / 2 / N; ++w) {
+    Vec<N> q;
+    for (size_t j = 0; j < N; ++j) q[j] = trajectory[w * N + j];
+    for (size_t i = 0; i < balls.size(); ++i) std::tie(xyz_w[3 * i], xyz_w[3 * i + 1], xyz_w[3 * i + 2]) = balls[i].fk(q.data());
+    if (!pairsClear(pairs, xyz_w, balls)) res = false;
+  }
+  return res;
+}
+
 // ------------------------------------------------------------- constraint-builder.h
 // Rows: (W-1)*D velocity<->position links, then per variable boxes (positions W*D, velocities
 // (W-1)*D, accelerations (W-2)*D), then D*W*(3 + (|obstacles| + |capsules| + |cuboids|)*|balls|) rows for the linearised
-// end-effector / obstacle constraints (allocated even when unused: bounds +-INF).
+// end-effector / obstacle constraints (allocated even when unused: bounds +-INF), then W*|pairs| rows more.  The populated
+// 3-D rows come first: the blocks of the (ball, waypoint) pairs, then the ball pairs' rows, pair-major.
 template <size_t N_DIM>
 class ConstraintBuilder {
   using OptPair = std::pair<std::optional<double>, std::optional<double>>;
 
  public:
   ConstraintBuilder(size_t waypoints, std::vector<RobotBall> m, std::vector<HorizontalLine> obstacles, std::vector<CapsuleObstacle> capsules = {},
-                    std::vector<CuboidObstacle> cuboids = {})
-      : W_(waypoints), balls_(std::move(m)), lines_(std::move(obstacles)), capsules_(std::move(capsules)), cuboids_(std::move(cuboids)) {
-    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size() + cuboids_.size())));
-    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size())); up_.reserve(lo_.capacity());
+                    std::vector<CuboidObstacle> cuboids = {}, std::vector<BallPair> pairs = {})
+      : W_(waypoints), balls_(std::move(m)), lines_(std::move(obstacles)), capsules_(std::move(capsules)), cuboids_(std::move(cuboids)),
+        pairs_(std::move(pairs)) {
+    for ([[maybe_unused]] const BallPair &pr : pairs_) assert(pr.a < balls_.size() && pr.b < balls_.size() && pr.a != pr.b && pr.margin >= 0.0);
+    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size() + cuboids_.size()) + pairs_.size()));
+    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size()) + W_ * pairs_.size()); up_.reserve(lo_.capacity());
     for (size_t t = 0; t + 1 < W_; ++t)                      // v_t - q_{t+1} + q_t = 0
       for (size_t j = 0; j < N_DIM; ++j) {
         lo_.push_back(-INF); up_.push_back(INF);
         put(lo_.size() - 1, {{nthVelocity(t) + j, 1.0}, {nthPos(t + 1) + j, -1.0}, {nthPos(t) + j, 1.0}}, {0.0, 0.0});
       }
     user_off_ = lo_.size();
-    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size()));
+    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size())) + W_ * pairs_.size();
     lo_.resize(user_off_ + extra, -INF);
     up_.resize(user_off_ + extra, INF);
   }
@@ -352,6 +391,8 @@ class ConstraintBuilder {
         for (const CuboidObstacle &cub : cuboids_) cuboidRow(row++, ball, cub, p, J, q, w);
       }
     }
+    for (const BallPair &pr : pairs_)                            // behind the block of the last ball, pair-major
+      for (size_t w = 0; w < W_; ++w) pairRow(row++, pr, trajectory, w);
     return *this;
   }
 
@@ -364,6 +405,11 @@ class ConstraintBuilder {
       for (size_t w = 0; w < W_; ++w) {
         if (ball.is_gripper) for (Axis axis : XYZ_AXES) axisRow(row++, ball, axis, J, w, -INF, INF);
         for (size_t k = 0; k < lines_.size() + capsules_.size() + cuboids_.size(); ++k) axisRow(row++, ball, Z, J, w, -INF, INF);
+      }
+    for (size_t k = 0; k < pairs_.size(); ++k)
+      for (size_t w = 0; w < W_; ++w, ++row) {
+        for (size_t j = 0; j < N_DIM; ++j) set(nthPos(w) + j, row, 0.0);
+        lo_[row] = -INF; up_[row] = INF;
       }
     return *this;
   }
@@ -392,6 +438,7 @@ class ConstraintBuilder {
   std::vector<HorizontalLine> lines_;
   std::vector<CapsuleObstacle> capsules_;
   std::vector<CuboidObstacle> cuboids_;
+  std::vector<BallPair> pairs_;
   // (col, row) -> value, last write wins ([REF] constraint-builder.h:129).  A write log that is sorted into CSC
   // order and de-duplicated on demand: the builder runs once per trajectory, segment and re-linearisation,
   // and a std::map made it the bottleneck of the batched driver.
@@ -496,6 +543,31 @@ class ConstraintBuilder {
     lo_[row] = sd - reach < cub.margin ? (reach - sd) + gq : -INF;
     up_[row] = INF;
   }
+  // n' J_a - n' J_b with n = (p_a - p_b) / |p_a - p_b| (+Z when the centres coincide), written whether the row is active or
+  // not; active within `margin` of contact: (r_a + r_b) - dist + (n' (J_a - J_b)) q <= (n' (J_a - J_b)) x
+  void pairRow(size_t row, const BallPair &pr, const QPVector &trajectory, size_t waypoint) {
+    const RobotBall &A = balls_[pr.a], &B = balls_[pr.b];
+    Vec<N_DIM> q;
+    for (size_t j = 0; j < N_DIM; ++j) q[j] = trajectory[waypoint * N_DIM + j];
+    const auto [ax, ay, az] = A.fk(q.data());
+    const auto [bx, by, bz] = B.fk(q.data());
+    const Point v{ax - bx, ay - by, az - bz};
+    const double dist = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), reach = A.radius + B.radius;
+    const bool far = dist > 1e-12;
+    const Point nrm{far ? v[0] / dist : 0.0, far ? v[1] / dist : 0.0, far ? v[2] / dist : 1.0};
+    std::array<double, 3 * N_DIM> Ja{}, Jb{};
+    A.jacobian(Ja.data(), q.data());
+    B.jacobian(Jb.data(), q.data());
+    double gq = 0.0;
+    for (size_t j = 0; j < N_DIM; ++j) {
+      const double g = (nrm[0] * Ja[0 * N_DIM + j] + nrm[1] * Ja[1 * N_DIM + j] + nrm[2] * Ja[2 * N_DIM + j]) -
+                       (nrm[0] * Jb[0 * N_DIM + j] + nrm[1] * Jb[1 * N_DIM + j] + nrm[2] * Jb[2 * N_DIM + j]);
+      set(nthPos(waypoint) + j, row, g);
+      gq += g * q[j];
+    }
+    lo_[row] = dist - reach < pr.margin ? (reach - dist) + gq : -INF;
+    up_[row] = INF;
+  }
 };
 
 // ------------------------------------------------------------------- gomp-solver.h
@@ -583,6 +655,8 @@ class GOMPSolver {
   std::vector<CapsuleObstacle> capsules;
   // Not in the reference either: cuboid obstacles (oriented boxes); set before run()
   std::vector<CuboidObstacle> cuboids;
+  // Self-collision: pairs of `mappers` balls that must stay apart (dhSelfPairs of dh_kinematics.hpp makes them); set before run()
+  std::vector<BallPair> pairs;
   // (tests) the acceptance test that ends the SQP loop
   bool acceptable(const QPVector &q_trajectory) const { return isSolutionOK(q_trajectory); }
 
@@ -611,7 +685,7 @@ class GOMPSolver {
   }
   ConstraintBuilder<N_DIM> jointSpaceRows(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
     assert(waypoints >= 4);
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -643,6 +717,7 @@ class GOMPSolver {
         if (!cuboidsClear(cuboids, p, ball)) res = false;
       }
     }
+    if (!pairsClearAlong<N_DIM>(pairs, mappers, q_trajectory)) res = false;
     return res;
   }
 };
@@ -772,6 +847,7 @@ class BatchGOMPSolver {
   bool reuse_solvers = true;      // keep the per-segment solvers across run() calls (see run())
   std::vector<CapsuleObstacle> capsules;      // capsule / sphere obstacles besides the lines; set before run()
   std::vector<CuboidObstacle> cuboids;        // cuboid obstacles (oriented boxes); set before run()
+  std::vector<BallPair> pairs;                // self-collision pairs of the balls; set before run()
   int solver_reuses = 0;          // how often a kept solver was re-initialised instead of a new one being built
   // where the wall time of the last run() went: building constraints, QP setup (analysis + upload + factorisation),
   // batched solves, feasibility checks + re-linearisation + update
@@ -805,7 +881,7 @@ class BatchGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -837,6 +913,7 @@ class BatchGOMPSolver {
         if (!cuboidsClear(cuboids, p, ball)) res = false;
       }
     }
+    if (!pairsClearAlong<N_DIM>(pairs, mappers, q_trajectory)) res = false;
     return res;
   }
 };
@@ -868,10 +945,11 @@ class ContinuousGOMPSolver {
     const size_t B = starts.size();
     assert(ends.size() == B && B > 0);
     starts_ = &starts; ends_ = &ends;
-    if (!(capsules == scene_capsules_ && cuboids == scene_cuboids_)) {   // the kept scenes hold the capsules and cuboids of the run that made them
+    if (!(capsules == scene_capsules_ && cuboids == scene_cuboids_ && pairs == scene_pairs_)) {   // the kept scenes hold the capsules, cuboids and pairs of the run that made them
       for (Stage &st : stages_) if (st.scene) { mi_gomp_scene_free(st.scene); st.scene = nullptr; }
       scene_capsules_ = capsules;
       scene_cuboids_ = cuboids;
+      scene_pairs_ = pairs;
     }
     traj_.clear(); traj_.resize(B);
     segments_run.assign(B, 0); qp_solves.assign(B, 0); qp_updates.assign(B, 0);
@@ -919,6 +997,8 @@ class ContinuousGOMPSolver {
   // Cuboid obstacles (oriented boxes, optionally rounded); set before run().  On the device path they go into the scene
   // (mi_gomp_scene_create_cuboids).
   std::vector<CuboidObstacle> cuboids;
+  // Self-collision pairs of the balls; set before run().  On the device path they go into the scene (mi_gomp_scene_create_pairs).
+  std::vector<BallPair> pairs;
   int pipeline_depth = 1;              // 2: a stage enqueues its next advance before it looks at the previous one's results
   int segments_per_advance = 4;        // a launch runs on until a QP of the stage finishes, at most that many segments
   // per stage: {waypoints, advances, seconds admitting, waiting for the device, processing finished QPs, idle}
@@ -962,6 +1042,7 @@ class ContinuousGOMPSolver {
   std::array<Stage, SEGMENTS> stages_;
   std::vector<CapsuleObstacle> scene_capsules_;
   std::vector<CuboidObstacle> scene_cuboids_;
+  std::vector<BallPair> scene_pairs_;
   const std::vector<Ctrl<N_DIM>> *starts_ = nullptr, *ends_ = nullptr;
   std::atomic<size_t> finished_{0};
   std::atomic<bool> failed_{false};
@@ -1080,7 +1161,12 @@ class ContinuousGOMPSolver {
       g.radius = c.radius; g.margin = c.margin;
       cubs.push_back(g);
     }
-    const int rc = !cubs.empty() ? mi_gomp_scene_create_cuboids(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+    std::vector<mi_gomp_pair> prs;
+    for (const BallPair &p : pairs) prs.push_back(mi_gomp_pair{(int32_t)p.a, (int32_t)p.b, p.margin});
+    const int rc = !prs.empty() ? mi_gomp_scene_create_pairs(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+                                                              (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(),
+                                                              (int64_t)cubs.size(), cubs.data(), (int64_t)prs.size(), prs.data(), lo, hi)
+                   : !cubs.empty() ? mi_gomp_scene_create_cuboids(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
                                                                 (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(),
                                                                 (int64_t)cubs.size(), cubs.data(), lo, hi)
                    : !caps.empty() ? mi_gomp_scene_create_world(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
@@ -1167,7 +1253,7 @@ class ContinuousGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -1199,6 +1285,7 @@ class ContinuousGOMPSolver {
         if (!cuboidsClear(cuboids, p, ball)) res = false;
       }
     }
+    if (!pairsClearAlong<N_DIM>(pairs, mappers, q_trajectory)) res = false;
     return res;
   }
 };

@@ -287,14 +287,18 @@ struct GompCapsuleDev { double a[3], e[3], ee, R, margin; };
 // a cuboid obstacle (mi_gomp_cuboid): the box |u_k . (x - o)| <= h_k swept by a sphere of radius R; u[3 k + i] = component i
 // of axis k in world coordinates, margin as for the capsule
 struct GompCuboidDev { double o[3], u[9], h[3], R, margin; };
+// a self-collision pair (mi_gomp_pair): balls a and b of the scene keep |p_a - p_b| - (r_a + r_b) >= 0; margin as for the capsule
+struct GompPairDev { int a, b; double margin; };
 struct GompArgs {
   int dims, W, n_balls, n_lines, n, m, nnzA, n_ids, row0, write_rows;
   int n_caps, n_cuboids;
+  int n_pairs, pair_row0;        // pair_row0: the first pair row = row0 + the rows of all (ball, waypoint) blocks
   const int *ids;                // the listed QPs
   const GompBallDev *balls;
   const GompLineDev *lines;
   const GompCapsuleDev *caps;    // [n_caps]: their rows follow the lines' in every (ball, waypoint) block
   const GompCuboidDev *cuboids;  // [n_cuboids]: their rows follow the capsules'
+  const GompPairDev *pairs;      // [n_pairs]: row pair_row0 + k W + w for (pair k, waypoint w), behind every ball's block
   double con_lo[3], con_hi[3];   // work-space box of the gripper balls (+-1e30 = none)
   const int *aidx;               // [3-D row][dims]: position of that row's entry in column nthPos(w) + j of A's value array
   const double *traj;            // [n_ids][n]: the trajectories to linearise around (row = position in the list)

@@ -3892,7 +3892,8 @@ hipError_t launch_ruiz(const RuizArgs &a, hipStream_t st) {
 // neighbouring waypoint), a dummy row otherwise - and the trajectory is accepted when every ball respects the box and is above
 // (below) the lines it collides with.  Every (ball, capsule) pair gets one row after the lines' (see the loop over g.caps) and
 // must keep a clearance of -1e-3 or more; every (ball, cuboid) pair one row after the capsules', by the same rule.  One
-// workgroup per trajectory, one thread per (ball, waypoint).
+// workgroup per trajectory, one thread per (ball, waypoint); behind those items one thread per (ball pair, waypoint): one row
+// each behind the block of the last ball, the same rule on the distance of the two centres.
 __device__ __forceinline__ void ur5e_point(const double *q, int frame, double *p, double *J /* 3 x 6 row-major */) {
   const double a[6] = {0.0, -0.425, -0.3922, 0.0, 0.0, 0.0}, d[6] = {0.1625, 0.0, 0.0, 0.1333, 0.0997, 0.0996};
   const double alpha[6] = {1.5707963267948966, 0.0, 0.0, 1.5707963267948966, -1.5707963267948966, 0.0};
@@ -4122,6 +4123,38 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
       g.l[(size_t)qp * g.m + row] = s < cb.margin ? (reach - sd) + gq : -MI_INFTY;
       g.u[(size_t)qp * g.m + row] = MI_INFTY;
     }
+  }
+  // ball pairs (BallPair of gomp.hpp, formulas at mi_gomp_pair): the items behind the (ball, waypoint) items, pair-major.  Both
+  // centres are in xyz already, so the verdict needs no kinematics; n is known before any Jacobian, so J_a is reduced to
+  // n' J_a before J_b is formed in the same array (one call site, not unrolled: never two Jacobians, one more copy of the
+  // kinematics).  The D numbers n' J_a wait in the row's own entries of A, which this lane alone writes and reads back.
+  for (int e = tid; e < g.n_pairs * W; e += blockDim.x) {
+    const int k = e / W, w = e % W;
+    const GompPairDev pr = g.pairs[k];
+    const double *xa = smem + ((size_t)pr.a * W + w) * 3, *xb = smem + ((size_t)pr.b * W + w) * 3;
+    const double v0 = xa[0] - xb[0], v1 = xa[1] - xb[1], v2 = xa[2] - xb[2];
+    const double dist = sqrt(v0 * v0 + v1 * v1 + v2 * v2), reach = g.balls[pr.a].radius + g.balls[pr.b].radius;
+    const double s = dist - reach;
+    if (!(s >= -1e-3)) ok = 0;
+    if (!wr) continue;
+    const bool far = dist > 1e-12;
+    const double n0 = far ? v0 / dist : 0.0, n1 = far ? v1 / dist : 0.0, n2 = far ? v2 / dist : 1.0;
+    const int row = g.pair_row0 + e;
+    const int *ai = g.aidx + (size_t)(row - g.row0) * D;
+    double *Aq = g.A + (size_t)qp * g.nnzA;
+    for (int j = 0; j < D; j++) q[j] = traj[(size_t)w * D + j];
+    double gq = 0.0;
+#pragma unroll 1
+    for (int side = 0; side < 2; side++) {
+      gomp_fk_jac(g.chain, g.balls[side ? pr.b : pr.a], D, q, p, J);
+      for (int j = 0; j < D; j++) {
+        const double t = n0 * J[0 * D + j] + n1 * J[1 * D + j] + n2 * J[2 * D + j];
+        if (side == 0) Aq[ai[j]] = t;
+        else { const double gj = Aq[ai[j]] - t; Aq[ai[j]] = gj; gq += gj * q[j]; }                // written for inactive rows too
+      }
+    }
+    g.l[(size_t)qp * g.m + row] = s < pr.margin ? (reach - dist) + gq : -MI_INFTY;
+    g.u[(size_t)qp * g.m + row] = MI_INFTY;
   }
   }
   if (tid == 0) g.ok[jq] = s_ok;

@@ -3812,12 +3812,13 @@ int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t
 // Besides the built-in models a scene may hold one DH chain (mi_gomp_chain) with balls fixed in its link frames.
 struct mi_gomp_scene {
   mi_osqp_batch *h = nullptr;
-  int dims = 0, W = 0, n_balls = 0, n_lines = 0, n_caps = 0, n_cuboids = 0, row0 = 0, n_rows3d = 0;
+  int dims = 0, W = 0, n_balls = 0, n_lines = 0, n_caps = 0, n_cuboids = 0, n_pairs = 0, pair_row0 = 0, row0 = 0, n_rows3d = 0;
   double con_lo[3] = {-1e30, -1e30, -1e30}, con_hi[3] = {1e30, 1e30, 1e30};
   DevBuf<GompBallDev> balls;
   DevBuf<GompLineDev> lines;
   DevBuf<GompCapsuleDev> caps;
   DevBuf<GompCuboidDev> cuboids;
+  DevBuf<GompPairDev> pairs;                  // their rows: pair_row0 + k W + w, behind every ball's block
   GompChainDev chain{};                       // the DH chain of the MI_GM_DH_CHAIN balls (n_joints 0: the scene has none)
   DevBuf<int> aidx;
   DevBuf<double> A, l, u;                     // QP-major raw rows as ConstraintBuilder::build() lays them out
@@ -3840,9 +3841,9 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
   if ((rc = ring_upload(h, sp, (size_t)nq * n * sizeof(double)))) return rc;
   hipStream_t st = h->stream;
   GompArgs g{};
-  g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n_caps = sc->n_caps; g.n_cuboids = sc->n_cuboids; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
+  g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n_caps = sc->n_caps; g.n_cuboids = sc->n_cuboids; g.n_pairs = sc->n_pairs; g.pair_row0 = sc->pair_row0; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
   g.row0 = sc->row0; g.write_rows = write_rows;
-  g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.caps = sc->caps.p; g.cuboids = sc->cuboids.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
+  g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.caps = sc->caps.p; g.cuboids = sc->cuboids.p; g.pairs = sc->pairs.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
   for (int k = 0; k < 3; k++) { g.con_lo[k] = sc->con_lo[k]; g.con_hi[k] = sc->con_hi[k]; }
   g.A = sc->A.p; g.l = sc->l.p; g.u = sc->u.p; g.ok = sc->h_ok;
   g.chain = sc->chain;
@@ -3854,12 +3855,13 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
 }
 
 // mi_gomp_scene_create (chain null: model 6 is refused as it always was), mi_gomp_scene_create_chain and
-// mi_gomp_scene_create_world (capsules besides) and mi_gomp_scene_create_cuboids (cuboids besides those).  Everything that
-// can be refused is refused here on the host, the checks that need no handle first.
+// mi_gomp_scene_create_world (capsules besides), mi_gomp_scene_create_cuboids (cuboids besides those) and
+// mi_gomp_scene_create_pairs (ball pairs besides those).  Everything that can be refused is refused here on the host, the
+// checks that need no handle first.
 static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain, bool chain_entry,
                              int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                              int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
-                             const double *con_lo, const double *con_hi) {
+                             int64_t n_pairs, const mi_gomp_pair *pairs, const double *con_lo, const double *con_hi) {
   if (!out) return MI_OSQP_ERR_NULL;
   *out = nullptr;
   if ((n_balls > 0 && !balls) || (n_lines > 0 && !lines)) return MI_OSQP_ERR_NULL;
@@ -3888,6 +3890,17 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
         const double dot = cb.axes[3 * i] * cb.axes[3 * j] + cb.axes[3 * i + 1] * cb.axes[3 * j + 1] + cb.axes[3 * i + 2] * cb.axes[3 * j + 2];
         if (!(std::fabs(dot - (i == j ? 1.0 : 0.0)) <= 1e-9)) { g_last_error = "cuboid " + std::to_string(c) + ": the axes are not orthonormal"; return MI_OSQP_ERR_INVALID_DATA; }
       }
+  }
+  if (n_pairs > 0 && !pairs) { g_last_error = "n_pairs > 0 and no pairs"; return MI_OSQP_ERR_NULL; }
+  if (n_pairs < 0) { g_last_error = "n_pairs is negative"; return MI_OSQP_ERR_INVALID_DATA; }
+  for (int64_t k = 0; k < n_pairs; k++) {
+    const mi_gomp_pair &pr = pairs[k];
+    if (!std::isfinite(pr.margin) || pr.margin < 0.0) { g_last_error = "pair " + std::to_string(k) + ": the margin must be finite and not negative"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (pr.a < 0 || pr.a >= n_balls || pr.b < 0 || pr.b >= n_balls) { g_last_error = "pair " + std::to_string(k) + ": a and b must be balls 0 .. n_balls - 1"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (pr.a == pr.b) { g_last_error = "pair " + std::to_string(k) + " joins a ball with itself"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (balls[pr.a].model == MI_GM_DH_CHAIN && balls[pr.b].model == MI_GM_DH_CHAIN && balls[pr.a].param[0] == balls[pr.b].param[0]) {
+      g_last_error = "pair " + std::to_string(k) + " joins two chain balls of one frame: their distance is constant"; return MI_OSQP_ERR_INVALID_DATA;
+    }
   }
   GompChainDev hc{};
   if (chain_entry) {
@@ -3927,28 +3940,37 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
     if ((balls[b].model <= MI_GM_UR5E_ELBOW && D != 6) || ((balls[b].model == MI_GM_YAW_2LINK || balls[b].model == MI_GM_TABLE) && D != 3)) return MI_OSQP_ERR_INVALID_DATA;
     rows3d += W * ((balls[b].is_gripper ? 3 : 0) + (int)n_lines + (int)n_capsules + (int)n_cuboids);
   }
+  const int pair_row0 = row0 + rows3d;                             // the pair rows: behind the block of the last ball, pair-major
+  rows3d += W * (int)n_pairs;
   if (row0 + rows3d > an.m) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene"; return MI_OSQP_ERR_INVALID_DATA; }
   DevGuard guard(h->device);
   mi_gomp_scene *sc = new (std::nothrow) mi_gomp_scene();
   if (!sc) return MI_OSQP_ERR_ALLOC;
   std::unique_ptr<mi_gomp_scene> own(sc);
-  sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->n_caps = (int)n_capsules; sc->n_cuboids = (int)n_cuboids; sc->row0 = row0; sc->n_rows3d = rows3d;
+  sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->n_caps = (int)n_capsules; sc->n_cuboids = (int)n_cuboids; sc->n_pairs = (int)n_pairs; sc->pair_row0 = pair_row0; sc->row0 = row0; sc->n_rows3d = rows3d;
   sc->chain = hc;
   for (int k = 0; k < 3; k++) { sc->con_lo[k] = con_lo ? con_lo[k] : -1e30; sc->con_hi[k] = con_hi ? con_hi[k] : 1e30; }
   // where the entries of the 3-D rows sit in A's value array: row r of waypoint w holds D entries in the columns of q_w
   std::vector<int> aidx((size_t)rows3d * D, -1);
   {
     int r = row0;
+    auto locate = [&](int w) {                                     // row r of waypoint w: its D entries, false when A lacks one
+      for (int j = 0; j < D; j++) {
+        const int col = w * D + j;
+        const int *lo = an.Ai.data() + an.Ap[col], *hi = an.Ai.data() + an.Ap[col + 1];
+        const int *it = std::lower_bound(lo, hi, r);
+        if (it == hi || *it != r) return false;
+        aidx[(size_t)(r - row0) * D + j] = (int)(it - an.Ai.data());
+      }
+      return true;
+    };
     for (int b = 0; b < (int)n_balls; b++)
       for (int w = 0; w < W; w++)
         for (int k = 0; k < (balls[b].is_gripper ? 3 : 0) + (int)n_lines + (int)n_capsules + (int)n_cuboids; k++, r++)
-          for (int j = 0; j < D; j++) {
-            const int col = w * D + j;
-            const int *lo = an.Ai.data() + an.Ap[col], *hi = an.Ai.data() + an.Ap[col + 1];
-            const int *it = std::lower_bound(lo, hi, r);
-            if (it == hi || *it != r) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene"; return MI_OSQP_ERR_INVALID_DATA; }
-            aidx[(size_t)(r - row0) * D + j] = (int)(it - an.Ai.data());
-          }
+          if (!locate(w)) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene"; return MI_OSQP_ERR_INVALID_DATA; }
+    for (int k = 0; k < (int)n_pairs; k++)
+      for (int w = 0; w < W; w++, r++)
+        if (!locate(w)) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene (pair " + std::to_string(k) + ")"; return MI_OSQP_ERR_INVALID_DATA; }
   }
   std::vector<GompBallDev> hb((size_t)n_balls);
   for (int b = 0; b < (int)n_balls; b++) { hb[b].model = balls[b].model; hb[b].is_gripper = balls[b].is_gripper; hb[b].radius = balls[b].radius; for (int k = 0; k < 12; k++) hb[b].param[k] = balls[b].param[k]; }
@@ -3974,8 +3996,10 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
     for (int k = 0; k < 9; k++) d.u[k] = cuboids[c].axes[k];
     d.R = cuboids[c].radius; d.margin = cuboids[c].margin;
   }
+  std::vector<GompPairDev> hpair((size_t)n_pairs);
+  for (int k = 0; k < (int)n_pairs; k++) { hpair[k].a = pairs[k].a; hpair[k].b = pairs[k].b; hpair[k].margin = pairs[k].margin; }
   int rc;
-  if ((rc = sc->balls.upload(hb)) || (rc = sc->lines.upload(hl)) || (n_capsules && (rc = sc->caps.upload(hcap))) || (n_cuboids && (rc = sc->cuboids.upload(hcub))) ||
+  if ((rc = sc->balls.upload(hb)) || (rc = sc->lines.upload(hl)) || (n_capsules && (rc = sc->caps.upload(hcap))) || (n_cuboids && (rc = sc->cuboids.upload(hcub))) || (n_pairs && (rc = sc->pairs.upload(hpair))) ||
       (rc = sc->aidx.upload(aidx)) ||
       (rc = sc->A.alloc((size_t)h->B * std::max(an.Ap[an.n], 1))) || (rc = sc->l.alloc((size_t)h->B * std::max(an.m, 1))) || (rc = sc->u.alloc((size_t)h->B * std::max(an.m, 1)))) return rc;
   HIPCHK(hostpool::alloc((void **)&sc->h_ok, (size_t)h->B * sizeof(int), &sc->h_ok_cap));
@@ -3990,22 +4014,29 @@ extern "C" {
 
 int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, int64_t n_balls, const mi_gomp_ball *balls,
                          int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_chain(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_world(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                int64_t n_capsules, const mi_gomp_capsule *capsules, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_cuboids(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                  int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                  int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
                                  const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids, 0, nullptr, con_lo, con_hi);
+}
+int mi_gomp_scene_create_pairs(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
+                               int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
+                               int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
+                               int64_t n_pairs, const mi_gomp_pair *pairs, const double *con_lo, const double *con_hi) {
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids,
+                           n_pairs, pairs, con_lo, con_hi);
 }
 
 void mi_gomp_scene_free(mi_gomp_scene *sc) {
