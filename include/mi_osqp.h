@@ -573,6 +573,35 @@ int mi_gomp_scene_create_pairs(mi_gomp_scene **out, mi_osqp_batch *h, int64_t di
                                int64_t n_lines, const mi_gomp_line *lines, int64_t n_capsules, const mi_gomp_capsule *capsules,
                                int64_t n_cuboids, const mi_gomp_cuboid *cuboids, int64_t n_pairs, const mi_gomp_pair *pairs,
                                const double *con_lo, const double *con_hi);
+/* A tilt limit: the unit vector `axis`, fixed in frame `frame` of the scene's mi_gomp_chain (1 <= frame <= n_joints), must stay
+ * within max_angle radians of the unit world vector `ref` ("keep the tool upright"); host twin: TiltLimit in
+ * include/mi_osqp/gomp.hpp.  At waypoint w, q = q_w, with R_k the rotation of frame k (R_0 = I) and z_j the third column of
+ * R_j, the axis of joint j, in this order of operations:
+ *   u_r = R_k[r][0] axis_0 + R_k[r][1] axis_1 + R_k[r][2] axis_2            (the axis in the world)
+ *   c   = u_x ref_x + u_y ref_y + u_z ref_z                                  (cosine of the tilt)
+ *   h_j = z_j x u;   g_j = h_jx ref_x + h_jy ref_y + h_jz ref_z   for j < k;   g_j = 0 for j >= k
+ * (a joint j < k rotates everything behind it about z_j, so du/dq_j = z_j x u: g is the exact gradient of c).  Three
+ * thresholds are taken once on the host, in fp64, when the scene is created:
+ *   cos_lim = cos(max_angle);  cos_act = cos(max(0, max_angle - margin));  cos_ok = cos(min(pi, max_angle + 1e-3)).
+ * The row of (tilt, waypoint) holds g_j in the columns of q_w, whether it is active or not.  It is active when c < cos_act,
+ * that is within `margin` radians of the cone: l = (cos_lim - c) + sum_j g_j q_w[j], u = +1e30, the linearisation of
+ * c(q) >= cos_lim around q_w; otherwise l = -1e30, u = +1e30.  A trajectory is accepted only if c >= cos_ok at every (tilt,
+ * waypoint): 1 mrad, the angular counterpart of the 1 mm of the other primitives.  The cosine form is smooth where the axis
+ * meets ref; an angle has no gradient there.  When u is parallel or antiparallel to ref the row is all zeros: parallel it is
+ * inactive; antiparallel it is active with l = cos_lim + 1 > 0, and that QP is primal infeasible. */
+typedef struct { int32_t frame; int32_t reserved; double axis[3]; double ref[3]; double max_angle; double margin; } mi_gomp_tilt;   /* 72 bytes */
+/* mi_gomp_scene_create_pairs with tilt limits besides.  The tilt rows follow the pair rows, tilt-major: the row of (tilt k,
+ * waypoint w) is the first 3-D row + the rows of all ball blocks + waypoints * n_pairs + k waypoints + w, so the constraint
+ * matrix must hold waypoints * n_tilts rows more.  n_tilts == 0: exactly mi_gomp_scene_create_pairs.  Refused on the host,
+ * before any device call, with *out = NULL, the handle usable and the reason in mi_osqp_last_error() naming the tilt's
+ * index: n_tilts > 0 without tilts, tilts without a chain (MI_OSQP_ERR_NULL); n_tilts < 0, a frame outside 1 .. n_joints, a
+ * field that is not finite, | |axis| - 1 | > 1e-9 and the same for ref, max_angle not in (0, pi), margin < 0, a constraint
+ * matrix that does not hold the rows (MI_OSQP_ERR_INVALID_DATA). */
+int mi_gomp_scene_create_tilts(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints,
+                               const mi_gomp_chain *chain, int64_t n_balls, const mi_gomp_ball *balls,
+                               int64_t n_lines, const mi_gomp_line *lines, int64_t n_capsules, const mi_gomp_capsule *capsules,
+                               int64_t n_cuboids, const mi_gomp_cuboid *cuboids, int64_t n_pairs, const mi_gomp_pair *pairs,
+                               int64_t n_tilts, const mi_gomp_tilt *tilts, const double *con_lo, const double *con_hi);
 void mi_gomp_scene_free(mi_gomp_scene *sc);          /* before mi_osqp_batch_free of its handle; one scene per handle */
 /* While a scene exists, mi_osqp_batch_reinit_some / _update_A_bounds_some of its handle also keep the QPs' raw constraint
  * data (as ConstraintBuilder::build() produced it) in the scene, so nothing extra is needed when a trajectory enters the

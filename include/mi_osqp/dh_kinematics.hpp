@@ -11,6 +11,9 @@
 //                                                       so ContinuousGOMPSolver (device_assembly, dh_chain = chain) can
 //                                                       re-linearise on the GPU
 //   miosqp_ref::dhSelfPairs(balls, gap, margin)         the self-collision pairs of such balls: frames at least `gap` apart
+//   mi_osqp::dh::axis(chain, q, frame, a, u, dU)        a unit vector a fixed in frame k: u = R_k a and (dU non-null) the 3 x n_joints
+//                                                       row-major derivative, column j = z_j x u for j < k, 0 for j >= k
+//   miosqp_ref::dhTilt(chain, frame, axis, ref, max_angle, margin)   a TiltLimit on such a vector, which names the frame for the device
 #pragma once
 
 #include <array>
@@ -56,6 +59,34 @@ inline void point(const mi_gomp_chain &ch, const double *q, int frame, const dou
   }
 }
 
+// point() without the origins: rotations only (the host twin of the device's dh_axis; formulas at mi_gomp_tilt)
+inline void axis(const mi_gomp_chain &ch, const double *q, int frame, const double a[3], double u[3], double *dU /* 3 x n row-major, or null */) {
+  const int n = ch.n_joints;
+  double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  double zj[kMaxJoints][3];
+  for (int i = 0; i < frame && i < n && i < kMaxJoints; i++) {
+    for (int r = 0; r < 3; r++) zj[i][r] = R[r][2];
+    const double th = q[i] + ch.theta0[i];
+    const double ct = std::cos(th), st = std::sin(th), ca = std::cos(ch.alpha[i]), sa = std::sin(ch.alpha[i]);
+    const double T[3][3] = {{ct, -st * ca, st * sa}, {st, ct * ca, -ct * sa}, {0.0, sa, ca}};
+    double G[3][3];
+    for (int r = 0; r < 3; r++)
+      for (int k = 0; k < 3; k++) G[r][k] = R[r][0] * T[0][k] + R[r][1] * T[1][k] + R[r][2] * T[2][k];
+    for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) R[r][k] = G[r][k];
+  }
+  for (int r = 0; r < 3; r++) u[r] = R[r][0] * a[0] + R[r][1] * a[1] + R[r][2] * a[2];
+  if (!dU) return;
+  for (int j = 0; j < n; j++) {
+    double col[3] = {0, 0, 0};
+    if (j < frame) {
+      col[0] = zj[j][1] * u[2] - zj[j][2] * u[1];
+      col[1] = zj[j][2] * u[0] - zj[j][0] * u[2];
+      col[2] = zj[j][0] * u[1] - zj[j][1] * u[0];
+    }
+    for (int ax = 0; ax < 3; ax++) dU[ax * n + j] = col[ax];
+  }
+}
+
 }  // namespace dh
 }  // namespace mi_osqp
 
@@ -76,6 +107,18 @@ inline RobotBall dhBall(const mi_gomp_chain &chain, int frame, const std::array<
   RobotBall b(std::move(fk), std::move(jac), radius, is_gripper);
   b.withBuiltin(MI_GOMP_MODEL_DH_CHAIN, {(double)frame, c[0], c[1], c[2]});
   return b;
+}
+
+// A tilt limit on the unit vector `axis` fixed in frame `frame` of the chain: it stays within max_angle radians of the unit
+// world vector `ref`, the row starts to constrain `margin` radians inside the cone.  The callback is what the sequential,
+// lock-step and host-assembling drivers call; frame and axis are what the device path reads.
+inline TiltLimit dhTilt(const mi_gomp_chain &chain, int frame, const std::array<double, 3> &axis, const std::array<double, 3> &ref, double max_angle,
+                        double margin = 0.0) {
+  TiltLimit t;
+  t.axis = [chain, frame, axis](const double *q, double *u, double *dU) { mi_osqp::dh::axis(chain, q, frame, axis.data(), u, dU); };
+  t.ref = ref; t.max_angle = max_angle; t.margin = margin;
+  t.builtin_frame = frame; t.builtin_axis = axis;
+  return t;
 }
 
 // The usual "skip adjacent links" rule of a self-collision model: every pair (i, j), i < j, of dhBall balls of `balls` whose

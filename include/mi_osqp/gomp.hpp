@@ -9,6 +9,7 @@
 //   CapsuleObstacle          not in the reference: a segment swept by a sphere (posts, pipes, other robots' links; a == b: a sphere)
 //   CuboidObstacle           not in the reference: an oriented box, optionally rounded (bin walls and floors, table tops, shelves)
 //   BallPair                 not in the reference: two balls of the robot that must stay apart (self-collision)
+//   TiltLimit                not in the reference: an axis of the robot that must stay within an angle of a world direction
 //   GOMPSolver<N>            [REF] src/gomp-solver.h:13-201
 //
 // Same names, argument meaning, row layout and control flow as the reference (the known-answer
@@ -312,30 +313,81 @@ bool pairsClearAlong(const std::vector<BallPair> &pairs, const std::vector<Robot
   return res;
 }
 
+// ------------------------------------------------------------- tilt limits: "keep the tool upright" (not in the reference)
+// A unit vector fixed in a link of the robot must stay within max_angle radians of the unit world vector `ref`:
+// c(q) = u(q) . ref >= cos(max_angle) (mi_gomp_tilt is its device twin, include/mi_osqp.h has the formulas).  The row of a
+// (tilt, waypoint) is the gradient of c in the joints, g_j = (du/dq_j) . ref, and becomes active `margin` radians inside the
+// cone.  When u is parallel or antiparallel to ref the gradient vanishes and the row is all zeros: parallel it is inactive,
+// antiparallel it is active with l = cos(max_angle) + 1 > 0 and the QP is primal infeasible - start inside the cone.
+using AxisFun = std::function<void(const double *, double *, double *)>;   // in: q; out: u[3] and (non-null) dU, 3 x N row-major, column j = du/dq_j
+struct TiltLimit {
+  AxisFun axis;                               // the axis in the world and its derivative; any arm, not only DH chains
+  std::array<double, 3> ref{0.0, 0.0, 1.0};
+  double max_angle = 0.0, margin = 0.0;       // radians
+  // as RobotBall::builtin_model: for an axis fixed in a frame of the planner's DH chain (dhTilt of dh_kinematics.hpp makes
+  // one) the frame and the axis in it, which the device path reads; frame 0: none
+  int builtin_frame = 0;
+  std::array<double, 3> builtin_axis{};
+  // the three thresholds, as mi_gomp_scene_create_tilts takes them
+  double cosLimit() const { return std::cos(max_angle); }
+  double cosActive() const { return std::cos(std::max(0.0, max_angle - margin)); }
+  double cosOK() const { return std::cos(std::min(M_PI, max_angle + ERROR)); }
+  bool operator==(const TiltLimit &o) const {   // (the callback cannot be compared: the kept device scenes hold the rest)
+    return ref == o.ref && max_angle == o.max_angle && margin == o.margin && builtin_frame == o.builtin_frame && builtin_axis == o.builtin_axis;
+  }
+};
+// c = u . ref at q, and (g non-null) its gradient g[N]
+template <size_t N>
+double tiltCosine(const TiltLimit &t, const double *q, double *g = nullptr) {
+  double u[3];
+  std::array<double, 3 * N> dU{};
+  t.axis(q, u, g ? dU.data() : nullptr);
+  if (g) for (size_t j = 0; j < N; ++j) g[j] = dU[0 * N + j] * t.ref[0] + dU[1 * N + j] * t.ref[1] + dU[2 * N + j] * t.ref[2];
+  return u[0] * t.ref[0] + u[1] * t.ref[1] + u[2] * t.ref[2];
+}
+// the tilt part of isSolutionOK at one waypoint (shared by the three drivers): within max_angle + 1 mrad
+template <size_t N>
+bool tiltsOK(const std::vector<TiltLimit> &tilts, const double *q) {
+  bool res = true;
+  for (const TiltLimit &t : tilts) if (!(tiltCosine<N>(t, q) >= t.cosOK())) res = false;
+  return res;
+}
+// tiltsOK at every waypoint of a joint trajectory (positions in the first half of the vector)
+template <size_t N>
+bool tiltsOKAlong(const std::vector<TiltLimit> &tilts, const QPVector &trajectory) {
+  if (tilts.empty()) return true;
+  bool res = true;
+  for (size_t w = 0; w < trajectory.size() / 2 / N; ++w)
+    if (!tiltsOK<N>(tilts, trajectory.data() + w * N)) res = false;
+  return res;
+}
+
 // ------------------------------------------------------------- constraint-builder.h
 // Rows: (W-1)*D velocity<->position links, then per variable boxes (positions W*D, velocities
 // (W-1)*D, accelerations (W-2)*D), then D*W*(3 + (|obstacles| + |capsules| + |cuboids|)*|balls|) rows for the linearised
-// end-effector / obstacle constraints (allocated even when unused: bounds +-INF), then W*|pairs| rows more.  The populated
-// 3-D rows come first: the blocks of the (ball, waypoint) pairs, then the ball pairs' rows, pair-major.
+// end-effector / obstacle constraints (allocated even when unused: bounds +-INF), then W*(|pairs| + |tilts|) rows more.  The
+// populated 3-D rows come first: the blocks of the (ball, waypoint) pairs, then the ball pairs' rows, pair-major, then the
+// tilt limits' rows, tilt-major.
 template <size_t N_DIM>
 class ConstraintBuilder {
   using OptPair = std::pair<std::optional<double>, std::optional<double>>;
 
  public:
   ConstraintBuilder(size_t waypoints, std::vector<RobotBall> m, std::vector<HorizontalLine> obstacles, std::vector<CapsuleObstacle> capsules = {},
-                    std::vector<CuboidObstacle> cuboids = {}, std::vector<BallPair> pairs = {})
+                    std::vector<CuboidObstacle> cuboids = {}, std::vector<BallPair> pairs = {}, std::vector<TiltLimit> tilts = {})
       : W_(waypoints), balls_(std::move(m)), lines_(std::move(obstacles)), capsules_(std::move(capsules)), cuboids_(std::move(cuboids)),
-        pairs_(std::move(pairs)) {
+        pairs_(std::move(pairs)), tilts_(std::move(tilts)) {
+    for ([[maybe_unused]] const TiltLimit &t : tilts_) assert(t.axis && t.max_angle > 0.0 && t.max_angle < M_PI && t.margin >= 0.0);
     for ([[maybe_unused]] const BallPair &pr : pairs_) assert(pr.a < balls_.size() && pr.b < balls_.size() && pr.a != pr.b && pr.margin >= 0.0);
-    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size() + cuboids_.size()) + pairs_.size()));
-    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size()) + W_ * pairs_.size()); up_.reserve(lo_.capacity());
+    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size() + cuboids_.size()) + pairs_.size() + tilts_.size()));
+    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size()) + W_ * (pairs_.size() + tilts_.size())); up_.reserve(lo_.capacity());
     for (size_t t = 0; t + 1 < W_; ++t)                      // v_t - q_{t+1} + q_t = 0
       for (size_t j = 0; j < N_DIM; ++j) {
         lo_.push_back(-INF); up_.push_back(INF);
         put(lo_.size() - 1, {{nthVelocity(t) + j, 1.0}, {nthPos(t + 1) + j, -1.0}, {nthPos(t) + j, 1.0}}, {0.0, 0.0});
       }
     user_off_ = lo_.size();
-    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size())) + W_ * pairs_.size();
+    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size())) + W_ * (pairs_.size() + tilts_.size());
     lo_.resize(user_off_ + extra, -INF);
     up_.resize(user_off_ + extra, INF);
   }
@@ -393,6 +445,8 @@ class ConstraintBuilder {
     }
     for (const BallPair &pr : pairs_)                            // behind the block of the last ball, pair-major
       for (size_t w = 0; w < W_; ++w) pairRow(row++, pr, trajectory, w);
+    for (const TiltLimit &t : tilts_)                            // behind the pair rows, tilt-major
+      for (size_t w = 0; w < W_; ++w) tiltRow(row++, t, trajectory, w);
     return *this;
   }
 
@@ -406,7 +460,7 @@ class ConstraintBuilder {
         if (ball.is_gripper) for (Axis axis : XYZ_AXES) axisRow(row++, ball, axis, J, w, -INF, INF);
         for (size_t k = 0; k < lines_.size() + capsules_.size() + cuboids_.size(); ++k) axisRow(row++, ball, Z, J, w, -INF, INF);
       }
-    for (size_t k = 0; k < pairs_.size(); ++k)
+    for (size_t k = 0; k < pairs_.size() + tilts_.size(); ++k)
       for (size_t w = 0; w < W_; ++w, ++row) {
         for (size_t j = 0; j < N_DIM; ++j) set(nthPos(w) + j, row, 0.0);
         lo_[row] = -INF; up_[row] = INF;
@@ -439,6 +493,7 @@ class ConstraintBuilder {
   std::vector<CapsuleObstacle> capsules_;
   std::vector<CuboidObstacle> cuboids_;
   std::vector<BallPair> pairs_;
+  std::vector<TiltLimit> tilts_;
   // (col, row) -> value, last write wins ([REF] constraint-builder.h:129).  A write log that is sorted into CSC
   // order and de-duplicated on demand: the builder runs once per trajectory, segment and re-linearisation,
   // and a std::map made it the bottleneck of the batched driver.
@@ -568,6 +623,20 @@ class ConstraintBuilder {
     lo_[row] = dist - reach < pr.margin ? (reach - dist) + gq : -INF;
     up_[row] = INF;
   }
+  // the gradient of c = u . ref, written whether the row is active or not; active within `margin` radians of the cone:
+  // cos(max_angle) - c + g q <= g x, the linearisation of c(x) >= cos(max_angle) around q
+  void tiltRow(size_t row, const TiltLimit &t, const QPVector &trajectory, size_t waypoint) {
+    Vec<N_DIM> q, g;
+    for (size_t j = 0; j < N_DIM; ++j) q[j] = trajectory[waypoint * N_DIM + j];
+    const double c = tiltCosine<N_DIM>(t, q.data(), g.data());
+    double gq = 0.0;
+    for (size_t j = 0; j < N_DIM; ++j) {
+      set(nthPos(waypoint) + j, row, g[j]);
+      gq += g[j] * q[j];
+    }
+    lo_[row] = c < t.cosActive() ? (t.cosLimit() - c) + gq : -INF;
+    up_[row] = INF;
+  }
 };
 
 // ------------------------------------------------------------------- gomp-solver.h
@@ -657,6 +726,8 @@ class GOMPSolver {
   std::vector<CuboidObstacle> cuboids;
   // Self-collision: pairs of `mappers` balls that must stay apart (dhSelfPairs of dh_kinematics.hpp makes them); set before run()
   std::vector<BallPair> pairs;
+  // Tilt limits: axes of the arm that must stay within an angle of a world direction (dhTilt of dh_kinematics.hpp makes them); set before run()
+  std::vector<TiltLimit> tilts;
   // (tests) the acceptance test that ends the SQP loop
   bool acceptable(const QPVector &q_trajectory) const { return isSolutionOK(q_trajectory); }
 
@@ -685,7 +756,7 @@ class GOMPSolver {
   }
   ConstraintBuilder<N_DIM> jointSpaceRows(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
     assert(waypoints >= 4);
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -718,6 +789,7 @@ class GOMPSolver {
       }
     }
     if (!pairsClearAlong<N_DIM>(pairs, mappers, q_trajectory)) res = false;
+    if (!tiltsOKAlong<N_DIM>(tilts, q_trajectory)) res = false;
     return res;
   }
 };
@@ -848,6 +920,7 @@ class BatchGOMPSolver {
   std::vector<CapsuleObstacle> capsules;      // capsule / sphere obstacles besides the lines; set before run()
   std::vector<CuboidObstacle> cuboids;        // cuboid obstacles (oriented boxes); set before run()
   std::vector<BallPair> pairs;                // self-collision pairs of the balls; set before run()
+  std::vector<TiltLimit> tilts;               // tilt limits; set before run()
   int solver_reuses = 0;          // how often a kept solver was re-initialised instead of a new one being built
   // where the wall time of the last run() went: building constraints, QP setup (analysis + upload + factorisation),
   // batched solves, feasibility checks + re-linearisation + update
@@ -881,7 +954,7 @@ class BatchGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -914,6 +987,7 @@ class BatchGOMPSolver {
       }
     }
     if (!pairsClearAlong<N_DIM>(pairs, mappers, q_trajectory)) res = false;
+    if (!tiltsOKAlong<N_DIM>(tilts, q_trajectory)) res = false;
     return res;
   }
 };
@@ -945,11 +1019,12 @@ class ContinuousGOMPSolver {
     const size_t B = starts.size();
     assert(ends.size() == B && B > 0);
     starts_ = &starts; ends_ = &ends;
-    if (!(capsules == scene_capsules_ && cuboids == scene_cuboids_ && pairs == scene_pairs_)) {   // the kept scenes hold the capsules, cuboids and pairs of the run that made them
+    if (!(capsules == scene_capsules_ && cuboids == scene_cuboids_ && pairs == scene_pairs_ && tilts == scene_tilts_)) {   // the kept scenes hold the capsules, cuboids, pairs and tilt limits of the run that made them
       for (Stage &st : stages_) if (st.scene) { mi_gomp_scene_free(st.scene); st.scene = nullptr; }
       scene_capsules_ = capsules;
       scene_cuboids_ = cuboids;
       scene_pairs_ = pairs;
+      scene_tilts_ = tilts;
     }
     traj_.clear(); traj_.resize(B);
     segments_run.assign(B, 0); qp_solves.assign(B, 0); qp_updates.assign(B, 0);
@@ -999,6 +1074,9 @@ class ContinuousGOMPSolver {
   std::vector<CuboidObstacle> cuboids;
   // Self-collision pairs of the balls; set before run().  On the device path they go into the scene (mi_gomp_scene_create_pairs).
   std::vector<BallPair> pairs;
+  // Tilt limits; set before run().  On the device path they go into the scene (mi_gomp_scene_create_tilts), which needs
+  // dh_chain and limits made by dhTilt (builtin_frame set).
+  std::vector<TiltLimit> tilts;
   int pipeline_depth = 1;              // 2: a stage enqueues its next advance before it looks at the previous one's results
   int segments_per_advance = 4;        // a launch runs on until a QP of the stage finishes, at most that many segments
   // per stage: {waypoints, advances, seconds admitting, waiting for the device, processing finished QPs, idle}
@@ -1043,6 +1121,7 @@ class ContinuousGOMPSolver {
   std::vector<CapsuleObstacle> scene_capsules_;
   std::vector<CuboidObstacle> scene_cuboids_;
   std::vector<BallPair> scene_pairs_;
+  std::vector<TiltLimit> scene_tilts_;
   const std::vector<Ctrl<N_DIM>> *starts_ = nullptr, *ends_ = nullptr;
   std::atomic<size_t> finished_{0};
   std::atomic<bool> failed_{false};
@@ -1126,6 +1205,7 @@ class ContinuousGOMPSolver {
   bool useDevice() const {
     if (!device_assembly) return false;
     for (const RobotBall &b : mappers) if (!b.builtin_model || (b.builtin_model == MI_GOMP_MODEL_DH_CHAIN && !dh_chain)) return false;
+    for (const TiltLimit &t : tilts) if (t.builtin_frame < 1 || !dh_chain) return false;       // (a callback alone: the host path)
     return true;
   }
   void makeScene(Stage &st) {
@@ -1163,7 +1243,18 @@ class ContinuousGOMPSolver {
     }
     std::vector<mi_gomp_pair> prs;
     for (const BallPair &p : pairs) prs.push_back(mi_gomp_pair{(int32_t)p.a, (int32_t)p.b, p.margin});
-    const int rc = !prs.empty() ? mi_gomp_scene_create_pairs(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+    std::vector<mi_gomp_tilt> tls;
+    for (const TiltLimit &t : tilts) {
+      mi_gomp_tilt g{};
+      g.frame = (int32_t)t.builtin_frame;
+      for (int k = 0; k < 3; k++) { g.axis[k] = t.builtin_axis[k]; g.ref[k] = t.ref[k]; }
+      g.max_angle = t.max_angle; g.margin = t.margin;
+      tls.push_back(g);
+    }
+    const int rc = !tls.empty() ? mi_gomp_scene_create_tilts(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+                                                              (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(),
+                                                              (int64_t)cubs.size(), cubs.data(), (int64_t)prs.size(), prs.data(), (int64_t)tls.size(), tls.data(), lo, hi)
+                   : !prs.empty() ? mi_gomp_scene_create_pairs(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
                                                               (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(),
                                                               (int64_t)cubs.size(), cubs.data(), (int64_t)prs.size(), prs.data(), lo, hi)
                    : !cubs.empty() ? mi_gomp_scene_create_cuboids(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
@@ -1253,7 +1344,7 @@ class ContinuousGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -1286,6 +1377,7 @@ class ContinuousGOMPSolver {
       }
     }
     if (!pairsClearAlong<N_DIM>(pairs, mappers, q_trajectory)) res = false;
+    if (!tiltsOKAlong<N_DIM>(tilts, q_trajectory)) res = false;
     return res;
   }
 };

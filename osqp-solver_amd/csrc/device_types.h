@@ -289,16 +289,22 @@ struct GompCapsuleDev { double a[3], e[3], ee, R, margin; };
 struct GompCuboidDev { double o[3], u[9], h[3], R, margin; };
 // a self-collision pair (mi_gomp_pair): balls a and b of the scene keep |p_a - p_b| - (r_a + r_b) >= 0; margin as for the capsule
 struct GompPairDev { int a, b; double margin; };
+// a tilt limit (mi_gomp_tilt): `axis`, fixed in frame `frame` of the chain, stays within max_angle of the world vector `ref`;
+// the three cosines are taken once on the host: cos_lim the limit, cos_act where the row starts to constrain, cos_ok what
+// the acceptance test allows
+struct GompTiltDev { int frame, pad; double axis[3], ref[3], cos_lim, cos_act, cos_ok; };
 struct GompArgs {
   int dims, W, n_balls, n_lines, n, m, nnzA, n_ids, row0, write_rows;
   int n_caps, n_cuboids;
   int n_pairs, pair_row0;        // pair_row0: the first pair row = row0 + the rows of all (ball, waypoint) blocks
+  int n_tilts, tilt_row0;        // tilt_row0: the first tilt row = pair_row0 + W n_pairs
   const int *ids;                // the listed QPs
   const GompBallDev *balls;
   const GompLineDev *lines;
   const GompCapsuleDev *caps;    // [n_caps]: their rows follow the lines' in every (ball, waypoint) block
   const GompCuboidDev *cuboids;  // [n_cuboids]: their rows follow the capsules'
   const GompPairDev *pairs;      // [n_pairs]: row pair_row0 + k W + w for (pair k, waypoint w), behind every ball's block
+  const GompTiltDev *tilts;      // [n_tilts]: row tilt_row0 + k W + w for (tilt k, waypoint w), behind the pair rows
   double con_lo[3], con_hi[3];   // work-space box of the gripper balls (+-1e30 = none)
   const int *aidx;               // [3-D row][dims]: position of that row's entry in column nthPos(w) + j of A's value array
   const double *traj;            // [n_ids][n]: the trajectories to linearise around (row = position in the list)

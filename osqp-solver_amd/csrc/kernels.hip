@@ -3893,7 +3893,9 @@ hipError_t launch_ruiz(const RuizArgs &a, hipStream_t st) {
 // (below) the lines it collides with.  Every (ball, capsule) pair gets one row after the lines' (see the loop over g.caps) and
 // must keep a clearance of -1e-3 or more; every (ball, cuboid) pair one row after the capsules', by the same rule.  One
 // workgroup per trajectory, one thread per (ball, waypoint); behind those items one thread per (ball pair, waypoint): one row
-// each behind the block of the last ball, the same rule on the distance of the two centres.
+// each behind the block of the last ball, the same rule on the distance of the two centres; behind those one thread per (tilt
+// limit, waypoint): one row each behind the pair rows, the gradient of the cosine between an axis of the chain and a world
+// vector, active near the cone, and no waypoint may be more than 1 mrad outside it.
 __device__ __forceinline__ void ur5e_point(const double *q, int frame, double *p, double *J /* 3 x 6 row-major */) {
   const double a[6] = {0.0, -0.425, -0.3922, 0.0, 0.0, 0.0}, d[6] = {0.1625, 0.0, 0.0, 0.1333, 0.0997, 0.0996};
   const double alpha[6] = {1.5707963267948966, 0.0, 0.0, 1.5707963267948966, -1.5707963267948966, 0.0};
@@ -3958,6 +3960,40 @@ __device__ __forceinline__ void dh_point(const GompChainDev &ch, const double *q
     J8[2 * MI_GOMP_MAXD + j] = on ? S[0][2] * r[1] - S[1][2] * r[0] : 0.0;
     dh_advance(S, s, ct[j], st[j], ch.ca[j], ch.sa[j], ch.a[j], ch.d[j], on);
   }
+}
+// A unit vector `a` fixed in frame `frame` of the chain (a tilt limit, formulas at mi_gomp_tilt): u = R_k a in the world,
+// c = u . ref, and with `grad` the gradient of c in the joints, g_j = (z_j x u) . ref for j < frame, 0 from `frame` on.
+// dh_point without the origins: rotations only, the same two walks over all MI_GOMP_MAXD joints under the same rule -
+// nothing indexed by the frame or by D.  The first walk gives u; the second forms g_j as it reaches z_j.
+__device__ __forceinline__ void dh_turn(double (&R)[3][3], double ct, double st, double ca, double sa, bool on) {
+  const double T[3][3] = {{ct, -st * ca, st * sa}, {st, ct * ca, -ct * sa}, {0.0, sa, ca}};
+  double G[3][3];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) G[r][c] = R[r][0] * T[0][c] + R[r][1] * T[1][c] + R[r][2] * T[2][c];
+  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) R[r][c] = on ? G[r][c] : R[r][c];
+}
+__device__ __forceinline__ double dh_axis(const GompChainDev &ch, const double *q, int frame, const double *a, const double *ref, bool grad, double *g8) {
+  double ct[MI_GOMP_MAXD], st[MI_GOMP_MAXD];
+  double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+#pragma unroll
+  for (int i = 0; i < MI_GOMP_MAXD; i++) {
+    const double th = i < frame ? q[i] + ch.theta0[i] : 0.0;
+    ct[i] = cos(th); st[i] = sin(th);
+    dh_turn(R, ct[i], st[i], ch.ca[i], ch.sa[i], i < frame);
+  }
+  double u[3];
+  for (int r = 0; r < 3; r++) u[r] = R[r][0] * a[0] + R[r][1] * a[1] + R[r][2] * a[2];
+  const double c = u[0] * ref[0] + u[1] * ref[1] + u[2] * ref[2];
+  if (!grad) return c;
+  double S[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+#pragma unroll
+  for (int j = 0; j < MI_GOMP_MAXD; j++) {
+    const bool on = j < frame;
+    const double h0 = S[1][2] * u[2] - S[2][2] * u[1], h1 = S[2][2] * u[0] - S[0][2] * u[2], h2 = S[0][2] * u[1] - S[1][2] * u[0];
+    g8[j] = on ? h0 * ref[0] + h1 * ref[1] + h2 * ref[2] : 0.0;
+    dh_turn(S, ct[j], st[j], ch.ca[j], ch.sa[j], on);
+  }
+  return c;
 }
 __device__ __forceinline__ void gomp_fk_jac(const GompChainDev &ch, const GompBallDev &b, int D, const double *q, double *p, double *J) {
   for (int k = 0; k < 3 * D; k++) J[k] = 0.0;
@@ -4154,6 +4190,30 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
       }
     }
     g.l[(size_t)qp * g.m + row] = s < pr.margin ? (reach - dist) + gq : -MI_INFTY;
+    g.u[(size_t)qp * g.m + row] = MI_INFTY;
+  }
+  // tilt limits (TiltLimit of gomp.hpp, formulas at mi_gomp_tilt): the items behind the pair items, tilt-major, walked flat.
+  // Rotations only (dh_axis): the verdict needs the cosine c and so the first walk of the chain, the row both walks.  One call
+  // site for both passes, not unrolled: one more copy of the chain's uniform values, not two.
+#pragma unroll 1
+  for (int e = tid; e < g.n_tilts * W; e += blockDim.x) {
+    const int k = e / W, w = e % W;
+    const GompTiltDev &tl = g.tilts[k];
+#pragma unroll
+    for (int j = 0; j < MI_GOMP_MAXD; j++) q[j] = j < D ? traj[(size_t)w * D + j] : 0.0;
+    const double c = dh_axis(g.chain, q, tl.frame, tl.axis, tl.ref, wr, J);
+    if (!(c >= tl.cos_ok)) ok = 0;
+    if (!wr) continue;
+    const int row = g.tilt_row0 + e;
+    const int *ai = g.aidx + (size_t)(row - g.row0) * D;
+    double gq = 0.0;
+#pragma unroll
+    for (int j = 0; j < MI_GOMP_MAXD; j++)
+      if (j < D) {
+        g.A[(size_t)qp * g.nnzA + ai[j]] = J[j];                                               // written for inactive rows too
+        gq += J[j] * q[j];
+      }
+    g.l[(size_t)qp * g.m + row] = c < tl.cos_act ? (tl.cos_lim - c) + gq : -MI_INFTY;
     g.u[(size_t)qp * g.m + row] = MI_INFTY;
   }
   }

@@ -3812,13 +3812,14 @@ int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t
 // Besides the built-in models a scene may hold one DH chain (mi_gomp_chain) with balls fixed in its link frames.
 struct mi_gomp_scene {
   mi_osqp_batch *h = nullptr;
-  int dims = 0, W = 0, n_balls = 0, n_lines = 0, n_caps = 0, n_cuboids = 0, n_pairs = 0, pair_row0 = 0, row0 = 0, n_rows3d = 0;
+  int dims = 0, W = 0, n_balls = 0, n_lines = 0, n_caps = 0, n_cuboids = 0, n_pairs = 0, pair_row0 = 0, n_tilts = 0, tilt_row0 = 0, row0 = 0, n_rows3d = 0;
   double con_lo[3] = {-1e30, -1e30, -1e30}, con_hi[3] = {1e30, 1e30, 1e30};
   DevBuf<GompBallDev> balls;
   DevBuf<GompLineDev> lines;
   DevBuf<GompCapsuleDev> caps;
   DevBuf<GompCuboidDev> cuboids;
   DevBuf<GompPairDev> pairs;                  // their rows: pair_row0 + k W + w, behind every ball's block
+  DevBuf<GompTiltDev> tilts;                  // their rows: tilt_row0 + k W + w, behind the pair rows
   GompChainDev chain{};                       // the DH chain of the MI_GM_DH_CHAIN balls (n_joints 0: the scene has none)
   DevBuf<int> aidx;
   DevBuf<double> A, l, u;                     // QP-major raw rows as ConstraintBuilder::build() lays them out
@@ -3841,9 +3842,9 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
   if ((rc = ring_upload(h, sp, (size_t)nq * n * sizeof(double)))) return rc;
   hipStream_t st = h->stream;
   GompArgs g{};
-  g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n_caps = sc->n_caps; g.n_cuboids = sc->n_cuboids; g.n_pairs = sc->n_pairs; g.pair_row0 = sc->pair_row0; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
+  g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n_caps = sc->n_caps; g.n_cuboids = sc->n_cuboids; g.n_pairs = sc->n_pairs; g.pair_row0 = sc->pair_row0; g.n_tilts = sc->n_tilts; g.tilt_row0 = sc->tilt_row0; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
   g.row0 = sc->row0; g.write_rows = write_rows;
-  g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.caps = sc->caps.p; g.cuboids = sc->cuboids.p; g.pairs = sc->pairs.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
+  g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.caps = sc->caps.p; g.cuboids = sc->cuboids.p; g.pairs = sc->pairs.p; g.tilts = sc->tilts.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
   for (int k = 0; k < 3; k++) { g.con_lo[k] = sc->con_lo[k]; g.con_hi[k] = sc->con_hi[k]; }
   g.A = sc->A.p; g.l = sc->l.p; g.u = sc->u.p; g.ok = sc->h_ok;
   g.chain = sc->chain;
@@ -3856,12 +3857,13 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
 
 // mi_gomp_scene_create (chain null: model 6 is refused as it always was), mi_gomp_scene_create_chain and
 // mi_gomp_scene_create_world (capsules besides), mi_gomp_scene_create_cuboids (cuboids besides those) and
-// mi_gomp_scene_create_pairs (ball pairs besides those).  Everything that can be refused is refused here on the host, the
-// checks that need no handle first.
+// mi_gomp_scene_create_pairs (ball pairs besides those) and mi_gomp_scene_create_tilts (tilt limits besides those).
+// Everything that can be refused is refused here on the host, the checks that need no handle first.
 static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain, bool chain_entry,
                              int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                              int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
-                             int64_t n_pairs, const mi_gomp_pair *pairs, const double *con_lo, const double *con_hi) {
+                             int64_t n_pairs, const mi_gomp_pair *pairs, int64_t n_tilts, const mi_gomp_tilt *tilts,
+                             const double *con_lo, const double *con_hi) {
   if (!out) return MI_OSQP_ERR_NULL;
   *out = nullptr;
   if ((n_balls > 0 && !balls) || (n_lines > 0 && !lines)) return MI_OSQP_ERR_NULL;
@@ -3902,6 +3904,9 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
       g_last_error = "pair " + std::to_string(k) + " joins two chain balls of one frame: their distance is constant"; return MI_OSQP_ERR_INVALID_DATA;
     }
   }
+  if (n_tilts > 0 && !tilts) { g_last_error = "n_tilts > 0 and no tilts"; return MI_OSQP_ERR_NULL; }
+  if (n_tilts < 0) { g_last_error = "n_tilts is negative"; return MI_OSQP_ERR_INVALID_DATA; }
+  if (n_tilts > 0 && !chain) { g_last_error = "tilt 0 names a frame of the chain and the scene has no chain"; return MI_OSQP_ERR_NULL; }
   GompChainDev hc{};
   if (chain_entry) {
     for (int64_t b = 0; b < n_balls; b++)
@@ -3927,6 +3932,28 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
       for (int i = nj; i < MI_GOMP_MAXD; i++) hc.ca[i] = 1.0;      // (never part of a result: identity joints)
     }
   }
+  // a tilt limit: the three cosines the kernel compares with are taken here, once, in fp64
+  std::vector<GompTiltDev> htilt((size_t)(n_tilts > 0 ? n_tilts : 0));
+  for (int64_t k = 0; k < n_tilts; k++) {
+    const mi_gomp_tilt &tl = tilts[k];
+    const std::string who = "tilt " + std::to_string(k);
+    bool finite = std::isfinite(tl.max_angle) && std::isfinite(tl.margin);
+    for (int i = 0; i < 3; i++) finite = finite && std::isfinite(tl.axis[i]) && std::isfinite(tl.ref[i]);
+    if (!finite) { g_last_error = who + " has a field that is not finite"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (tl.frame < 1 || tl.frame > hc.n_joints) { g_last_error = who + ": frame must be 1 .. n_joints"; return MI_OSQP_ERR_INVALID_DATA; }
+    const double na = std::sqrt(tl.axis[0] * tl.axis[0] + tl.axis[1] * tl.axis[1] + tl.axis[2] * tl.axis[2]);
+    const double nr = std::sqrt(tl.ref[0] * tl.ref[0] + tl.ref[1] * tl.ref[1] + tl.ref[2] * tl.ref[2]);
+    if (!(std::fabs(na - 1.0) <= 1e-9)) { g_last_error = who + ": axis is not a unit vector"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (!(std::fabs(nr - 1.0) <= 1e-9)) { g_last_error = who + ": ref is not a unit vector"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (!(tl.max_angle > 0.0 && tl.max_angle < M_PI)) { g_last_error = who + ": max_angle must lie in (0, pi)"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (tl.margin < 0.0) { g_last_error = who + ": the margin must not be negative"; return MI_OSQP_ERR_INVALID_DATA; }
+    GompTiltDev &d = htilt[(size_t)k];
+    d.frame = tl.frame; d.pad = 0;
+    for (int i = 0; i < 3; i++) { d.axis[i] = tl.axis[i]; d.ref[i] = tl.ref[i]; }
+    d.cos_lim = std::cos(tl.max_angle);
+    d.cos_act = std::cos(std::max(0.0, tl.max_angle - tl.margin));
+    d.cos_ok = std::cos(std::min(M_PI, tl.max_angle + 1e-3));
+  }
   if (!h) return MI_OSQP_ERR_NULL;
   const Analysis &an = (*h->anp);
   const int D = (int)dims, W = (int)waypoints;
@@ -3942,12 +3969,18 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
   }
   const int pair_row0 = row0 + rows3d;                             // the pair rows: behind the block of the last ball, pair-major
   rows3d += W * (int)n_pairs;
-  if (row0 + rows3d > an.m) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene"; return MI_OSQP_ERR_INVALID_DATA; }
+  const int tilt_row0 = row0 + rows3d;                             // the tilt rows: behind the pair rows, tilt-major
+  rows3d += W * (int)n_tilts;
+  if (row0 + rows3d > an.m) {
+    g_last_error = "the constraint matrix does not hold the 3-D rows of this scene";
+    if (n_tilts > 0 && tilt_row0 <= an.m) g_last_error += " (tilt " + std::to_string((an.m - tilt_row0) / W) + ")";   // the first tilt without its rows
+    return MI_OSQP_ERR_INVALID_DATA;
+  }
   DevGuard guard(h->device);
   mi_gomp_scene *sc = new (std::nothrow) mi_gomp_scene();
   if (!sc) return MI_OSQP_ERR_ALLOC;
   std::unique_ptr<mi_gomp_scene> own(sc);
-  sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->n_caps = (int)n_capsules; sc->n_cuboids = (int)n_cuboids; sc->n_pairs = (int)n_pairs; sc->pair_row0 = pair_row0; sc->row0 = row0; sc->n_rows3d = rows3d;
+  sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->n_caps = (int)n_capsules; sc->n_cuboids = (int)n_cuboids; sc->n_pairs = (int)n_pairs; sc->pair_row0 = pair_row0; sc->n_tilts = (int)n_tilts; sc->tilt_row0 = tilt_row0; sc->row0 = row0; sc->n_rows3d = rows3d;
   sc->chain = hc;
   for (int k = 0; k < 3; k++) { sc->con_lo[k] = con_lo ? con_lo[k] : -1e30; sc->con_hi[k] = con_hi ? con_hi[k] : 1e30; }
   // where the entries of the 3-D rows sit in A's value array: row r of waypoint w holds D entries in the columns of q_w
@@ -3971,6 +4004,9 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
     for (int k = 0; k < (int)n_pairs; k++)
       for (int w = 0; w < W; w++, r++)
         if (!locate(w)) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene (pair " + std::to_string(k) + ")"; return MI_OSQP_ERR_INVALID_DATA; }
+    for (int k = 0; k < (int)n_tilts; k++)
+      for (int w = 0; w < W; w++, r++)
+        if (!locate(w)) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene (tilt " + std::to_string(k) + ")"; return MI_OSQP_ERR_INVALID_DATA; }
   }
   std::vector<GompBallDev> hb((size_t)n_balls);
   for (int b = 0; b < (int)n_balls; b++) { hb[b].model = balls[b].model; hb[b].is_gripper = balls[b].is_gripper; hb[b].radius = balls[b].radius; for (int k = 0; k < 12; k++) hb[b].param[k] = balls[b].param[k]; }
@@ -3999,7 +4035,7 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
   std::vector<GompPairDev> hpair((size_t)n_pairs);
   for (int k = 0; k < (int)n_pairs; k++) { hpair[k].a = pairs[k].a; hpair[k].b = pairs[k].b; hpair[k].margin = pairs[k].margin; }
   int rc;
-  if ((rc = sc->balls.upload(hb)) || (rc = sc->lines.upload(hl)) || (n_capsules && (rc = sc->caps.upload(hcap))) || (n_cuboids && (rc = sc->cuboids.upload(hcub))) || (n_pairs && (rc = sc->pairs.upload(hpair))) ||
+  if ((rc = sc->balls.upload(hb)) || (rc = sc->lines.upload(hl)) || (n_capsules && (rc = sc->caps.upload(hcap))) || (n_cuboids && (rc = sc->cuboids.upload(hcub))) || (n_pairs && (rc = sc->pairs.upload(hpair))) || (n_tilts && (rc = sc->tilts.upload(htilt))) ||
       (rc = sc->aidx.upload(aidx)) ||
       (rc = sc->A.alloc((size_t)h->B * std::max(an.Ap[an.n], 1))) || (rc = sc->l.alloc((size_t)h->B * std::max(an.m, 1))) || (rc = sc->u.alloc((size_t)h->B * std::max(an.m, 1)))) return rc;
   HIPCHK(hostpool::alloc((void **)&sc->h_ok, (size_t)h->B * sizeof(int), &sc->h_ok_cap));
@@ -4014,29 +4050,37 @@ extern "C" {
 
 int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, int64_t n_balls, const mi_gomp_ball *balls,
                          int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_chain(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_world(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                int64_t n_capsules, const mi_gomp_capsule *capsules, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_cuboids(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                  int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                  int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
                                  const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_pairs(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
                                int64_t n_pairs, const mi_gomp_pair *pairs, const double *con_lo, const double *con_hi) {
   return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids,
-                           n_pairs, pairs, con_lo, con_hi);
+                           n_pairs, pairs, 0, nullptr, con_lo, con_hi);
+}
+int mi_gomp_scene_create_tilts(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
+                               int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
+                               int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
+                               int64_t n_pairs, const mi_gomp_pair *pairs, int64_t n_tilts, const mi_gomp_tilt *tilts,
+                               const double *con_lo, const double *con_hi) {
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids,
+                           n_pairs, pairs, n_tilts, tilts, con_lo, con_hi);
 }
 
 void mi_gomp_scene_free(mi_gomp_scene *sc) {
