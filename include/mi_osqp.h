@@ -401,6 +401,18 @@ int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t
  * advances may be waiting for their poll().  A blocking mi_osqp_batch_* call ends the continuous mode of the handle (solves
  * in flight are forgotten).  Not available for handles whose solve vector does not fit LDS (large single QPs).
  *
+ * Results across the two modes.  The first per-QP call after setup or after a blocking call begins a continuous phase; the
+ * next blocking call ends it.  A QP that finishes no solve in a phase keeps the results it had on entry - those of its last
+ * finished solve, blocking or of an earlier phase, or the state after setup (zero x and y, status_val -10) if it was never
+ * solved -, whatever the other QPs of the handle, its tile partner included, are given and solve meanwhile:
+ *   - get_primal_some / get_dual_some / get_info_some return for it, from the first call of the phase on, what
+ *     mi_osqp_batch_get_primal / _get_dual / _get_info returned on entry, in every field of mi_osqp_info (rho_updates reads 0
+ *     where a whole-batch data update since the QP's last solve has restarted the count), until poll() reports a solve of it;
+ *   - after the phase the whole-batch getters return the same for it, next to the new results of the QPs that did finish,
+ *     and mi_osqp_batch_adjoint differentiates its solution of before the phase;
+ *   - its certificates read NaN through get_*_inf_cert_some (below) and are served again by the whole-batch getters after
+ *     the phase.
+ *
  * reinit_some = QPSolver::QPSolver for those QPs ([REF] src/osqp-wrapper.h:16-31) with the P and q in force (those given
  * at setup, or by the last mi_osqp_batch_update_P / _update_P_A / _update_P_device / update_P_some / _update_q / update_q_some of the QP) and new A values / bounds: equilibration from the raw data, rho = settings.rho, zero iterates, no rho updates - the state
  * mi_osqp_batch_setup leaves for that QP, bit for bit, without analysis or allocation.

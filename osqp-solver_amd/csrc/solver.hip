@@ -2175,6 +2175,17 @@ static int get_cert(mi_osqp_batch *h, double *out, bool primal) {
 int mi_osqp_batch_get_prim_inf_cert(mi_osqp_batch *h, double *dy_out) { return get_cert(h, dy_out, true); }
 int mi_osqp_batch_get_dual_inf_cert(mi_osqp_batch *h, double *dx_out) { return get_cert(h, dx_out, false); }
 
+// the report of QP q as the host images h_iscal / h_dscal hold it (the caller has fetched them)
+static void info_from_images(const mi_osqp_batch *h, int q, mi_osqp_info &I) {
+  const int BT = h->BT, b = q % BT;
+  const int *ti = h->h_iscal + (size_t)(q / BT) * IS_COUNT * BT;
+  const double *td = h->h_dscal + (size_t)(q / BT) * DS_COUNT * BT;
+  I.iter = ti[IS_ITER * BT + b]; I.status_val = ti[IS_STATUS * BT + b]; I.exit_code = exit_code_of((int)I.status_val);
+  I.obj_val = td[DS_OBJ * BT + b]; I.pri_res = td[DS_PRI_RES * BT + b]; I.dua_res = td[DS_DUA_RES * BT + b];
+  I.rho_updates = ti[IS_RHO_UPDATES * BT + b]; I.rho_estimate = td[DS_RHO_EST * BT + b]; I.rho = td[DS_RHO * BT + b];
+  I.status_polish = h->pol_status.empty() ? 0 : h->pol_status[(size_t)q];
+}
+
 int mi_osqp_batch_get_info(mi_osqp_batch *h, mi_osqp_info *info) {
   CallTimer timer_("batch_get_info");
   if (!h || !info) return MI_OSQP_ERR_NULL;
@@ -2183,17 +2194,7 @@ int mi_osqp_batch_get_info(mi_osqp_batch *h, mi_osqp_info *info) {
   size_t icnt = (size_t)h->ntiles * IS_COUNT * h->BT, dcnt = (size_t)h->ntiles * DS_COUNT * h->BT;
   HIPCHK(hipMemcpy(h->h_iscal, h->iscal.p, icnt * sizeof(int), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(h->h_dscal, h->dscal.p, dcnt * sizeof(double), hipMemcpyDeviceToHost));
-  const int BT = h->BT;
-  for (int q = 0; q < h->B; q++) {
-    const int *ti = h->h_iscal + (size_t)(q / BT) * IS_COUNT * BT;
-    const double *td = h->h_dscal + (size_t)(q / BT) * DS_COUNT * BT;
-    int b = q % BT;
-    mi_osqp_info &I = info[q];
-    I.iter = ti[IS_ITER * BT + b]; I.status_val = ti[IS_STATUS * BT + b]; I.exit_code = exit_code_of((int)I.status_val);
-    I.obj_val = td[DS_OBJ * BT + b]; I.pri_res = td[DS_PRI_RES * BT + b]; I.dua_res = td[DS_DUA_RES * BT + b];
-    I.rho_updates = ti[IS_RHO_UPDATES * BT + b]; I.rho_estimate = td[DS_RHO_EST * BT + b]; I.rho = td[DS_RHO * BT + b];
-    I.status_polish = h->pol_status.empty() ? 0 : h->pol_status[(size_t)q];
-  }
+  for (int q = 0; q < h->B; q++) info_from_images(h, q, info[q]);
   return MI_OSQP_OK;
 }
 
@@ -3094,19 +3095,27 @@ static int cont_enter(mi_osqp_batch *h) {
   if ((rc = c.counter.zero(h->stream))) return rc;
   c.h_done[0] = c.h_done[1] = 0;
   // the state of the last blocking solve, if any, stays valid; every slot is idle until its solve is begun
+  HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(h->h_iscal, h->iscal.p, icnt * sizeof(int), hipMemcpyDeviceToHost));
+  // ... and so do its results: the pinned images start as what the whole-batch getters return now (a block of the pool
+  // holds another handle's rows, and a handle's own images those of its last phase), so that a QP which finishes no solve in
+  // this phase reads the same through the *_some getters and has the same rows handed back by cont_leave
+  HIPCHK(hipMemcpy(c.xh, h->x_out.p, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost));
+  if (m) HIPCHK(hipMemcpy(c.yh, h->y_out.p, (size_t)B * m * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(h->h_dscal, h->dscal.p, (size_t)h->ntiles * DS_COUNT * BT * sizeof(double), hipMemcpyDeviceToHost));
   // (the certificates of the last blocking solve stay with their QPs - cont_leave hands the image back; most batches have none)
   if (any_cert_status(h)) HIPCHK(hipMemcpy(c.ch, h->cert_out.p, cert_bytes, hipMemcpyDeviceToHost));
   for (int t = 0; t < h->ntiles; t++)
     for (int b = 0; b < BT; b++) {
       int *p = h->h_iscal + (size_t)t * IS_COUNT * BT;
       p[IS_DONE * BT + b] = 1; p[IS_CUR * BT + b] = 0; p[IS_PENDING * BT + b] = 0; p[IS_EPOCH * BT + b] = 0;
-      if (!h->solved_once) p[IS_STATUS * BT + b] = 0;      // (no solve yet: the word is not initialised, and the adjoint reads it)
       if (h->clear_rho_updates) p[IS_RHO_UPDATES * BT + b] = 0;
       if (t * BT + b < B && h->failed[(size_t)t * BT + b]) p[IS_NEED_REFACTOR * BT + b] = -1;
     }
   h->clear_rho_updates = false;
-  h->solved_once = true;               // (from here on every status word is either 0 or what a finished solve left)
+  h->solved_once = true;               // (a QP never solved keeps the -10 of setup: it reads as unsolved in every getter, and the adjoint skips it)
+  // get_info_some until the QP's first report of this phase: what mi_osqp_batch_get_info returns once the phase is over
+  for (int q = 0; q < B; q++) info_from_images(h, q, c.info[(size_t)q]);
   HIPCHK(hipMemcpyAsync(h->iscal.p, h->h_iscal, icnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
   memcpy(c.h_is[0], h->h_iscal, icnt * sizeof(int)); memcpy(c.h_is[1], h->h_iscal, icnt * sizeof(int));      // the host images advance_kernel writes
   if (!c.stop.p && (rc = c.stop.alloc(4))) return rc;
