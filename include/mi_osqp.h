@@ -614,6 +614,52 @@ int mi_gomp_scene_create_tilts(mi_gomp_scene **out, mi_osqp_batch *h, int64_t di
                                int64_t n_lines, const mi_gomp_line *lines, int64_t n_capsules, const mi_gomp_capsule *capsules,
                                int64_t n_cuboids, const mi_gomp_cuboid *cuboids, int64_t n_pairs, const mi_gomp_pair *pairs,
                                int64_t n_tilts, const mi_gomp_tilt *tilts, const double *con_lo, const double *con_hi);
+/* A distance grid: a sensed world.  A box of n[0] x n[1] x n[2] nodes (each n[k] >= 2) of spacing cell > 0 on all axes,
+ * axis-aligned in the world, node (0,0,0) at `origin`; each node holds a finite distance to the nearest surface, positive in
+ * free space, negative inside material, possibly truncated; the x index is fastest: V[(iz * n[1] + iy) * n[0] + ix].  Host
+ * twin: DistanceGrid in include/mi_osqp/gomp.hpp.  inv_cell = 1 / cell is taken once on the host, in fp64, when the scene is
+ * created.  For a ball with centre p = fk(q_w), radius r and 3 x D position Jacobian J, in this order of operations:
+ *   f_k = (p_k - origin_k) * inv_cell                                   k = 0, 1, 2
+ *   inside  <=>  for every k:  f_k >= 0  and  f_k <= n_k - 1             (written so that a NaN is outside)
+ *   outside:  the grid says nothing: g = 0 (the zeros are written), l = -1e30, u = +1e30, the verdict is not touched
+ *   inside:   i_k = min(n_k - 2, (int) floor(f_k));   t_k = f_k - i_k     (0 <= t_k <= 1; a point on a cell face belongs to the
+ *                                                                          upper cell, the last node to the last cell with t = 1)
+ *     v_abc = V at node (i_0 + a, i_1 + b, i_2 + c),  a, b, c in {0, 1}
+ *     e_bc  = v_1bc - v_0bc;          x_bc = v_0bc + t_0 * e_bc          (along x: 4 differences, 4 values)
+ *     ey_c  = x_1c - x_0c;            y_c  = x_0c + t_1 * ey_c           (along y, of the values)
+ *     ex_c  = e_0c + t_1 * (e_1c - e_0c)                                 (along y, of the x differences)
+ *     phi   = y_0 + t_2 * (y_1 - y_0)
+ *     G_x   = (ex_0 + t_2 * (ex_1 - ex_0)) * inv_cell
+ *     G_y   = (ey_0 + t_2 * (ey_1 - ey_0)) * inv_cell
+ *     G_z   = (y_1 - y_0) * inv_cell
+ *     reach = offset + r;   s = phi - reach
+ *     g_j   = G_x J[x][j] + G_y J[y][j] + G_z J[z][j]                    written whether the row is active or not
+ *     s < margin:  l = (reach - phi) + sum_j g_j q_w[j],  u = +1e30       otherwise l = -1e30, u = +1e30
+ *     accepted only if s >= -1e-3
+ * G is the exact gradient of the trilinear interpolant inside the cell and is deliberately not normalised: the row is the exact
+ * linearisation of phi(p(q)) - reach >= 0.  Where G = 0 (a flat, truncated region) the row is all zeros; such a row that is
+ * active with s < 0 makes its QP primal infeasible: start outside the material, and truncate no lower than the margin.
+ * offset >= 0 inflates the obstacles; margin >= 0 has the capsule's meaning. */
+typedef struct { double origin[3]; double cell; int32_t n[3]; int32_t reserved; double offset; double margin;
+                 const double *values; } mi_gomp_grid;   /* 72 bytes; values: host memory, copied at creation */
+/* mi_gomp_scene_create_tilts with distance grids besides.  Inside the block of a (ball, waypoint) pair the grids' rows follow
+ * the cuboids', in the order given: a ball's block is (gripper ? 3 : 0) + n_lines + n_capsules + n_cuboids + n_grids rows per
+ * waypoint; the pair rows and then the tilt rows follow the last block.  n_grids == 0: exactly mi_gomp_scene_create_tilts.
+ * Refused on the host, before any device call, with *out = NULL, the handle usable and the reason in mi_osqp_last_error()
+ * naming the grid's index: n_grids > 0 without grids, a grid without values (MI_OSQP_ERR_NULL); n_grids < 0, an n[k] outside
+ * 2 .. 1024 or more than 2^24 values, a cell, offset or margin that is not finite, cell <= 0, a negative offset or margin, an
+ * origin that is not finite, a value that is not finite (the message names the first such node), a constraint matrix that
+ * does not hold the rows (MI_OSQP_ERR_INVALID_DATA). */
+int mi_gomp_scene_create_grids(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
+        int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
+        int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
+        int64_t n_pairs, const mi_gomp_pair *pairs, int64_t n_tilts, const mi_gomp_tilt *tilts,
+        int64_t n_grids, const mi_gomp_grid *grids, const double *con_lo, const double *con_hi);
+/* New values of the same shape for grid k of the scene (a new camera frame without a new scene), copied on the handle's
+ * stream.  Kept rows are not touched: the next mi_gomp_assemble_some / mi_gomp_relinearise_some sees the new values.  Refused,
+ * with nothing changed: no scene or no values (MI_OSQP_ERR_NULL); a scene without grids, k outside 0 .. n_grids - 1, a value
+ * that is not finite (MI_OSQP_ERR_INVALID_DATA). */
+int mi_gomp_scene_update_grid(mi_gomp_scene *sc, int64_t k, const double *values);
 void mi_gomp_scene_free(mi_gomp_scene *sc);          /* before mi_osqp_batch_free of its handle; one scene per handle */
 /* While a scene exists, mi_osqp_batch_reinit_some / _update_A_bounds_some of its handle also keep the QPs' raw constraint
  * data (as ConstraintBuilder::build() produced it) in the scene, so nothing extra is needed when a trajectory enters the

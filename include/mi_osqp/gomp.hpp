@@ -10,6 +10,7 @@
 //   CuboidObstacle           not in the reference: an oriented box, optionally rounded (bin walls and floors, table tops, shelves)
 //   BallPair                 not in the reference: two balls of the robot that must stay apart (self-collision)
 //   TiltLimit                not in the reference: an axis of the robot that must stay within an angle of a world direction
+//   DistanceGrid             not in the reference: a sensed world, a voxel grid of distances to the nearest surface
 //   GOMPSolver<N>            [REF] src/gomp-solver.h:13-201
 //
 // Same names, argument meaning, row layout and control flow as the reference (the known-answer
@@ -278,6 +279,88 @@ inline bool cuboidsClear(const std::vector<CuboidObstacle> &cuboids, const Point
   return res;
 }
 
+// ------------------------------------------------------------- distance grids: a sensed world (not in the reference)
+// A box of n[0] x n[1] x n[2] nodes of spacing `cell`, axis-aligned in the world, node (0,0,0) at `origin`, each node holding
+// the distance to the nearest surface (positive: free space, negative: inside material, possibly truncated), the x index
+// fastest (mi_gomp_grid is its device twin, include/mi_osqp.h has the formulas in the order both sides compute them).  A ball
+// keeps phi(P) - (offset + ball.radius) >= 0 with phi the trilinear interpolant; its row is the exact gradient of phi in the
+// cell, NOT normalised, times the Jacobian.  Outside the box the grid says nothing.  Where the gradient vanishes (a flat,
+// truncated region) the row is all zeros; active with phi below the reach its QP is primal infeasible - start outside the
+// material, and truncate no lower than the margin.  The values are shared: copying a grid copies a pointer.
+class DistanceGrid {
+ public:
+  using Values = std::shared_ptr<const std::vector<double>>;
+  DistanceGrid(const Point &origin_, double cell_, const std::array<int, 3> &n_, Values values_, double offset_ = 0.0, double margin_ = 0.0)
+      : origin(origin_), cell(cell_), n(n_), offset(offset_), margin(margin_), values(std::move(values_)) {
+    assert(cell > 0.0 && n[0] >= 2 && n[1] >= 2 && n[2] >= 2 && offset >= 0.0 && margin >= 0.0);
+    assert(values && values->size() == (size_t)n[0] * (size_t)n[1] * (size_t)n[2]);
+  }
+  DistanceGrid(const Point &origin_, double cell_, const std::array<int, 3> &n_, std::vector<double> values_, double offset_ = 0.0, double margin_ = 0.0)
+      : DistanceGrid(origin_, cell_, n_, std::make_shared<const std::vector<double>>(std::move(values_)), offset_, margin_) {}
+  // every node gets the minimum of the primitives' exact signed distances (their radii included)
+  static DistanceGrid fromObstacles(const Point &origin, double cell, const std::array<int, 3> &n, const std::vector<CapsuleObstacle> &capsules,
+                                    const std::vector<CuboidObstacle> &cuboids, double offset = 0.0, double margin = 0.0) {
+    std::vector<double> v((size_t)n[0] * (size_t)n[1] * (size_t)n[2]);
+    for (int iz = 0; iz < n[2]; ++iz)
+      for (int iy = 0; iy < n[1]; ++iy)
+        for (int ix = 0; ix < n[0]; ++ix) {
+          const Point P{origin[0] + ix * cell, origin[1] + iy * cell, origin[2] + iz * cell};
+          double d = INF;
+          for (const CapsuleObstacle &c : capsules) d = std::fmin(d, c.distance(P) - c.radius);
+          for (const CuboidObstacle &c : cuboids) d = std::fmin(d, c.signedDistance(P) - c.radius);
+          v[((size_t)iz * (size_t)n[1] + (size_t)iy) * (size_t)n[0] + (size_t)ix] = d;
+        }
+    return DistanceGrid(origin, cell, n, std::move(v), offset, margin);
+  }
+  Point origin;
+  double cell;
+  std::array<int, 3> n;
+  double offset, margin;
+  Values values;
+  double invCell() const { return 1.0 / cell; }
+  struct Sample { bool inside; double phi; Point grad; };
+  Sample sample(const Point &P) const {
+    const double inv = invCell();
+    double f[3];
+    bool inside = true;
+    for (size_t k = 0; k < 3; ++k) {
+      f[k] = (P[k] - origin[k]) * inv;
+      if (!(f[k] >= 0.0 && f[k] <= (double)(n[k] - 1))) inside = false;      // (a NaN is outside)
+    }
+    if (!inside) return {false, 0.0, {0.0, 0.0, 0.0}};
+    size_t i[3];
+    double t[3];
+    for (size_t k = 0; k < 3; ++k) {
+      const int ik = std::max(0, std::min(n[k] - 2, (int)std::floor(f[k])));
+      i[k] = (size_t)ik;
+      t[k] = f[k] - (double)ik;
+    }
+    const size_t sy = (size_t)n[0], sz = (size_t)n[0] * (size_t)n[1];
+    const double *v = values->data() + (i[2] * sz + i[1] * sy + i[0]);
+    const double v000 = v[0], v100 = v[1], v010 = v[sy], v110 = v[sy + 1], v001 = v[sz], v101 = v[sz + 1], v011 = v[sz + sy], v111 = v[sz + sy + 1];
+    const double e00 = v100 - v000, e10 = v110 - v010, e01 = v101 - v001, e11 = v111 - v011;
+    const double x00 = v000 + t[0] * e00, x10 = v010 + t[0] * e10, x01 = v001 + t[0] * e01, x11 = v011 + t[0] * e11;
+    const double ey0 = x10 - x00, ey1 = x11 - x01;
+    const double y0 = x00 + t[1] * ey0, y1 = x01 + t[1] * ey1;
+    const double ex0 = e00 + t[1] * (e10 - e00), ex1 = e01 + t[1] * (e11 - e01);
+    return {true, y0 + t[2] * (y1 - y0), {(ex0 + t[2] * (ex1 - ex0)) * inv, (ey0 + t[2] * (ey1 - ey0)) * inv, (y1 - y0) * inv}};
+  }
+  // phi - (offset + ball.radius); +INF outside the box: the grid says nothing there
+  double clearance(const Point &P, const RobotBall &ball) const {
+    const Sample s = sample(P);
+    return s.inside ? s.phi - (offset + ball.radius) : INF;
+  }
+  bool operator==(const DistanceGrid &o) const {
+    return origin == o.origin && cell == o.cell && n == o.n && offset == o.offset && margin == o.margin && (values == o.values || *values == *o.values);
+  }
+};
+// the grid part of isSolutionOK, for one ball at one waypoint (shared by the three drivers)
+inline bool gridsClear(const std::vector<DistanceGrid> &grids, const Point &P, const RobotBall &ball) {
+  bool res = true;
+  for (const DistanceGrid &gr : grids) if (!(gr.clearance(P, ball) >= -ERROR)) res = false;
+  return res;
+}
+
 // ------------------------------------------------------------- ball pairs: self-collision (not in the reference)
 // Balls a and b of the planner's ball list must keep |p_a - p_b| - (r_a + r_b) >= 0 (mi_gomp_pair is its device twin,
 // include/mi_osqp.h has the formulas).  The row of a (pair, waypoint) is the linearisation of that clearance in the joints,
@@ -364,30 +447,31 @@ bool tiltsOKAlong(const std::vector<TiltLimit> &tilts, const QPVector &trajector
 
 // ------------------------------------------------------------- constraint-builder.h
 // Rows: (W-1)*D velocity<->position links, then per variable boxes (positions W*D, velocities
-// (W-1)*D, accelerations (W-2)*D), then D*W*(3 + (|obstacles| + |capsules| + |cuboids|)*|balls|) rows for the linearised
+// (W-1)*D, accelerations (W-2)*D), then D*W*(3 + (|obstacles| + |capsules| + |cuboids| + |grids|)*|balls|) rows for the linearised
 // end-effector / obstacle constraints (allocated even when unused: bounds +-INF), then W*(|pairs| + |tilts|) rows more.  The
-// populated 3-D rows come first: the blocks of the (ball, waypoint) pairs, then the ball pairs' rows, pair-major, then the
-// tilt limits' rows, tilt-major.
+// populated 3-D rows come first: the blocks of the (ball, waypoint) pairs (work-space rows of a gripper ball, lines, capsules,
+// cuboids, grids), then the ball pairs' rows, pair-major, then the tilt limits' rows, tilt-major.
 template <size_t N_DIM>
 class ConstraintBuilder {
   using OptPair = std::pair<std::optional<double>, std::optional<double>>;
 
  public:
   ConstraintBuilder(size_t waypoints, std::vector<RobotBall> m, std::vector<HorizontalLine> obstacles, std::vector<CapsuleObstacle> capsules = {},
-                    std::vector<CuboidObstacle> cuboids = {}, std::vector<BallPair> pairs = {}, std::vector<TiltLimit> tilts = {})
+                    std::vector<CuboidObstacle> cuboids = {}, std::vector<BallPair> pairs = {}, std::vector<TiltLimit> tilts = {},
+                    std::vector<DistanceGrid> grids = {})
       : W_(waypoints), balls_(std::move(m)), lines_(std::move(obstacles)), capsules_(std::move(capsules)), cuboids_(std::move(cuboids)),
-        pairs_(std::move(pairs)), tilts_(std::move(tilts)) {
+        pairs_(std::move(pairs)), tilts_(std::move(tilts)), grids_(std::move(grids)) {
     for ([[maybe_unused]] const TiltLimit &t : tilts_) assert(t.axis && t.max_angle > 0.0 && t.max_angle < M_PI && t.margin >= 0.0);
     for ([[maybe_unused]] const BallPair &pr : pairs_) assert(pr.a < balls_.size() && pr.b < balls_.size() && pr.a != pr.b && pr.margin >= 0.0);
-    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size() + cuboids_.size()) + pairs_.size() + tilts_.size()));
-    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size()) + W_ * (pairs_.size() + tilts_.size())); up_.reserve(lo_.capacity());
+    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size() + cuboids_.size() + grids_.size()) + pairs_.size() + tilts_.size()));
+    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size() + cuboids_.size() + grids_.size()) * balls_.size()) + W_ * (pairs_.size() + tilts_.size())); up_.reserve(lo_.capacity());
     for (size_t t = 0; t + 1 < W_; ++t)                      // v_t - q_{t+1} + q_t = 0
       for (size_t j = 0; j < N_DIM; ++j) {
         lo_.push_back(-INF); up_.push_back(INF);
         put(lo_.size() - 1, {{nthVelocity(t) + j, 1.0}, {nthPos(t + 1) + j, -1.0}, {nthPos(t) + j, 1.0}}, {0.0, 0.0});
       }
     user_off_ = lo_.size();
-    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size() + cuboids_.size()) * balls_.size())) + W_ * (pairs_.size() + tilts_.size());
+    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size() + cuboids_.size() + grids_.size()) * balls_.size())) + W_ * (pairs_.size() + tilts_.size());
     lo_.resize(user_off_ + extra, -INF);
     up_.resize(user_off_ + extra, INF);
   }
@@ -441,6 +525,7 @@ class ConstraintBuilder {
         }
         for (const CapsuleObstacle &cap : capsules_) capsuleRow(row++, ball, cap, p, J, q, w);
         for (const CuboidObstacle &cub : cuboids_) cuboidRow(row++, ball, cub, p, J, q, w);
+        for (const DistanceGrid &gr : grids_) gridRow(row++, ball, gr, p, J, q, w);
       }
     }
     for (const BallPair &pr : pairs_)                            // behind the block of the last ball, pair-major
@@ -458,7 +543,7 @@ class ConstraintBuilder {
     for (const RobotBall &ball : balls_)
       for (size_t w = 0; w < W_; ++w) {
         if (ball.is_gripper) for (Axis axis : XYZ_AXES) axisRow(row++, ball, axis, J, w, -INF, INF);
-        for (size_t k = 0; k < lines_.size() + capsules_.size() + cuboids_.size(); ++k) axisRow(row++, ball, Z, J, w, -INF, INF);
+        for (size_t k = 0; k < lines_.size() + capsules_.size() + cuboids_.size() + grids_.size(); ++k) axisRow(row++, ball, Z, J, w, -INF, INF);
       }
     for (size_t k = 0; k < pairs_.size() + tilts_.size(); ++k)
       for (size_t w = 0; w < W_; ++w, ++row) {
@@ -494,6 +579,7 @@ class ConstraintBuilder {
   std::vector<CuboidObstacle> cuboids_;
   std::vector<BallPair> pairs_;
   std::vector<TiltLimit> tilts_;
+  std::vector<DistanceGrid> grids_;
   // (col, row) -> value, last write wins ([REF] constraint-builder.h:129).  A write log that is sorted into CSC
   // order and de-duplicated on demand: the builder runs once per trajectory, segment and re-linearisation,
   // and a std::map made it the bottleneck of the batched driver.
@@ -596,6 +682,21 @@ class ConstraintBuilder {
       gq += g * q[j];
     }
     lo_[row] = sd - reach < cub.margin ? (reach - sd) + gq : -INF;
+    up_[row] = INF;
+  }
+  // G' J with G the gradient of the grid's interpolant at p (DistanceGrid::sample), not normalised, written whether the row is
+  // active or not; active within `margin`: (offset + r) - phi + (G' J) q <= (G' J) x.  Outside the box: a zero row, no bounds
+  void gridRow(size_t row, const RobotBall &ball, const DistanceGrid &gr, const Point &p, const std::array<double, 3 * N_DIM> &J,
+               const Vec<N_DIM> &q, size_t waypoint) {
+    const DistanceGrid::Sample sm = gr.sample(p);
+    const double reach = gr.offset + ball.radius;
+    double gq = 0.0;
+    for (size_t j = 0; j < N_DIM; ++j) {
+      const double g = sm.inside ? sm.grad[0] * J[0 * N_DIM + j] + sm.grad[1] * J[1 * N_DIM + j] + sm.grad[2] * J[2 * N_DIM + j] : 0.0;
+      set(nthPos(waypoint) + j, row, g);
+      gq += g * q[j];
+    }
+    lo_[row] = sm.inside && sm.phi - reach < gr.margin ? (reach - sm.phi) + gq : -INF;
     up_[row] = INF;
   }
   // n' J_a - n' J_b with n = (p_a - p_b) / |p_a - p_b| (+Z when the centres coincide), written whether the row is active or
@@ -728,6 +829,8 @@ class GOMPSolver {
   std::vector<BallPair> pairs;
   // Tilt limits: axes of the arm that must stay within an angle of a world direction (dhTilt of dh_kinematics.hpp makes them); set before run()
   std::vector<TiltLimit> tilts;
+  // Distance grids: a sensed world, sampled trilinearly (DistanceGrid::fromObstacles makes one from primitives); set before run()
+  std::vector<DistanceGrid> grids;
   // (tests) the acceptance test that ends the SQP loop
   bool acceptable(const QPVector &q_trajectory) const { return isSolutionOK(q_trajectory); }
 
@@ -756,7 +859,7 @@ class GOMPSolver {
   }
   ConstraintBuilder<N_DIM> jointSpaceRows(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
     assert(waypoints >= 4);
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts, grids};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -786,6 +889,7 @@ class GOMPSolver {
           if (line.hasCollision(w, xyz, ball) && !line.isAbove(p, ball)) res = false;
         if (!capsulesClear(capsules, p, ball)) res = false;
         if (!cuboidsClear(cuboids, p, ball)) res = false;
+        if (!gridsClear(grids, p, ball)) res = false;
       }
     }
     if (!pairsClearAlong<N_DIM>(pairs, mappers, q_trajectory)) res = false;
@@ -921,6 +1025,7 @@ class BatchGOMPSolver {
   std::vector<CuboidObstacle> cuboids;        // cuboid obstacles (oriented boxes); set before run()
   std::vector<BallPair> pairs;                // self-collision pairs of the balls; set before run()
   std::vector<TiltLimit> tilts;               // tilt limits; set before run()
+  std::vector<DistanceGrid> grids;            // distance grids; set before run()
   int solver_reuses = 0;          // how often a kept solver was re-initialised instead of a new one being built
   // where the wall time of the last run() went: building constraints, QP setup (analysis + upload + factorisation),
   // batched solves, feasibility checks + re-linearisation + update
@@ -954,7 +1059,7 @@ class BatchGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts, grids};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -984,6 +1089,7 @@ class BatchGOMPSolver {
           if (line.hasCollision(w, xyz, ball) && !line.isAbove(p, ball)) res = false;
         if (!capsulesClear(capsules, p, ball)) res = false;
         if (!cuboidsClear(cuboids, p, ball)) res = false;
+        if (!gridsClear(grids, p, ball)) res = false;
       }
     }
     if (!pairsClearAlong<N_DIM>(pairs, mappers, q_trajectory)) res = false;
@@ -1019,12 +1125,13 @@ class ContinuousGOMPSolver {
     const size_t B = starts.size();
     assert(ends.size() == B && B > 0);
     starts_ = &starts; ends_ = &ends;
-    if (!(capsules == scene_capsules_ && cuboids == scene_cuboids_ && pairs == scene_pairs_ && tilts == scene_tilts_)) {   // the kept scenes hold the capsules, cuboids, pairs and tilt limits of the run that made them
+    if (!(capsules == scene_capsules_ && cuboids == scene_cuboids_ && pairs == scene_pairs_ && tilts == scene_tilts_ && grids == scene_grids_)) {   // the kept scenes hold the capsules, cuboids, pairs and tilt limits of the run that made them
       for (Stage &st : stages_) if (st.scene) { mi_gomp_scene_free(st.scene); st.scene = nullptr; }
       scene_capsules_ = capsules;
       scene_cuboids_ = cuboids;
       scene_pairs_ = pairs;
       scene_tilts_ = tilts;
+      scene_grids_ = grids;
     }
     traj_.clear(); traj_.resize(B);
     segments_run.assign(B, 0); qp_solves.assign(B, 0); qp_updates.assign(B, 0);
@@ -1077,6 +1184,21 @@ class ContinuousGOMPSolver {
   // Tilt limits; set before run().  On the device path they go into the scene (mi_gomp_scene_create_tilts), which needs
   // dh_chain and limits made by dhTilt (builtin_frame set).
   std::vector<TiltLimit> tilts;
+  // Distance grids; set before run().  On the device path they go into the scene (mi_gomp_scene_create_grids).
+  std::vector<DistanceGrid> grids;
+  // A new camera frame for grid k: new values of the same shape, on the host copy and in every kept device scene; between
+  // run() calls.  false when k or the number of values is wrong, or a device scene refuses them.
+  bool updateGrid(size_t k, std::vector<double> values) {
+    if (k >= grids.size() || values.size() != grids[k].values->size()) return false;
+    bool res = true;
+    if (k < scene_grids_.size() && grids[k] == scene_grids_[k])
+      for (Stage &st : stages_)
+        if (st.scene && mi_gomp_scene_update_grid(st.scene, (int64_t)k, values.data()) != MI_OSQP_OK) res = false;
+    if (!res) return false;
+    grids[k].values = std::make_shared<const std::vector<double>>(std::move(values));
+    if (k < scene_grids_.size()) scene_grids_[k].values = grids[k].values;
+    return true;
+  }
   int pipeline_depth = 1;              // 2: a stage enqueues its next advance before it looks at the previous one's results
   int segments_per_advance = 4;        // a launch runs on until a QP of the stage finishes, at most that many segments
   // per stage: {waypoints, advances, seconds admitting, waiting for the device, processing finished QPs, idle}
@@ -1122,6 +1244,7 @@ class ContinuousGOMPSolver {
   std::vector<CuboidObstacle> scene_cuboids_;
   std::vector<BallPair> scene_pairs_;
   std::vector<TiltLimit> scene_tilts_;
+  std::vector<DistanceGrid> scene_grids_;
   const std::vector<Ctrl<N_DIM>> *starts_ = nullptr, *ends_ = nullptr;
   std::atomic<size_t> finished_{0};
   std::atomic<bool> failed_{false};
@@ -1251,7 +1374,18 @@ class ContinuousGOMPSolver {
       g.max_angle = t.max_angle; g.margin = t.margin;
       tls.push_back(g);
     }
-    const int rc = !tls.empty() ? mi_gomp_scene_create_tilts(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+    std::vector<mi_gomp_grid> grs;
+    for (const DistanceGrid &d : grids) {
+      mi_gomp_grid g{};
+      for (int k = 0; k < 3; k++) { g.origin[k] = d.origin[k]; g.n[k] = (int32_t)d.n[k]; }
+      g.cell = d.cell; g.offset = d.offset; g.margin = d.margin; g.values = d.values->data();
+      grs.push_back(g);
+    }
+    const int rc = !grs.empty() ? mi_gomp_scene_create_grids(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+                                                              (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(),
+                                                              (int64_t)cubs.size(), cubs.data(), (int64_t)prs.size(), prs.data(), (int64_t)tls.size(), tls.data(),
+                                                              (int64_t)grs.size(), grs.data(), lo, hi)
+                   : !tls.empty() ? mi_gomp_scene_create_tilts(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
                                                               (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(),
                                                               (int64_t)cubs.size(), cubs.data(), (int64_t)prs.size(), prs.data(), (int64_t)tls.size(), tls.data(), lo, hi)
                    : !prs.empty() ? mi_gomp_scene_create_pairs(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
@@ -1344,7 +1478,7 @@ class ContinuousGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts, grids};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
         .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
@@ -1374,6 +1508,7 @@ class ContinuousGOMPSolver {
           if (line.hasCollision(w, xyz, ball) && !line.isAbove(p, ball)) res = false;
         if (!capsulesClear(capsules, p, ball)) res = false;
         if (!cuboidsClear(cuboids, p, ball)) res = false;
+        if (!gridsClear(grids, p, ball)) res = false;
       }
     }
     if (!pairsClearAlong<N_DIM>(pairs, mappers, q_trajectory)) res = false;

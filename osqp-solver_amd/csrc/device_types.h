@@ -293,9 +293,14 @@ struct GompPairDev { int a, b; double margin; };
 // the three cosines are taken once on the host: cos_lim the limit, cos_act where the row starts to constrain, cos_ok what
 // the acceptance test allows
 struct GompTiltDev { int frame, pad; double axis[3], ref[3], cos_lim, cos_act, cos_ok; };
+// a distance grid (mi_gomp_grid): n[0] x n[1] x n[2] nodes of spacing 1 / inv_cell, node (0,0,0) at `origin`, the x index
+// fastest: V[iz sz + iy sy + ix] with sy = n[0], sz = n[0] n[1]; `values` points into the scene's one buffer of all grids' nodes
+struct GompGridDev { double origin[3], inv_cell; int n[3], sy, sz, pad; double offset, margin; const double *values; };
 struct GompArgs {
   int dims, W, n_balls, n_lines, n, m, nnzA, n_ids, row0, write_rows;
   int n_caps, n_cuboids;
+  int n_grids, grid_pad;         // their rows follow the cuboids' in every (ball, waypoint) block
+  const GompGridDev *grids;      // [n_grids]
   int n_pairs, pair_row0;        // pair_row0: the first pair row = row0 + the rows of all (ball, waypoint) blocks
   int n_tilts, tilt_row0;        // tilt_row0: the first tilt row = pair_row0 + W n_pairs
   const int *ids;                // the listed QPs

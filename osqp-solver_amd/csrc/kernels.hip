@@ -3891,7 +3891,8 @@ hipError_t launch_ruiz(const RuizArgs &a, hipStream_t st) {
 // line's vertical plane at that waypoint (HorizontalLine::hasCollision: close to it, or on opposite sides of it from a
 // neighbouring waypoint), a dummy row otherwise - and the trajectory is accepted when every ball respects the box and is above
 // (below) the lines it collides with.  Every (ball, capsule) pair gets one row after the lines' (see the loop over g.caps) and
-// must keep a clearance of -1e-3 or more; every (ball, cuboid) pair one row after the capsules', by the same rule.  One
+// must keep a clearance of -1e-3 or more; every (ball, cuboid) pair one row after the capsules', by the same rule; every
+// (ball, distance grid) pair one row after the cuboids', the gradient of the trilinear interpolant of the grid's nodes.  One
 // workgroup per trajectory, one thread per (ball, waypoint); behind those items one thread per (ball pair, waypoint): one row
 // each behind the block of the last ball, the same rule on the distance of the two centres; behind those one thread per (tilt
 // limit, waypoint): one row each behind the pair rows, the gradient of the cosine between an axis of the chain and a world
@@ -4027,11 +4028,45 @@ __device__ __forceinline__ void gomp_dist_xy(const GompLineDev &ln, const double
   for (int k = 0; k < 3; k++) t += (P[k] - ln.A[k]) * ln.D[k];
   dxy[0] = ln.A[0] + t * ln.D[0] - P[0]; dxy[1] = ln.A[1] + t * ln.D[1] - P[1];
 }
+// One distance grid at the point p (formulas and their order at mi_gomp_grid): true when p lies in the box of the nodes, then
+// phi = the trilinear interpolant and, with `grad`, (G0, G1, G2) = its gradient inside the cell.
+// ADDRESS SAFETY.  A lane reads eight nodes at base + {0, 1} + {0, sy} + {0, sz}, base = (i2 sz + i1 sy + i0), and every
+// i_k is in [0, n_k - 2] for EVERY lane, whatever its p:
+//   1. `inside` is a chain of >= and <= on f_k: a NaN fails it, +-inf and 1e300 fail it;
+//   2. the cell index is formed from h_k = inside ? f_k : 0, a number in [0, n_k - 1] - never from an unchecked f_k, so the
+//      conversion to int is always defined;
+//   3. it is then clamped to [0, n_k - 2] in integer arithmetic all the same;
+//   4. the offset is a size_t product of numbers below 2^24 (the host refuses larger grids).
+// A lane outside reads cell (0, 0, 0) and discards what it read: no divergence around the gather.  The eight addresses are a
+// base and three strides, never an indexed local array (that would live in scratch).
+__device__ __forceinline__ bool gomp_grid_sample(const GompGridDev &gd, const double *p, bool grad, double &phi, double &G0, double &G1, double &G2) {
+  const double f0 = (p[0] - gd.origin[0]) * gd.inv_cell, f1 = (p[1] - gd.origin[1]) * gd.inv_cell, f2 = (p[2] - gd.origin[2]) * gd.inv_cell;
+  const bool inside = f0 >= 0.0 && f0 <= (double)(gd.n[0] - 1) && f1 >= 0.0 && f1 <= (double)(gd.n[1] - 1) && f2 >= 0.0 && f2 <= (double)(gd.n[2] - 1);
+  const double h0 = inside ? f0 : 0.0, h1 = inside ? f1 : 0.0, h2 = inside ? f2 : 0.0;
+  const int i0 = max(0, min(gd.n[0] - 2, (int)floor(h0))), i1 = max(0, min(gd.n[1] - 2, (int)floor(h1))), i2 = max(0, min(gd.n[2] - 2, (int)floor(h2)));
+  const double t0 = h0 - (double)i0, t1 = h1 - (double)i1, t2 = h2 - (double)i2;
+  const size_t sy = (size_t)gd.sy, sz = (size_t)gd.sz;
+  const double *v = gd.values + ((size_t)i2 * sz + (size_t)i1 * sy + (size_t)i0);
+  const double v000 = __ldg(v), v100 = __ldg(v + 1), v010 = __ldg(v + sy), v110 = __ldg(v + sy + 1);
+  const double v001 = __ldg(v + sz), v101 = __ldg(v + sz + 1), v011 = __ldg(v + sz + sy), v111 = __ldg(v + sz + sy + 1);
+  const double e00 = v100 - v000, e10 = v110 - v010, e01 = v101 - v001, e11 = v111 - v011;   // e_bc: along x
+  const double x00 = v000 + t0 * e00, x10 = v010 + t0 * e10, x01 = v001 + t0 * e01, x11 = v011 + t0 * e11;
+  const double ey0 = x10 - x00, ey1 = x11 - x01;                                               // along y, of the values
+  const double y0 = x00 + t1 * ey0, y1 = x01 + t1 * ey1;
+  phi = y0 + t2 * (y1 - y0);
+  if (grad) {
+    const double ex0 = e00 + t1 * (e10 - e00), ex1 = e01 + t1 * (e11 - e01);                   // along y, of the x differences
+    G0 = (ex0 + t2 * (ex1 - ex0)) * gd.inv_cell;
+    G1 = (ey0 + t2 * (ey1 - ey0)) * gd.inv_cell;
+    G2 = (y1 - y0) * gd.inv_cell;
+  } else G0 = G1 = G2 = 0.0;
+  return inside;
+}
 __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
   extern __shared__ double smem[];                 // xyz[n_balls][W][3]
   __shared__ int s_ok;
   const int jq = blockIdx.x, qp = g.ids[jq], tid = threadIdx.x;
-  const int D = g.dims, W = g.W, NB = g.n_balls, NL = g.n_lines, NC = g.n_caps, NX = g.n_cuboids;
+  const int D = g.dims, W = g.W, NB = g.n_balls, NL = g.n_lines, NC = g.n_caps, NX = g.n_cuboids, NG = g.n_grids;
   const double *traj = g.traj + (size_t)jq * g.n;
   if (tid == 0) s_ok = 1;
   double p[3] = {0, 0, 0}, J[3 * MI_GOMP_MAXD], q[MI_GOMP_MAXD];
@@ -4064,8 +4099,8 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
     for (int ax = 0; ax < 3; ax++) { double sacc = 0.0; for (int j = 0; j < D; j++) sacc += J[ax * D + j] * q[j]; Jq[ax] = sacc; }
     // this pair's first row: the balls before it (all their waypoints), then the waypoints before it of this ball
     int row = g.row0;
-    for (int b2 = 0; b2 < bi; b2++) row += W * ((g.balls[b2].is_gripper ? 3 : 0) + NL + NC + NX);
-    row += w * ((ball.is_gripper ? 3 : 0) + NL + NC + NX);
+    for (int b2 = 0; b2 < bi; b2++) row += W * ((g.balls[b2].is_gripper ? 3 : 0) + NL + NC + NX + NG);
+    row += w * ((ball.is_gripper ? 3 : 0) + NL + NC + NX + NG);
     auto put = [&](int r, int axis, double low, double upp) {
       if (!wr) return;
       const int *ai = g.aidx + (size_t)(r - g.row0) * D;
@@ -4157,6 +4192,29 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
         gq += gj * q[j];
       }
       g.l[(size_t)qp * g.m + row] = s < cb.margin ? (reach - sd) + gq : -MI_INFTY;
+      g.u[(size_t)qp * g.m + row] = MI_INFTY;
+    }
+    // distance grids (DistanceGrid of gomp.hpp, formulas at mi_gomp_grid): the trilinear interpolant of the nodes' distances
+    // and its exact gradient in the cell.  The descriptor is the same for every lane (scalar loads); the eight corners are a
+    // per-lane gather (gomp_grid_sample).  A ball outside the box, or at a coordinate that is not finite, gets a zero row
+    // without bounds and no say in the verdict.  The verdict pass needs phi only, the row pass the gradient too.
+#pragma unroll 1
+    for (int gi = 0; gi < NG; gi++, row++) {
+      const GompGridDev &gd = g.grids[gi];
+      double phi, G0, G1, G2;
+      const bool inside = gomp_grid_sample(gd, p, wr, phi, G0, G1, G2);
+      const double reach = gd.offset + ball.radius;
+      const double s = phi - reach;
+      if (inside && !(s >= -1e-3)) ok = 0;
+      if (!wr) continue;
+      const int *ai = g.aidx + (size_t)(row - g.row0) * D;
+      double gq = 0.0;
+      for (int j = 0; j < D; j++) {
+        const double gj = inside ? G0 * J[0 * D + j] + G1 * J[1 * D + j] + G2 * J[2 * D + j] : 0.0;
+        g.A[(size_t)qp * g.nnzA + ai[j]] = gj;                                               // written for inactive rows too
+        gq += gj * q[j];
+      }
+      g.l[(size_t)qp * g.m + row] = inside && s < gd.margin ? (reach - phi) + gq : -MI_INFTY;
       g.u[(size_t)qp * g.m + row] = MI_INFTY;
     }
   }

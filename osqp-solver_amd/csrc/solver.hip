@@ -3821,7 +3821,7 @@ int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t
 // Besides the built-in models a scene may hold one DH chain (mi_gomp_chain) with balls fixed in its link frames.
 struct mi_gomp_scene {
   mi_osqp_batch *h = nullptr;
-  int dims = 0, W = 0, n_balls = 0, n_lines = 0, n_caps = 0, n_cuboids = 0, n_pairs = 0, pair_row0 = 0, n_tilts = 0, tilt_row0 = 0, row0 = 0, n_rows3d = 0;
+  int dims = 0, W = 0, n_balls = 0, n_lines = 0, n_caps = 0, n_cuboids = 0, n_pairs = 0, pair_row0 = 0, n_tilts = 0, tilt_row0 = 0, row0 = 0, n_rows3d = 0, n_grids = 0;
   double con_lo[3] = {-1e30, -1e30, -1e30}, con_hi[3] = {1e30, 1e30, 1e30};
   DevBuf<GompBallDev> balls;
   DevBuf<GompLineDev> lines;
@@ -3829,6 +3829,9 @@ struct mi_gomp_scene {
   DevBuf<GompCuboidDev> cuboids;
   DevBuf<GompPairDev> pairs;                  // their rows: pair_row0 + k W + w, behind every ball's block
   DevBuf<GompTiltDev> tilts;                  // their rows: tilt_row0 + k W + w, behind the pair rows
+  DevBuf<GompGridDev> grids;                  // distance grids: their rows follow the cuboids' in every (ball, waypoint) block
+  DevBuf<double> grid_vals;                   // the nodes of all grids, one after the other
+  std::vector<size_t> grid_off, grid_len;     // where grid k's nodes start in grid_vals and how many they are
   GompChainDev chain{};                       // the DH chain of the MI_GM_DH_CHAIN balls (n_joints 0: the scene has none)
   DevBuf<int> aidx;
   DevBuf<double> A, l, u;                     // QP-major raw rows as ConstraintBuilder::build() lays them out
@@ -3851,9 +3854,9 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
   if ((rc = ring_upload(h, sp, (size_t)nq * n * sizeof(double)))) return rc;
   hipStream_t st = h->stream;
   GompArgs g{};
-  g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n_caps = sc->n_caps; g.n_cuboids = sc->n_cuboids; g.n_pairs = sc->n_pairs; g.pair_row0 = sc->pair_row0; g.n_tilts = sc->n_tilts; g.tilt_row0 = sc->tilt_row0; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
+  g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n_caps = sc->n_caps; g.n_cuboids = sc->n_cuboids; g.n_pairs = sc->n_pairs; g.pair_row0 = sc->pair_row0; g.n_tilts = sc->n_tilts; g.tilt_row0 = sc->tilt_row0; g.n_grids = sc->n_grids; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
   g.row0 = sc->row0; g.write_rows = write_rows;
-  g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.caps = sc->caps.p; g.cuboids = sc->cuboids.p; g.pairs = sc->pairs.p; g.tilts = sc->tilts.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
+  g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.caps = sc->caps.p; g.cuboids = sc->cuboids.p; g.pairs = sc->pairs.p; g.tilts = sc->tilts.p; g.grids = sc->grids.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
   for (int k = 0; k < 3; k++) { g.con_lo[k] = sc->con_lo[k]; g.con_hi[k] = sc->con_hi[k]; }
   g.A = sc->A.p; g.l = sc->l.p; g.u = sc->u.p; g.ok = sc->h_ok;
   g.chain = sc->chain;
@@ -3866,13 +3869,25 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
 
 // mi_gomp_scene_create (chain null: model 6 is refused as it always was), mi_gomp_scene_create_chain and
 // mi_gomp_scene_create_world (capsules besides), mi_gomp_scene_create_cuboids (cuboids besides those) and
-// mi_gomp_scene_create_pairs (ball pairs besides those) and mi_gomp_scene_create_tilts (tilt limits besides those).
+// mi_gomp_scene_create_pairs (ball pairs besides those), mi_gomp_scene_create_tilts (tilt limits besides those) and
+// mi_gomp_scene_create_grids (distance grids besides those).
 // Everything that can be refused is refused here on the host, the checks that need no handle first.
+// every node of a grid is a finite number: the message names the first that is not, by its indices
+static int gomp_grid_values_finite(const std::string &who, const int32_t *n, const double *values) {
+  const size_t count = (size_t)n[0] * (size_t)n[1] * (size_t)n[2];
+  for (size_t i = 0; i < count; i++)
+    if (!std::isfinite(values[i])) {
+      g_last_error = who + ": the value of node (" + std::to_string(i % (size_t)n[0]) + ", " + std::to_string(i / (size_t)n[0] % (size_t)n[1]) + ", " +
+                     std::to_string(i / ((size_t)n[0] * (size_t)n[1])) + ") is not finite";
+      return MI_OSQP_ERR_INVALID_DATA;
+    }
+  return 0;
+}
 static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain, bool chain_entry,
                              int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                              int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
                              int64_t n_pairs, const mi_gomp_pair *pairs, int64_t n_tilts, const mi_gomp_tilt *tilts,
-                             const double *con_lo, const double *con_hi) {
+                             int64_t n_grids, const mi_gomp_grid *grids, const double *con_lo, const double *con_hi) {
   if (!out) return MI_OSQP_ERR_NULL;
   *out = nullptr;
   if ((n_balls > 0 && !balls) || (n_lines > 0 && !lines)) return MI_OSQP_ERR_NULL;
@@ -3963,6 +3978,36 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
     d.cos_act = std::cos(std::max(0.0, tl.max_angle - tl.margin));
     d.cos_ok = std::cos(std::min(M_PI, tl.max_angle + 1e-3));
   }
+  // a distance grid: shape, spacing and every node are checked here; 1 / cell is taken once, in fp64
+  if (n_grids > 0 && !grids) { g_last_error = "n_grids > 0 and no grids"; return MI_OSQP_ERR_NULL; }
+  if (n_grids < 0) { g_last_error = "n_grids is negative"; return MI_OSQP_ERR_INVALID_DATA; }
+  std::vector<GompGridDev> hgrid((size_t)(n_grids > 0 ? n_grids : 0));
+  std::vector<size_t> grid_off, grid_len;
+  size_t grid_total = 0;
+  for (int64_t k = 0; k < n_grids; k++) {
+    const mi_gomp_grid &gr = grids[k];
+    const std::string who = "grid " + std::to_string(k);
+    if (!gr.values) { g_last_error = who + " has no values"; return MI_OSQP_ERR_NULL; }
+    size_t count = 1;
+    for (int i = 0; i < 3; i++) {
+      if (gr.n[i] < 2 || gr.n[i] > 1024) { g_last_error = who + ": n[" + std::to_string(i) + "] must be 2 .. 1024"; return MI_OSQP_ERR_INVALID_DATA; }
+      count *= (size_t)gr.n[i];
+    }
+    if (count > ((size_t)1 << 24)) { g_last_error = who + " has more than 2^24 values"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (!std::isfinite(gr.cell) || !std::isfinite(gr.offset) || !std::isfinite(gr.margin)) { g_last_error = who + " has a field that is not finite"; return MI_OSQP_ERR_INVALID_DATA; }
+    for (int i = 0; i < 3; i++)
+      if (!std::isfinite(gr.origin[i])) { g_last_error = who + " has an origin that is not finite"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (!(gr.cell > 0.0)) { g_last_error = who + ": cell must be positive"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (gr.offset < 0.0 || gr.margin < 0.0) { g_last_error = who + ": offset and margin must not be negative"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (int rc = gomp_grid_values_finite(who, gr.n, gr.values)) return rc;
+    GompGridDev &d = hgrid[(size_t)k];
+    for (int i = 0; i < 3; i++) { d.origin[i] = gr.origin[i]; d.n[i] = gr.n[i]; }
+    d.inv_cell = 1.0 / gr.cell;
+    d.sy = gr.n[0]; d.sz = gr.n[0] * gr.n[1]; d.pad = 0;
+    d.offset = gr.offset; d.margin = gr.margin; d.values = nullptr;
+    grid_off.push_back(grid_total); grid_len.push_back(count);
+    grid_total += count;
+  }
   if (!h) return MI_OSQP_ERR_NULL;
   const Analysis &an = (*h->anp);
   const int D = (int)dims, W = (int)waypoints;
@@ -3974,7 +4019,7 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
   for (int b = 0; b < (int)n_balls; b++) {
     if (balls[b].model < MI_GM_UR5E_FLANGE || balls[b].model > (hc.n_joints ? MI_GM_DH_CHAIN : MI_GM_TABLE)) return MI_OSQP_ERR_INVALID_DATA;
     if ((balls[b].model <= MI_GM_UR5E_ELBOW && D != 6) || ((balls[b].model == MI_GM_YAW_2LINK || balls[b].model == MI_GM_TABLE) && D != 3)) return MI_OSQP_ERR_INVALID_DATA;
-    rows3d += W * ((balls[b].is_gripper ? 3 : 0) + (int)n_lines + (int)n_capsules + (int)n_cuboids);
+    rows3d += W * ((balls[b].is_gripper ? 3 : 0) + (int)n_lines + (int)n_capsules + (int)n_cuboids + (int)n_grids);
   }
   const int pair_row0 = row0 + rows3d;                             // the pair rows: behind the block of the last ball, pair-major
   rows3d += W * (int)n_pairs;
@@ -3983,13 +4028,22 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
   if (row0 + rows3d > an.m) {
     g_last_error = "the constraint matrix does not hold the 3-D rows of this scene";
     if (n_tilts > 0 && tilt_row0 <= an.m) g_last_error += " (tilt " + std::to_string((an.m - tilt_row0) / W) + ")";   // the first tilt without its rows
+    else if (n_grids > 0) {                                        // the first grid row the matrix lacks, if a grid row is the first
+      int r = row0;
+      for (int b = 0; b < (int)n_balls && r <= an.m; b++)
+        for (int w = 0; w < W && r <= an.m; w++) {
+          const int before = (balls[b].is_gripper ? 3 : 0) + (int)n_lines + (int)n_capsules + (int)n_cuboids;
+          if (an.m >= r + before && an.m < r + before + (int)n_grids) g_last_error += " (grid " + std::to_string(an.m - r - before) + ")";
+          r += before + (int)n_grids;
+        }
+    }
     return MI_OSQP_ERR_INVALID_DATA;
   }
   DevGuard guard(h->device);
   mi_gomp_scene *sc = new (std::nothrow) mi_gomp_scene();
   if (!sc) return MI_OSQP_ERR_ALLOC;
   std::unique_ptr<mi_gomp_scene> own(sc);
-  sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->n_caps = (int)n_capsules; sc->n_cuboids = (int)n_cuboids; sc->n_pairs = (int)n_pairs; sc->pair_row0 = pair_row0; sc->n_tilts = (int)n_tilts; sc->tilt_row0 = tilt_row0; sc->row0 = row0; sc->n_rows3d = rows3d;
+  sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->n_caps = (int)n_capsules; sc->n_cuboids = (int)n_cuboids; sc->n_pairs = (int)n_pairs; sc->pair_row0 = pair_row0; sc->n_tilts = (int)n_tilts; sc->tilt_row0 = tilt_row0; sc->row0 = row0; sc->n_rows3d = rows3d; sc->n_grids = (int)n_grids;
   sc->chain = hc;
   for (int k = 0; k < 3; k++) { sc->con_lo[k] = con_lo ? con_lo[k] : -1e30; sc->con_hi[k] = con_hi ? con_hi[k] : 1e30; }
   // where the entries of the 3-D rows sit in A's value array: row r of waypoint w holds D entries in the columns of q_w
@@ -4008,8 +4062,12 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
     };
     for (int b = 0; b < (int)n_balls; b++)
       for (int w = 0; w < W; w++)
-        for (int k = 0; k < (balls[b].is_gripper ? 3 : 0) + (int)n_lines + (int)n_capsules + (int)n_cuboids; k++, r++)
-          if (!locate(w)) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene"; return MI_OSQP_ERR_INVALID_DATA; }
+        for (int k = 0, before = (balls[b].is_gripper ? 3 : 0) + (int)n_lines + (int)n_capsules + (int)n_cuboids; k < before + (int)n_grids; k++, r++)
+          if (!locate(w)) {
+            g_last_error = "the constraint matrix does not hold the 3-D rows of this scene";
+            if (k >= before) g_last_error += " (grid " + std::to_string(k - before) + ")";
+            return MI_OSQP_ERR_INVALID_DATA;
+          }
     for (int k = 0; k < (int)n_pairs; k++)
       for (int w = 0; w < W; w++, r++)
         if (!locate(w)) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene (pair " + std::to_string(k) + ")"; return MI_OSQP_ERR_INVALID_DATA; }
@@ -4047,6 +4105,15 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
   if ((rc = sc->balls.upload(hb)) || (rc = sc->lines.upload(hl)) || (n_capsules && (rc = sc->caps.upload(hcap))) || (n_cuboids && (rc = sc->cuboids.upload(hcub))) || (n_pairs && (rc = sc->pairs.upload(hpair))) || (n_tilts && (rc = sc->tilts.upload(htilt))) ||
       (rc = sc->aidx.upload(aidx)) ||
       (rc = sc->A.alloc((size_t)h->B * std::max(an.Ap[an.n], 1))) || (rc = sc->l.alloc((size_t)h->B * std::max(an.m, 1))) || (rc = sc->u.alloc((size_t)h->B * std::max(an.m, 1)))) return rc;
+  if (n_grids > 0) {                                               // all nodes in one buffer, the descriptors (pointing into it) in a second
+    if ((rc = sc->grid_vals.alloc(grid_total))) return rc;
+    for (int k = 0; k < (int)n_grids; k++) {
+      hgrid[k].values = sc->grid_vals.p + grid_off[k];
+      HIPCHK(hipMemcpy(sc->grid_vals.p + grid_off[k], grids[k].values, grid_len[k] * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if ((rc = sc->grids.upload(hgrid))) return rc;
+    sc->grid_off = grid_off; sc->grid_len = grid_len;
+  }
   HIPCHK(hostpool::alloc((void **)&sc->h_ok, (size_t)h->B * sizeof(int), &sc->h_ok_cap));
   HIPCHK(hipEventCreateWithFlags(&sc->ev, hipEventDisableTiming));
   if (h->cont.keepA) { g_last_error = "the solver already has a scene"; return MI_OSQP_ERR_INVALID_DATA; }
@@ -4059,37 +4126,58 @@ extern "C" {
 
 int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, int64_t n_balls, const mi_gomp_ball *balls,
                          int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_chain(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_world(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                int64_t n_capsules, const mi_gomp_capsule *capsules, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_cuboids(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                  int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                  int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
                                  const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_pairs(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
                                int64_t n_pairs, const mi_gomp_pair *pairs, const double *con_lo, const double *con_hi) {
   return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids,
-                           n_pairs, pairs, 0, nullptr, con_lo, con_hi);
+                           n_pairs, pairs, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_tilts(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
                                int64_t n_pairs, const mi_gomp_pair *pairs, int64_t n_tilts, const mi_gomp_tilt *tilts,
                                const double *con_lo, const double *con_hi) {
+  return mi_gomp_scene_create_grids(out, h, dims, waypoints, chain, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids,
+                                    n_pairs, pairs, n_tilts, tilts, 0, nullptr, con_lo, con_hi);
+}
+int mi_gomp_scene_create_grids(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
+                               int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
+                               int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
+                               int64_t n_pairs, const mi_gomp_pair *pairs, int64_t n_tilts, const mi_gomp_tilt *tilts,
+                               int64_t n_grids, const mi_gomp_grid *grids, const double *con_lo, const double *con_hi) {
   return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids,
-                           n_pairs, pairs, n_tilts, tilts, con_lo, con_hi);
+                           n_pairs, pairs, n_tilts, tilts, n_grids, grids, con_lo, con_hi);
+}
+// a new camera frame: new node values of the same shape for grid k, on the handle's stream; kept rows are not touched
+int mi_gomp_scene_update_grid(mi_gomp_scene *sc, int64_t k, const double *values) {
+  if (!sc || !values) return MI_OSQP_ERR_NULL;
+  if (sc->n_grids == 0) { g_last_error = "the scene has no grids"; return MI_OSQP_ERR_INVALID_DATA; }
+  if (k < 0 || k >= sc->n_grids) { g_last_error = "grid " + std::to_string(k) + ": the scene has grids 0 .. " + std::to_string(sc->n_grids - 1); return MI_OSQP_ERR_INVALID_DATA; }
+  for (size_t i = 0; i < sc->grid_len[(size_t)k]; i++)
+    if (!std::isfinite(values[i])) { g_last_error = "grid " + std::to_string(k) + ": value " + std::to_string(i) + " is not finite"; return MI_OSQP_ERR_INVALID_DATA; }
+  mi_osqp_batch *h = sc->h;
+  DevGuard guard(h->device);
+  HIPCHK(hipMemcpyAsync(sc->grid_vals.p + sc->grid_off[(size_t)k], values, sc->grid_len[(size_t)k] * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));          // (the caller's array is pageable)
+  return MI_OSQP_OK;
 }
 
 void mi_gomp_scene_free(mi_gomp_scene *sc) {
