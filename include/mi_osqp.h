@@ -660,6 +660,46 @@ int mi_gomp_scene_create_grids(mi_gomp_scene **out, mi_osqp_batch *h, int64_t di
  * with nothing changed: no scene or no values (MI_OSQP_ERR_NULL); a scene without grids, k outside 0 .. n_grids - 1, a value
  * that is not finite (MI_OSQP_ERR_INVALID_DATA). */
 int mi_gomp_scene_update_grid(mi_gomp_scene *sc, int64_t k, const double *values);
+/* A grasp goal: where a trajectory has to arrive, in task space (host twin: GraspGoal in include/mi_osqp/gomp.hpp).  The
+ * structure, shared by every QP of the scene: the centre of ball `ball` at waypoint `waypoint`, and with frame >= 1 the unit
+ * vector `axis` fixed in frame `frame` of the scene's mi_gomp_chain (frame 0: a position-only goal, `axis` is not read).  What
+ * is asked differs from QP to QP (mi_gomp_goal_value): the target `point`, half widths tol[3] >= 0 (>= 1e30: that axis is
+ * free; 0: an equality), and for frame >= 1 the unit world vector `ref` and max_angle in (0, pi).  A goal owns four rows, their
+ * entries in the columns of q_w, w its waypoint.  With p the ball's centre at q_w, J its Jacobian and
+ * Jq_ax = sum_j J[ax][j] q_w[j], j ascending, in this order of operations:
+ *   rows 0 .. 2 (ax = x, y, z) hold J[ax][j];  a free axis: l = -1e30, u = +1e30;  otherwise
+ *     l = ((point_ax - tol_ax) - p_ax) + Jq_ax,   u = ((point_ax + tol_ax) - p_ax) + Jq_ax
+ *   (the ball's radius does not enter: a goal is about the centre).  Always active: there is no margin.  A trajectory is
+ *   accepted only if fabs(p_ax - point_ax) <= tol_ax + 1e-3 on every axis that is not free (a NaN fails).
+ *   row 3, frame 0: zeros (written), l = -1e30, u = +1e30, no say in the verdict.
+ *   row 3, frame >= 1: c and g_j exactly those of mi_gomp_tilt; the row holds g_j, l = (cos_lim - c) + sum_j g_j q_w[j],
+ *     u = +1e30, always active; accepted only if c >= cos_ok, with cos_lim = cos(max_angle) and
+ *     cos_ok = cos(min(pi, max_angle + 1e-3)) taken once on the host, in fp64, when the values are set.
+ * Where the axis is exactly opposite to ref the row is all zeros with l = cos_lim + 1 > 0 and that QP is primal infeasible, as
+ * for tilt limits: seed on the right side - linearise first around joints whose axis is not opposite to ref. */
+typedef struct { int32_t ball; int32_t waypoint; int32_t frame; int32_t reserved; double axis[3]; } mi_gomp_goal;   /* 40 bytes */
+typedef struct { double point[3]; double tol[3]; double ref[3]; double max_angle; } mi_gomp_goal_value;             /* 80 bytes */
+/* mi_gomp_scene_create_grids with 0 .. 4 grasp goals besides.  The goal rows follow the tilt rows, goal-major: row r of goal k
+ * is the first 3-D row + the rows of all ball blocks + waypoints * (n_pairs + n_tilts) + 4 k + r, so the constraint matrix must
+ * hold 4 n_goals rows more, each with entries in the columns of its goal's waypoint.  n_goals == 0: exactly
+ * mi_gomp_scene_create_grids.  Refused on the host, before any device call, with *out = NULL, the handle usable and the reason
+ * in mi_osqp_last_error() naming the goal's index: n_goals > 0 without goals, a frame >= 1 without a chain (MI_OSQP_ERR_NULL);
+ * n_goals outside 0 .. 4, a ball outside 0 .. n_balls - 1, a waypoint outside 0 .. waypoints - 1, a frame outside
+ * 0 .. n_joints, an axis that is not finite or (frame >= 1) not a unit vector to 1e-9, a constraint matrix that does not hold
+ * the rows (MI_OSQP_ERR_INVALID_DATA). */
+int mi_gomp_scene_create_goals(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
+        int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
+        int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
+        int64_t n_pairs, const mi_gomp_pair *pairs, int64_t n_tilts, const mi_gomp_tilt *tilts,
+        int64_t n_grids, const mi_gomp_grid *grids, int64_t n_goals, const mi_gomp_goal *goals,
+        const double *con_lo, const double *con_hi);
+/* What the listed QPs ask of the scene's goals: values[j * n_goals + k] for goal k of QP ids[j], copied on the handle's stream
+ * (also for idle QPs of a handle in the continuous mode).  Kept rows are not touched: the next mi_gomp_assemble_some /
+ * mi_gomp_relinearise_some of such a QP reads the new values, and both refuse a QP of a goal scene whose values were never set
+ * (MI_OSQP_ERR_INVALID_DATA).  Refused, with nothing changed: no scene, ids or values (MI_OSQP_ERR_NULL); a scene without
+ * goals, an id outside 0 .. B - 1, a value that is not finite, a negative tol, and for a goal with frame >= 1 a ref that is not
+ * a unit vector to 1e-9 or a max_angle outside (0, pi) (MI_OSQP_ERR_INVALID_DATA). */
+int mi_gomp_scene_set_goal_values(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, const mi_gomp_goal_value *values);
 void mi_gomp_scene_free(mi_gomp_scene *sc);          /* before mi_osqp_batch_free of its handle; one scene per handle */
 /* While a scene exists, mi_osqp_batch_reinit_some / _update_A_bounds_some of its handle also keep the QPs' raw constraint
  * data (as ConstraintBuilder::build() produced it) in the scene, so nothing extra is needed when a trajectory enters the

@@ -14,6 +14,8 @@
 //   mi_osqp::dh::axis(chain, q, frame, a, u, dU)        a unit vector a fixed in frame k: u = R_k a and (dU non-null) the 3 x n_joints
 //                                                       row-major derivative, column j = z_j x u for j < k, 0 for j >= k
 //   miosqp_ref::dhTilt(chain, frame, axis, ref, max_angle, margin)   a TiltLimit on such a vector, which names the frame for the device
+//   miosqp_ref::dhGoal(chain, ball, frame, axis)        the structure of a GraspGoal: ball `ball` of the planner's list and such a vector
+//                                                       (frame 0: the position only)
 #pragma once
 
 #include <array>
@@ -119,6 +121,20 @@ inline TiltLimit dhTilt(const mi_gomp_chain &chain, int frame, const std::array<
   t.ref = ref; t.max_angle = max_angle; t.margin = margin;
   t.builtin_frame = frame; t.builtin_axis = axis;
   return t;
+}
+
+// The structure of a grasp goal: ball `ball` of the planner's ball list reaches the target point, and the unit vector `axis`
+// fixed in frame `frame` of the chain the target cone (frame 0: a position-only goal, `axis` is not read).  The waypoint is
+// the planner's to set, the target the caller's (GoalTarget).  The callback is what the sequential, lock-step and
+// host-assembling drivers call; frame and axis are what the device path reads.
+inline GraspGoal dhGoal(const mi_gomp_chain &chain, size_t ball, int frame = 0, const std::array<double, 3> &axis = {0.0, 0.0, 1.0}) {
+  GraspGoal g;
+  g.ball = ball;
+  if (frame >= 1) {
+    g.axis = [chain, frame, axis](const double *q, double *u, double *dU) { mi_osqp::dh::axis(chain, q, frame, axis.data(), u, dU); };
+    g.builtin_frame = frame; g.builtin_axis = axis;
+  }
+  return g;
 }
 
 // The usual "skip adjacent links" rule of a self-collision model: every pair (i, j), i < j, of dhBall balls of `balls` whose

@@ -11,6 +11,7 @@
 //   BallPair                 not in the reference: two balls of the robot that must stay apart (self-collision)
 //   TiltLimit                not in the reference: an axis of the robot that must stay within an angle of a world direction
 //   DistanceGrid             not in the reference: a sensed world, a voxel grid of distances to the nearest surface
+//   GraspGoal                not in the reference: where to arrive, in task space - a target box for a ball, a cone for an axis
 //   GOMPSolver<N>            [REF] src/gomp-solver.h:13-201
 //
 // Same names, argument meaning, row layout and control flow as the reference (the known-answer
@@ -445,12 +446,91 @@ bool tiltsOKAlong(const std::vector<TiltLimit> &tilts, const QPVector &trajector
   return res;
 }
 
+// ------------------------------------------------------------- grasp goals: task-space targets (not in the reference)
+// Where a trajectory has to arrive, said in task space instead of as one joint vector: at waypoint `waypoint` the centre of
+// ball `ball` lies in the box point +- tol, and (with `axis` set) a unit vector fixed in a link stays within max_angle of the
+// world vector `ref` - a suction cup on a cylinder is free to turn about its approach axis, a bin pick has a tolerance box,
+// and the planner chooses the joints inside that set (mi_gomp_goal / mi_gomp_goal_value are the device twins,
+// include/mi_osqp.h has the formulas).  ball, waypoint and axis are the structure every trajectory of a planner shares;
+// GoalTarget is what one trajectory asks.  A goal owns four rows in the columns of its waypoint: x, y, z of the centre (the
+// ball's radius does not enter) and the cosine's gradient; all are always active, there is no margin.  Where the axis is
+// exactly opposite to ref the fourth row is all zeros with l > 0 and the QP is primal infeasible, as for tilt limits: seed on
+// the right side - the joints the first linearisation is taken at must not point the axis away from ref.
+constexpr double GOAL_FREE = 1e30;               // a half width from here on: that axis is free
+struct GoalTarget {
+  Point point{0.0, 0.0, 0.0};
+  std::array<double, 3> tol{GOAL_FREE, GOAL_FREE, GOAL_FREE};      // half widths >= 0; 0: an equality
+  std::array<double, 3> ref{0.0, 0.0, 1.0};                        // unit world vector (read only when the goal has an axis)
+  double max_angle = M_PI / 2;                                     // in (0, pi), radians
+  bool operator==(const GoalTarget &o) const { return point == o.point && tol == o.tol && ref == o.ref && max_angle == o.max_angle; }
+};
+struct GraspGoal {
+  size_t ball = 0, waypoint = 0;
+  AxisFun axis;                               // the axis in the world and its derivative; empty: a position-only goal
+  // as TiltLimit::builtin_frame: for an axis fixed in a frame of the planner's DH chain (dhGoal of dh_kinematics.hpp makes
+  // one) the frame and the axis in it, which the device path reads; frame 0 with `axis` empty: position only
+  int builtin_frame = 0;
+  std::array<double, 3> builtin_axis{};
+  GoalTarget target;
+  double cosLimit() const { return std::cos(target.max_angle); }
+  double cosOK() const { return std::cos(std::min(M_PI, target.max_angle + ERROR)); }
+  bool operator==(const GraspGoal &o) const {   // (the callback cannot be compared: the kept device scenes hold the rest)
+    return ball == o.ball && waypoint == o.waypoint && bool(axis) == bool(o.axis) && builtin_frame == o.builtin_frame && builtin_axis == o.builtin_axis;
+  }
+};
+// c = u . ref of a goal with an axis at q, and (g non-null) its gradient g[N]: tiltCosine's formulas
+template <size_t N>
+double goalCosine(const GraspGoal &gl, const double *q, double *g = nullptr) {
+  double u[3];
+  std::array<double, 3 * N> dU{};
+  gl.axis(q, u, g ? dU.data() : nullptr);
+  const std::array<double, 3> &ref = gl.target.ref;
+  if (g) for (size_t j = 0; j < N; ++j) g[j] = dU[0 * N + j] * ref[0] + dU[1 * N + j] * ref[1] + dU[2 * N + j] * ref[2];
+  return u[0] * ref[0] + u[1] * ref[1] + u[2] * ref[2];
+}
+// the goal part of isSolutionOK (shared by the three drivers): q the joints of the goal's waypoint; the centre within
+// tol + 1 mm on every axis that is not free, the axis within max_angle + 1 mrad (a NaN fails both)
+template <size_t N>
+bool goalOK(const GraspGoal &gl, const std::vector<RobotBall> &balls, const double *q) {
+  bool res = true;
+  Vec<N> qq;
+  for (size_t j = 0; j < N; ++j) qq[j] = q[j];
+  const auto [x, y, z] = balls[gl.ball].fk(qq.data());
+  const Point p{x, y, z};
+  for (size_t ax = 0; ax < 3; ++ax)
+    if (!(gl.target.tol[ax] >= GOAL_FREE) && !(std::fabs(p[ax] - gl.target.point[ax]) <= gl.target.tol[ax] + ERROR)) res = false;
+  if (gl.axis && !(goalCosine<N>(gl, qq.data()) >= gl.cosOK())) res = false;
+  return res;
+}
+// The joint-space warm start of a run towards a grasp goal: a straight line from `start` that reaches `seed` at the third-last
+// waypoint and stays there (the end conditions make the last three waypoints coincide), zero velocities.  The first QP is
+// then linearised at the seed itself: a seed that satisfies the goal is a feasible end point of it.
+template <size_t N>
+QPVector goalWarmStart(const Vec<N> &start, const Vec<N> &seed, size_t waypoints) {
+  assert(waypoints >= 4);
+  QPVector w = linspace<N>(start, seed, waypoints - 2);
+  w.resize((waypoints - 3) * N);                            // (the line's last point is the seed to round-off: the seed itself)
+  for (size_t k = 0; k < 3; ++k) w.insert(w.end(), seed.begin(), seed.end());
+  w.resize(2 * waypoints * N, 0.0);
+  return w;
+}
+// goalOK of every goal on a joint trajectory (positions in the first half of the vector)
+template <size_t N>
+bool goalsOKAlong(const std::vector<GraspGoal> &goals, const std::vector<RobotBall> &balls, const QPVector &trajectory) {
+  bool res = true;
+  for (const GraspGoal &gl : goals) {
+    if (gl.waypoint >= trajectory.size() / 2 / N) { res = false; continue; }
+    if (!goalOK<N>(gl, balls, trajectory.data() + gl.waypoint * N)) res = false;
+  }
+  return res;
+}
+
 // ------------------------------------------------------------- constraint-builder.h
 // Rows: (W-1)*D velocity<->position links, then per variable boxes (positions W*D, velocities
 // (W-1)*D, accelerations (W-2)*D), then D*W*(3 + (|obstacles| + |capsules| + |cuboids| + |grids|)*|balls|) rows for the linearised
-// end-effector / obstacle constraints (allocated even when unused: bounds +-INF), then W*(|pairs| + |tilts|) rows more.  The
+// end-effector / obstacle constraints (allocated even when unused: bounds +-INF), then W*(|pairs| + |tilts|) + 4 |goals| rows more.  The
 // populated 3-D rows come first: the blocks of the (ball, waypoint) pairs (work-space rows of a gripper ball, lines, capsules,
-// cuboids, grids), then the ball pairs' rows, pair-major, then the tilt limits' rows, tilt-major.
+// cuboids, grids), then the ball pairs' rows, pair-major, then the tilt limits' rows, tilt-major, then four rows a grasp goal.
 template <size_t N_DIM>
 class ConstraintBuilder {
   using OptPair = std::pair<std::optional<double>, std::optional<double>>;
@@ -458,20 +538,21 @@ class ConstraintBuilder {
  public:
   ConstraintBuilder(size_t waypoints, std::vector<RobotBall> m, std::vector<HorizontalLine> obstacles, std::vector<CapsuleObstacle> capsules = {},
                     std::vector<CuboidObstacle> cuboids = {}, std::vector<BallPair> pairs = {}, std::vector<TiltLimit> tilts = {},
-                    std::vector<DistanceGrid> grids = {})
+                    std::vector<DistanceGrid> grids = {}, std::vector<GraspGoal> goals = {})
       : W_(waypoints), balls_(std::move(m)), lines_(std::move(obstacles)), capsules_(std::move(capsules)), cuboids_(std::move(cuboids)),
-        pairs_(std::move(pairs)), tilts_(std::move(tilts)), grids_(std::move(grids)) {
+        pairs_(std::move(pairs)), tilts_(std::move(tilts)), grids_(std::move(grids)), goals_(std::move(goals)) {
+    for ([[maybe_unused]] const GraspGoal &gl : goals_) assert(gl.ball < balls_.size() && gl.waypoint < W_);
     for ([[maybe_unused]] const TiltLimit &t : tilts_) assert(t.axis && t.max_angle > 0.0 && t.max_angle < M_PI && t.margin >= 0.0);
     for ([[maybe_unused]] const BallPair &pr : pairs_) assert(pr.a < balls_.size() && pr.b < balls_.size() && pr.a != pr.b && pr.margin >= 0.0);
-    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size() + cuboids_.size() + grids_.size()) + pairs_.size() + tilts_.size()));
-    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size() + cuboids_.size() + grids_.size()) * balls_.size()) + W_ * (pairs_.size() + tilts_.size())); up_.reserve(lo_.capacity());
+    cells_.reserve(N_DIM * W_ * (10 + 3 * balls_.size() * (1 + lines_.size() + capsules_.size() + cuboids_.size() + grids_.size()) + pairs_.size() + tilts_.size()) + 4 * N_DIM * goals_.size());
+    lo_.reserve(N_DIM * W_ * (7 + (lines_.size() + capsules_.size() + cuboids_.size() + grids_.size()) * balls_.size()) + W_ * (pairs_.size() + tilts_.size()) + 4 * goals_.size()); up_.reserve(lo_.capacity());
     for (size_t t = 0; t + 1 < W_; ++t)                      // v_t - q_{t+1} + q_t = 0
       for (size_t j = 0; j < N_DIM; ++j) {
         lo_.push_back(-INF); up_.push_back(INF);
         put(lo_.size() - 1, {{nthVelocity(t) + j, 1.0}, {nthPos(t + 1) + j, -1.0}, {nthPos(t) + j, 1.0}}, {0.0, 0.0});
       }
     user_off_ = lo_.size();
-    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size() + cuboids_.size() + grids_.size()) * balls_.size())) + W_ * (pairs_.size() + tilts_.size());
+    const size_t extra = N_DIM * (W_ + W_ - 1 + W_ - 2 + W_ * (3 + (lines_.size() + capsules_.size() + cuboids_.size() + grids_.size()) * balls_.size())) + W_ * (pairs_.size() + tilts_.size()) + 4 * goals_.size();
     lo_.resize(user_off_ + extra, -INF);
     up_.resize(user_off_ + extra, INF);
   }
@@ -532,6 +613,7 @@ class ConstraintBuilder {
       for (size_t w = 0; w < W_; ++w) pairRow(row++, pr, trajectory, w);
     for (const TiltLimit &t : tilts_)                            // behind the pair rows, tilt-major
       for (size_t w = 0; w < W_; ++w) tiltRow(row++, t, trajectory, w);
+    for (const GraspGoal &gl : goals_) { goalRow(row, gl, trajectory); row += 4; }   // behind the tilt rows, goal-major, four a goal
     return *this;
   }
 
@@ -550,6 +632,21 @@ class ConstraintBuilder {
         for (size_t j = 0; j < N_DIM; ++j) set(nthPos(w) + j, row, 0.0);
         lo_[row] = -INF; up_[row] = INF;
       }
+    for (const GraspGoal &gl : goals_)
+      for (size_t r = 0; r < 4; ++r, ++row) {
+        for (size_t j = 0; j < N_DIM; ++j) set(nthPos(gl.waypoint) + j, row, 0.0);
+        lo_[row] = -INF; up_[row] = INF;
+      }
+    return *this;
+  }
+
+  // what this trajectory asks of goal k (a builder copied from a template: the structure stays, the values are its own);
+  // the next withObstacles() writes the rows
+  ConstraintBuilder &setGoalTarget(size_t k, const GoalTarget &target) {
+    assert(k < goals_.size());
+    assert(target.tol[0] >= 0.0 && target.tol[1] >= 0.0 && target.tol[2] >= 0.0);
+    assert(!goals_[k].axis || (target.max_angle > 0.0 && target.max_angle < M_PI));
+    goals_[k].target = target;
     return *this;
   }
 
@@ -580,6 +677,7 @@ class ConstraintBuilder {
   std::vector<BallPair> pairs_;
   std::vector<TiltLimit> tilts_;
   std::vector<DistanceGrid> grids_;
+  std::vector<GraspGoal> goals_;
   // (col, row) -> value, last write wins ([REF] constraint-builder.h:129).  A write log that is sorted into CSC
   // order and de-duplicated on demand: the builder runs once per trajectory, segment and re-linearisation,
   // and a std::map made it the bottleneck of the batched driver.
@@ -738,6 +836,38 @@ class ConstraintBuilder {
     lo_[row] = c < t.cosActive() ? (t.cosLimit() - c) + gq : -INF;
     up_[row] = INF;
   }
+  // the four rows of a goal, from `row` on, in the columns of its waypoint: J[ax] with the box around the target point for
+  // x, y, z (a free axis: no bounds), then the gradient of c = u . ref with cos(max_angle) - c + g q <= g x (no axis: zeros,
+  // no bounds).  Always active.
+  void goalRow(size_t row, const GraspGoal &gl, const QPVector &trajectory) {
+    const size_t w = gl.waypoint;
+    const RobotBall &ball = balls_[gl.ball];
+    Vec<N_DIM> q, g;
+    for (size_t j = 0; j < N_DIM; ++j) q[j] = trajectory[w * N_DIM + j];
+    const auto [px, py, pz] = ball.fk(q.data());
+    const Point p{px, py, pz};
+    std::array<double, 3 * N_DIM> J{};
+    ball.jacobian(J.data(), q.data());
+    for (size_t ax = 0; ax < 3; ++ax) {
+      double Jq = 0.0;
+      for (size_t j = 0; j < N_DIM; ++j) {
+        set(nthPos(w) + j, row + ax, J[ax * N_DIM + j]);
+        Jq += J[ax * N_DIM + j] * q[j];
+      }
+      const bool free_axis = gl.target.tol[ax] >= GOAL_FREE;
+      lo_[row + ax] = free_axis ? -INF : ((gl.target.point[ax] - gl.target.tol[ax]) - p[ax]) + Jq;
+      up_[row + ax] = free_axis ? INF : ((gl.target.point[ax] + gl.target.tol[ax]) - p[ax]) + Jq;
+    }
+    double c = 0.0, gq = 0.0;
+    g.fill(0.0);
+    if (gl.axis) c = goalCosine<N_DIM>(gl, q.data(), g.data());
+    for (size_t j = 0; j < N_DIM; ++j) {
+      set(nthPos(w) + j, row + 3, g[j]);
+      gq += g[j] * q[j];
+    }
+    lo_[row + 3] = gl.axis ? (gl.cosLimit() - c) + gq : -INF;
+    up_[row + 3] = INF;
+  }
 };
 
 // ------------------------------------------------------------------- gomp-solver.h
@@ -799,6 +929,17 @@ class GOMPSolver {
     return {last_code, last_solution};
   }
 
+  // The same with a grasp goal for an end condition (`goal` names the ball and the axis): the third-last waypoint of every
+  // horizon must reach `target` instead of one joint vector.  `seed` - joints that reach it, from any IK - is used only for
+  // the joint-space warm start; the planner chooses the end point.  Zero end velocity and acceleration stay.
+  std::pair<ExitCode, QPVector> run(Ctrl<N_DIM> start_pos, Ctrl<N_DIM> seed, const GoalTarget &target) {
+    assert(goal);
+    target_ = &target;
+    auto res = run(start_pos, seed);
+    target_ = nullptr;
+    return res;
+  }
+
   // SQP inner loop for one horizon
   std::pair<ExitCode, QPVector> run(Ctrl<N_DIM> start_pos, Ctrl<N_DIM> end_pos, size_t waypoints, const QPVector &warm_start) {
     ConstraintBuilder<N_DIM> builder = initConstraints(start_pos, end_pos, warm_start, waypoints);
@@ -831,8 +972,25 @@ class GOMPSolver {
   std::vector<TiltLimit> tilts;
   // Distance grids: a sensed world, sampled trilinearly (DistanceGrid::fromObstacles makes one from primitives); set before run()
   std::vector<DistanceGrid> grids;
-  // (tests) the acceptance test that ends the SQP loop
+  // The structure of the grasp goal of run(start, seed, target): ball and axis (dhGoal of dh_kinematics.hpp makes one); its
+  // waypoint is set by the planner, its target by the call.  run(start, end) does not look at it.
+  std::optional<GraspGoal> goal;
+  // (tests) the acceptance test that ends the SQP loop; with a target: that of run(start, seed, target)
   bool acceptable(const QPVector &q_trajectory) const { return isSolutionOK(q_trajectory); }
+  bool acceptable(const QPVector &q_trajectory, const GoalTarget &target) {
+    target_ = &target;
+    const bool r = isSolutionOK(q_trajectory);
+    target_ = nullptr;
+    return r;
+  }
+  // (tests) the first QP of a horizon, as run() sets it up: constraints linearised around the warm start
+  QPConstraints firstConstraints(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints, const QPVector &warm_start,
+                                 const GoalTarget *target = nullptr) {
+    target_ = target;
+    QPConstraints c = initConstraints(start_pos, end_pos, warm_start, waypoints).build();
+    target_ = nullptr;
+    return c;
+  }
 
  private:
   struct PrefetchJoiner { std::vector<std::thread> threads; ~PrefetchJoiner() { for (auto &t : threads) t.join(); } };
@@ -844,8 +1002,18 @@ class GOMPSolver {
   const std::vector<RobotBall> mappers;
   const InverseKinematics gripper_ik;
   const bool verbose;
+  const GoalTarget *target_ = nullptr;       // run(start, seed, target) in progress
+
+  // `goal` at the third-last of `waypoints` waypoints, asking for *target_
+  std::vector<GraspGoal> goalsAt(size_t waypoints) const {
+    if (!target_) return {};
+    GraspGoal g = *goal;
+    g.waypoint = waypoints - 3; g.target = *target_;
+    return {g};
+  }
 
   QPVector calcWarmStart(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos) const {
+    if (target_) return goalWarmStart<N_DIM>(start_pos, end_pos, max_waypoints);
     QPVector w = linspace<N_DIM>(start_pos, end_pos, max_waypoints);      // joint-space line, zero velocities
     w.resize(2 * max_waypoints * N_DIM, 0.0);
     return w;
@@ -859,10 +1027,10 @@ class GOMPSolver {
   }
   ConstraintBuilder<N_DIM> jointSpaceRows(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
     assert(waypoints >= 4);
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts, grids};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts, grids, goalsAt(waypoints)};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
-        .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
+        .position(waypoints - 3, target_ ? pos_con : constraints::equal<N_DIM>(end_pos))
         .velocities(0, waypoints - 4, vel_con)
         .velocity(waypoints - 3, constraints::eqZero<N_DIM>())
         .accelerations(0, waypoints - 4, acc_con)
@@ -894,6 +1062,7 @@ class GOMPSolver {
     }
     if (!pairsClearAlong<N_DIM>(pairs, mappers, q_trajectory)) res = false;
     if (!tiltsOKAlong<N_DIM>(tilts, q_trajectory)) res = false;
+    if (target_ && !goalsOKAlong<N_DIM>(goalsAt(q_trajectory.size() / 2 / N_DIM), mappers, q_trajectory)) res = false;
     return res;
   }
 };
@@ -929,6 +1098,7 @@ class BatchGOMPSolver {
     using clk_ = std::chrono::steady_clock;
     auto since_ = [](clk_::time_point t) { return std::chrono::duration<double>(clk_::now() - t).count(); };
     for (size_t b = 0; b < B; ++b) {
+      if (targets_) { last_solution[b] = goalWarmStart<N_DIM>(starts[b], ends[b], max_waypoints); continue; }
       last_solution[b] = linspace<N_DIM>(starts[b], ends[b], max_waypoints);      // joint-space line, zero velocities
       last_solution[b].resize(2 * max_waypoints * N_DIM, 0.0);
     }
@@ -959,9 +1129,10 @@ class BatchGOMPSolver {
           warm[k][waypoints * N_DIM + t] = prev[waypoints * N_DIM + t];
         }
         builders[k] = tmpl;
-        builders[k].position(0, constraints::equal<N_DIM>(starts[ids[k]]))
-            .position(waypoints - 3, constraints::equal<N_DIM>(ends[ids[k]]))
-            .withObstacles(con_3d, warm[k]);
+        builders[k].position(0, constraints::equal<N_DIM>(starts[ids[k]]));
+        if (targets_) builders[k].setGoalTarget(0, (*targets_)[ids[k]]);
+        else builders[k].position(waypoints - 3, constraints::equal<N_DIM>(ends[ids[k]]));
+        builders[k].withObstacles(con_3d, warm[k]);
         cons[k] = builders[k].build();
         seg_solution[k] = warm[k];
       });
@@ -992,7 +1163,7 @@ class BatchGOMPSolver {
           ++qp_solves[ids[k]];
           const auto &[exit_code, solution] = res[k];
           if (exit_code != ExitCode::kOptimal) { seg_solution[k] = solution; running[k] = 0; --n_running; continue; }
-          if (isSolutionOK(solution)) { seg_solution[k] = solution; seg_code[k] = ExitCode::kOptimal; running[k] = 0; --n_running; continue; }
+          if (isSolutionOK(solution, ids[k])) { seg_solution[k] = solution; seg_code[k] = ExitCode::kOptimal; running[k] = 0; --n_running; continue; }
           if (it + 1 < MAX_ITERATIONS) {
             cons[k] = builders[k].withObstacles(con_3d, solution).build();
             ++qp_updates[ids[k]];
@@ -1017,6 +1188,18 @@ class BatchGOMPSolver {
     return out;
   }
 
+  // The same with a grasp goal for an end condition, as GOMPSolver::run(start, seed, target): `goal` names the ball and the
+  // axis, targets[b] is what trajectory b asks, seeds[b] serves its joint-space warm start only.
+  std::vector<std::pair<ExitCode, QPVector>> run(const std::vector<Ctrl<N_DIM>> &starts, const std::vector<Ctrl<N_DIM>> &seeds,
+                                                 const std::vector<GoalTarget> &targets) {
+    assert(goal && targets.size() == starts.size());
+    targets_ = &targets;
+    auto res = run(starts, seeds);
+    targets_ = nullptr;
+    return res;
+  }
+  std::optional<GraspGoal> goal;              // the structure of the goal of run(starts, seeds, targets); run(starts, ends) does not look at it
+
   // per-trajectory counters (comparable with GOMPSolver's) and the number of batched solves
   std::vector<int> segments_run, qp_solves, qp_updates;
   int batch_solves = 0;
@@ -1039,6 +1222,15 @@ class BatchGOMPSolver {
   const std::vector<HorizontalLine> obstacles;
   const std::vector<RobotBall> mappers;
   const bool verbose;
+  const std::vector<GoalTarget> *targets_ = nullptr;      // run(starts, seeds, targets) in progress
+
+  // `goal` at the third-last of `waypoints` waypoints (the targets are set per trajectory)
+  std::vector<GraspGoal> goalsAt(size_t waypoints) const {
+    if (!targets_) return {};
+    GraspGoal g = *goal;
+    g.waypoint = waypoints - 3;
+    return {g};
+  }
 
   std::array<std::unique_ptr<BatchSolverT>, SEGMENTS> solver_cache_;
   // (a batch solver type without reinit(), e.g. a test double, is always rebuilt)
@@ -1059,10 +1251,10 @@ class BatchGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts, grids};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts, grids, goalsAt(waypoints)};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
-        .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
+        .position(waypoints - 3, targets_ ? pos_con : constraints::equal<N_DIM>(end_pos))
         .velocities(0, waypoints - 4, vel_con)
         .velocity(waypoints - 3, constraints::eqZero<N_DIM>())
         .accelerations(0, waypoints - 4, acc_con)
@@ -1071,8 +1263,13 @@ class BatchGOMPSolver {
     return b;
   }
 
-  bool isSolutionOK(const QPVector &q_trajectory) const {
+  bool isSolutionOK(const QPVector &q_trajectory, size_t b) const {
     bool res = true;
+    if (targets_) {                                               // the goal of trajectory b at the third-last waypoint
+      std::vector<GraspGoal> gs = goalsAt(q_trajectory.size() / 2 / N_DIM);
+      gs[0].target = (*targets_)[b];
+      if (!goalsOKAlong<N_DIM>(gs, mappers, q_trajectory)) res = false;
+    }
     for (const RobotBall &ball : mappers) {
       const QPVector xyz = mapJointTrajectoryToXYZ<N_DIM>(q_trajectory, ball.fk);
       const int waypoints = (int)xyz.size() / 3;
@@ -1125,20 +1322,25 @@ class ContinuousGOMPSolver {
     const size_t B = starts.size();
     assert(ends.size() == B && B > 0);
     starts_ = &starts; ends_ = &ends;
-    if (!(capsules == scene_capsules_ && cuboids == scene_cuboids_ && pairs == scene_pairs_ && tilts == scene_tilts_ && grids == scene_grids_)) {   // the kept scenes hold the capsules, cuboids, pairs and tilt limits of the run that made them
+    const std::optional<GraspGoal> goal_now = targets_ ? goal : std::nullopt;
+    if (!(capsules == scene_capsules_ && cuboids == scene_cuboids_ && pairs == scene_pairs_ && tilts == scene_tilts_ && grids == scene_grids_ && goal_now == scene_goal_)) {   // the kept scenes hold the capsules, cuboids, pairs and tilt limits of the run that made them
       for (Stage &st : stages_) if (st.scene) { mi_gomp_scene_free(st.scene); st.scene = nullptr; }
       scene_capsules_ = capsules;
       scene_cuboids_ = cuboids;
       scene_pairs_ = pairs;
       scene_tilts_ = tilts;
       scene_grids_ = grids;
+      scene_goal_ = goal_now;
     }
     traj_.clear(); traj_.resize(B);
     segments_run.assign(B, 0); qp_solves.assign(B, 0); qp_updates.assign(B, 0);
     advances = 0; solver_reuses = 0;
     for (size_t b = 0; b < B; ++b) {
-      traj_[b].last_solution = linspace<N_DIM>(starts[b], ends[b], max_waypoints);      // joint-space line, zero velocities
-      traj_[b].last_solution.resize(2 * max_waypoints * N_DIM, 0.0);
+      if (targets_) traj_[b].last_solution = goalWarmStart<N_DIM>(starts[b], ends[b], max_waypoints);
+      else {
+        traj_[b].last_solution = linspace<N_DIM>(starts[b], ends[b], max_waypoints);      // joint-space line, zero velocities
+        traj_[b].last_solution.resize(2 * max_waypoints * N_DIM, 0.0);
+      }
       traj_[b].builder = std::make_unique<ConstraintBuilder<N_DIM>>(4, std::vector<RobotBall>{}, std::vector<HorizontalLine>{});
     }
     for (int s = 0; s < SEGMENTS; ++s) {
@@ -1161,6 +1363,21 @@ class ContinuousGOMPSolver {
     }
     return out;
   }
+
+  // The same with a grasp goal for an end condition, as GOMPSolver::run(start, seed, target): `goal` names the ball and the
+  // axis, targets[b] is what trajectory b asks, seeds[b] serves its joint-space warm start only.  On the device path the goal
+  // goes into the scene (mi_gomp_scene_create_goals) and every arrival's target with it (mi_gomp_scene_set_goal_values).
+  std::vector<std::pair<ExitCode, QPVector>> run(const std::vector<Ctrl<N_DIM>> &starts, const std::vector<Ctrl<N_DIM>> &seeds,
+                                                 const std::vector<GoalTarget> &targets) {
+    assert(goal && targets.size() == starts.size());
+    targets_ = &targets;
+    auto res = run(starts, seeds);
+    targets_ = nullptr;
+    return res;
+  }
+  // The structure of the goal of run(starts, seeds, targets); run(starts, ends) does not look at it.  The device path needs
+  // its ball to name a built-in model and, if it has an axis, dh_chain and a goal made by dhGoal (builtin_frame >= 1).
+  std::optional<GraspGoal> goal;
 
   // per-trajectory counters (comparable with GOMPSolver's)
   std::vector<int> segments_run, qp_solves, qp_updates;
@@ -1245,6 +1462,15 @@ class ContinuousGOMPSolver {
   std::vector<BallPair> scene_pairs_;
   std::vector<TiltLimit> scene_tilts_;
   std::vector<DistanceGrid> scene_grids_;
+  std::optional<GraspGoal> scene_goal_;                // the goal structure of the kept scenes (none: they were made without)
+  const std::vector<GoalTarget> *targets_ = nullptr;   // run(starts, seeds, targets) in progress
+  // `goal` at the third-last of `waypoints` waypoints (the targets are set per trajectory)
+  std::vector<GraspGoal> goalsAt(size_t waypoints) const {
+    if (!targets_) return {};
+    GraspGoal g = *goal;
+    g.waypoint = waypoints - 3;
+    return {g};
+  }
   const std::vector<Ctrl<N_DIM>> *starts_ = nullptr, *ends_ = nullptr;
   std::atomic<size_t> finished_{0};
   std::atomic<bool> failed_{false};
@@ -1303,9 +1529,10 @@ class ContinuousGOMPSolver {
         T.warm[W * N_DIM + t] = prev[W * N_DIM + t];
       }
       *T.builder = tmpl;
-      T.builder->position(0, constraints::equal<N_DIM>((*starts_)[arrivals[k]]))
-          .position(W - 3, constraints::equal<N_DIM>((*ends_)[arrivals[k]]))
-          .withObstacles(con_3d, T.warm);
+      T.builder->position(0, constraints::equal<N_DIM>((*starts_)[arrivals[k]]));
+      if (targets_) T.builder->setGoalTarget(0, (*targets_)[arrivals[k]]);
+      else T.builder->position(W - 3, constraints::equal<N_DIM>((*ends_)[arrivals[k]]));
+      T.builder->withObstacles(con_3d, T.warm);
       T.cons = T.builder->build();
       T.seg_solution = T.warm; T.seg_code = ExitCode::kUnknown; T.sqp_it = 0;
     };
@@ -1320,6 +1547,18 @@ class ContinuousGOMPSolver {
     std::vector<const QPVector *> xs;
     for (size_t b : arrivals) { ids.push_back((long long)b); cs.push_back(&traj_[b].cons); xs.push_back(&traj_[b].warm); }
     st.qp->reinit(ids, cs);
+    if (st.scene && targets_) {                                   // what the arrivals ask of the scene's goal
+      std::vector<mi_gomp_goal_value> vals;
+      for (size_t b : arrivals) {
+        const GoalTarget &t = (*targets_)[b];
+        mi_gomp_goal_value v{};
+        for (int k = 0; k < 3; ++k) { v.point[k] = t.point[k]; v.tol[k] = t.tol[k]; v.ref[k] = t.ref[k]; }
+        v.max_angle = t.max_angle;
+        vals.push_back(v);
+      }
+      const int rc = mi_gomp_scene_set_goal_values(st.scene, (int64_t)ids.size(), reinterpret_cast<const int64_t *>(ids.data()), vals.data());
+      if (rc != MI_OSQP_OK) { std::fprintf(stderr, "ContinuousGOMPSolver: goal values refused: %s (%s)\n", mi_osqp_error_name(rc), mi_osqp_last_error()); failed_ = true; wakeAll(); return; }
+    }
     // (with a device scene the library keeps these rows on the device as well: the re-linearisations to come start from them)
     st.qp->setWarmStart(ids, xs);
     st.qp->begin(ids);
@@ -1329,6 +1568,10 @@ class ContinuousGOMPSolver {
     if (!device_assembly) return false;
     for (const RobotBall &b : mappers) if (!b.builtin_model || (b.builtin_model == MI_GOMP_MODEL_DH_CHAIN && !dh_chain)) return false;
     for (const TiltLimit &t : tilts) if (t.builtin_frame < 1 || !dh_chain) return false;       // (a callback alone: the host path)
+    if (targets_) {                                               // the goal's ball is one of the balls above; its axis as a tilt's
+      if (goal->ball >= mappers.size()) return false;
+      if (goal->axis && (goal->builtin_frame < 1 || !dh_chain)) return false;
+    }
     return true;
   }
   void makeScene(Stage &st) {
@@ -1381,7 +1624,18 @@ class ContinuousGOMPSolver {
       g.cell = d.cell; g.offset = d.offset; g.margin = d.margin; g.values = d.values->data();
       grs.push_back(g);
     }
-    const int rc = !grs.empty() ? mi_gomp_scene_create_grids(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+    std::vector<mi_gomp_goal> gls;
+    for (const GraspGoal &g0 : goalsAt(st.waypoints)) {
+      mi_gomp_goal g{};
+      g.ball = (int32_t)g0.ball; g.waypoint = (int32_t)g0.waypoint; g.frame = g0.axis ? (int32_t)g0.builtin_frame : 0;
+      for (int k = 0; k < 3; k++) g.axis[k] = g0.builtin_axis[k];
+      gls.push_back(g);
+    }
+    const int rc = !gls.empty() ? mi_gomp_scene_create_goals(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
+                                                              (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(),
+                                                              (int64_t)cubs.size(), cubs.data(), (int64_t)prs.size(), prs.data(), (int64_t)tls.size(), tls.data(),
+                                                              (int64_t)grs.size(), grs.data(), (int64_t)gls.size(), gls.data(), lo, hi)
+                   : !grs.empty() ? mi_gomp_scene_create_grids(&st.scene, st.qp->handle(), (int64_t)N_DIM, (int64_t)st.waypoints, dh_chain ? &*dh_chain : nullptr,
                                                               (int64_t)balls.size(), balls.data(), (int64_t)lines.size(), lines.data(), (int64_t)caps.size(), caps.data(),
                                                               (int64_t)cubs.size(), cubs.data(), (int64_t)prs.size(), prs.data(), (int64_t)tls.size(), tls.data(),
                                                               (int64_t)grs.size(), grs.data(), lo, hi)
@@ -1442,7 +1696,7 @@ class ContinuousGOMPSolver {
       ++qp_solves[b];
       bool ends_here = true;
       if (exit_code != ExitCode::kOptimal) T.seg_solution = std::move(solution);                          // there are no solutions
-      else if (isSolutionOK(solution)) { T.seg_solution = std::move(solution); T.seg_code = ExitCode::kOptimal; }
+      else if (isSolutionOK(solution, b)) { T.seg_solution = std::move(solution); T.seg_code = ExitCode::kOptimal; }
       else {
         // (the reference re-linearises and updates also in the last of its MAX_ITERATIONS rounds; that update has no reader)
         ++qp_updates[b];
@@ -1478,10 +1732,10 @@ class ContinuousGOMPSolver {
 
   // initConstraints of GOMPSolver ([REF] src/gomp-solver.h:98-110) without its last call (the obstacle rows), normalised
   ConstraintBuilder<N_DIM> jointSpaceTemplate(const Ctrl<N_DIM> &start_pos, const Ctrl<N_DIM> &end_pos, size_t waypoints) const {
-    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts, grids};
+    ConstraintBuilder<N_DIM> b{waypoints, mappers, obstacles, capsules, cuboids, pairs, tilts, grids, goalsAt(waypoints)};
     b.position(0, constraints::equal<N_DIM>(start_pos))
         .positions(1, waypoints - 2, pos_con)
-        .position(waypoints - 3, constraints::equal<N_DIM>(end_pos))
+        .position(waypoints - 3, targets_ ? pos_con : constraints::equal<N_DIM>(end_pos))
         .velocities(0, waypoints - 4, vel_con)
         .velocity(waypoints - 3, constraints::eqZero<N_DIM>())
         .accelerations(0, waypoints - 4, acc_con)
@@ -1490,8 +1744,13 @@ class ContinuousGOMPSolver {
     return b;
   }
 
-  bool isSolutionOK(const QPVector &q_trajectory) const {
+  bool isSolutionOK(const QPVector &q_trajectory, size_t b) const {
     bool res = true;
+    if (targets_) {                                               // the goal of trajectory b at the third-last waypoint
+      std::vector<GraspGoal> gs = goalsAt(q_trajectory.size() / 2 / N_DIM);
+      gs[0].target = (*targets_)[b];
+      if (!goalsOKAlong<N_DIM>(gs, mappers, q_trajectory)) res = false;
+    }
     for (const RobotBall &ball : mappers) {
       const QPVector xyz = mapJointTrajectoryToXYZ<N_DIM>(q_trajectory, ball.fk);
       const int waypoints = (int)xyz.size() / 3;

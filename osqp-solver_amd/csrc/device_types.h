@@ -296,6 +296,11 @@ struct GompTiltDev { int frame, pad; double axis[3], ref[3], cos_lim, cos_act, c
 // a distance grid (mi_gomp_grid): n[0] x n[1] x n[2] nodes of spacing 1 / inv_cell, node (0,0,0) at `origin`, the x index
 // fastest: V[iz sz + iy sy + ix] with sy = n[0], sz = n[0] n[1]; `values` points into the scene's one buffer of all grids' nodes
 struct GompGridDev { double origin[3], inv_cell; int n[3], sy, sz, pad; double offset, margin; const double *values; };
+// a grasp goal (mi_gomp_goal): the centre of ball `ball` at waypoint `waypoint` reaches a per-QP target box and, with frame >= 1,
+// `axis`, fixed in that frame of the chain, a per-QP cone; four rows a goal, in the columns of that one waypoint
+struct GompGoalDev { int ball, waypoint, frame, pad; double axis[3]; };
+// what a QP asks of a goal (mi_gomp_goal_value); the two cosines are taken once on the host when the values are set
+struct GompGoalValDev { double point[3], tol[3], ref[3], cos_lim, cos_ok; };
 struct GompArgs {
   int dims, W, n_balls, n_lines, n, m, nnzA, n_ids, row0, write_rows;
   int n_caps, n_cuboids;
@@ -310,6 +315,9 @@ struct GompArgs {
   const GompCuboidDev *cuboids;  // [n_cuboids]: their rows follow the capsules'
   const GompPairDev *pairs;      // [n_pairs]: row pair_row0 + k W + w for (pair k, waypoint w), behind every ball's block
   const GompTiltDev *tilts;      // [n_tilts]: row tilt_row0 + k W + w for (tilt k, waypoint w), behind the pair rows
+  int n_goals, goal_row0;        // goal_row0: the first goal row = tilt_row0 + W n_tilts; row goal_row0 + 4 k + r for row r of goal k
+  const GompGoalDev *goals;      // [n_goals]
+  const GompGoalValDev *goal_vals;   // [B][n_goals]: by the QP's id, not by its place in the list
   double con_lo[3], con_hi[3];   // work-space box of the gripper balls (+-1e30 = none)
   const int *aidx;               // [3-D row][dims]: position of that row's entry in column nthPos(w) + j of A's value array
   const double *traj;            // [n_ids][n]: the trajectories to linearise around (row = position in the list)

@@ -3896,7 +3896,9 @@ hipError_t launch_ruiz(const RuizArgs &a, hipStream_t st) {
 // workgroup per trajectory, one thread per (ball, waypoint); behind those items one thread per (ball pair, waypoint): one row
 // each behind the block of the last ball, the same rule on the distance of the two centres; behind those one thread per (tilt
 // limit, waypoint): one row each behind the pair rows, the gradient of the cosine between an axis of the chain and a world
-// vector, active near the cone, and no waypoint may be more than 1 mrad outside it.
+// vector, active near the cone, and no waypoint may be more than 1 mrad outside it; behind those one thread per grasp goal:
+// four rows each behind the tilt rows, at the goal's one waypoint - the centre of a ball against a per-trajectory target box
+// and the cosine of an axis against a per-trajectory cone -, always active.
 __device__ __forceinline__ void ur5e_point(const double *q, int frame, double *p, double *J /* 3 x 6 row-major */) {
   const double a[6] = {0.0, -0.425, -0.3922, 0.0, 0.0, 0.0}, d[6] = {0.1625, 0.0, 0.0, 0.1333, 0.0997, 0.0996};
   const double alpha[6] = {1.5707963267948966, 0.0, 0.0, 1.5707963267948966, -1.5707963267948966, 0.0};
@@ -4273,6 +4275,52 @@ __global__ __launch_bounds__(256) void gomp_relinearise_kernel(GompArgs g) {
       }
     g.l[(size_t)qp * g.m + row] = c < tl.cos_act ? (tl.cos_lim - c) + gq : -MI_INFTY;
     g.u[(size_t)qp * g.m + row] = MI_INFTY;
+  }
+  // grasp goals (GraspGoal of gomp.hpp, formulas at mi_gomp_goal): the items behind the tilt items, one lane per goal, four
+  // rows each at the goal's one waypoint.  What is asked differs from QP to QP: the values are read at the QP's id, not at
+  // its place in the list.  The position verdict reads the centre in xyz; the axis verdict needs the first walk of dh_axis
+  // (frame 0: the identity, and no say).  The row pass forms the axis row first, then the Jacobian in the same array: one
+  // call site each, not unrolled.  Always active: no margin.
+#pragma unroll 1
+  for (int e = tid; e < g.n_goals; e += blockDim.x) {
+    const GompGoalDev &gl = g.goals[e];
+    const GompGoalValDev &gv = g.goal_vals[(size_t)qp * g.n_goals + e];
+    const int w = gl.waypoint;
+    const double *xg = smem + ((size_t)gl.ball * W + w) * 3;
+    for (int ax = 0; ax < 3; ax++)
+      if (!(gv.tol[ax] >= 1e30) && !(fabs(xg[ax] - gv.point[ax]) <= gv.tol[ax] + 1e-3)) ok = 0;   // (a NaN fails)
+#pragma unroll
+    for (int j = 0; j < MI_GOMP_MAXD; j++) q[j] = j < D ? traj[(size_t)w * D + j] : 0.0;
+    const bool has_axis = gl.frame >= 1;
+    const double c = dh_axis(g.chain, q, gl.frame, gl.axis, gv.ref, wr, J);
+    if (has_axis && !(c >= gv.cos_ok)) ok = 0;
+    if (!wr) continue;
+    const int row = g.goal_row0 + 4 * e;
+    double *Aq = g.A + (size_t)qp * g.nnzA;
+    {
+      const int *ai = g.aidx + (size_t)(row + 3 - g.row0) * D;
+      double gq = 0.0;
+#pragma unroll
+      for (int j = 0; j < MI_GOMP_MAXD; j++)
+        if (j < D) {
+          Aq[ai[j]] = J[j];                                                                      // frame 0: zeros, written
+          gq += J[j] * q[j];
+        }
+      g.l[(size_t)qp * g.m + row + 3] = has_axis ? (gv.cos_lim - c) + gq : -MI_INFTY;
+      g.u[(size_t)qp * g.m + row + 3] = MI_INFTY;
+    }
+    gomp_fk_jac(g.chain, g.balls[gl.ball], D, q, p, J);
+    for (int ax = 0; ax < 3; ax++) {
+      const int *ai = g.aidx + (size_t)(row + ax - g.row0) * D;
+      double Jq = 0.0;
+      for (int j = 0; j < D; j++) {
+        Aq[ai[j]] = J[ax * D + j];
+        Jq += J[ax * D + j] * q[j];
+      }
+      const bool free_axis = gv.tol[ax] >= 1e30;
+      g.l[(size_t)qp * g.m + row + ax] = free_axis ? -MI_INFTY : ((gv.point[ax] - gv.tol[ax]) - p[ax]) + Jq;
+      g.u[(size_t)qp * g.m + row + ax] = free_axis ? MI_INFTY : ((gv.point[ax] + gv.tol[ax]) - p[ax]) + Jq;
+    }
   }
   }
   if (tid == 0) g.ok[jq] = s_ok;

@@ -3821,7 +3821,7 @@ int mi_osqp_batch_update_rho_some(mi_osqp_batch *h, int64_t n_ids, const int64_t
 // Besides the built-in models a scene may hold one DH chain (mi_gomp_chain) with balls fixed in its link frames.
 struct mi_gomp_scene {
   mi_osqp_batch *h = nullptr;
-  int dims = 0, W = 0, n_balls = 0, n_lines = 0, n_caps = 0, n_cuboids = 0, n_pairs = 0, pair_row0 = 0, n_tilts = 0, tilt_row0 = 0, row0 = 0, n_rows3d = 0, n_grids = 0;
+  int dims = 0, W = 0, n_balls = 0, n_lines = 0, n_caps = 0, n_cuboids = 0, n_pairs = 0, pair_row0 = 0, n_tilts = 0, tilt_row0 = 0, row0 = 0, n_rows3d = 0, n_grids = 0, n_goals = 0, goal_row0 = 0;
   double con_lo[3] = {-1e30, -1e30, -1e30}, con_hi[3] = {1e30, 1e30, 1e30};
   DevBuf<GompBallDev> balls;
   DevBuf<GompLineDev> lines;
@@ -3832,6 +3832,10 @@ struct mi_gomp_scene {
   DevBuf<GompGridDev> grids;                  // distance grids: their rows follow the cuboids' in every (ball, waypoint) block
   DevBuf<double> grid_vals;                   // the nodes of all grids, one after the other
   std::vector<size_t> grid_off, grid_len;     // where grid k's nodes start in grid_vals and how many they are
+  DevBuf<GompGoalDev> goals;                  // grasp goals: their rows goal_row0 + 4 k + r, behind the tilt rows
+  DevBuf<GompGoalValDev> goal_vals;           // [B][n_goals]: what each QP asks of the goals (mi_gomp_scene_set_goal_values)
+  std::vector<int> goal_frame;                // the goals' frames, for the checks of the values
+  std::vector<char> goal_set;                 // [B]: this QP's values have been set
   GompChainDev chain{};                       // the DH chain of the MI_GM_DH_CHAIN balls (n_joints 0: the scene has none)
   DevBuf<int> aidx;
   DevBuf<double> A, l, u;                     // QP-major raw rows as ConstraintBuilder::build() lays them out
@@ -3854,9 +3858,9 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
   if ((rc = ring_upload(h, sp, (size_t)nq * n * sizeof(double)))) return rc;
   hipStream_t st = h->stream;
   GompArgs g{};
-  g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n_caps = sc->n_caps; g.n_cuboids = sc->n_cuboids; g.n_pairs = sc->n_pairs; g.pair_row0 = sc->pair_row0; g.n_tilts = sc->n_tilts; g.tilt_row0 = sc->tilt_row0; g.n_grids = sc->n_grids; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
+  g.dims = sc->dims; g.W = sc->W; g.n_balls = sc->n_balls; g.n_lines = sc->n_lines; g.n_caps = sc->n_caps; g.n_cuboids = sc->n_cuboids; g.n_pairs = sc->n_pairs; g.pair_row0 = sc->pair_row0; g.n_tilts = sc->n_tilts; g.tilt_row0 = sc->tilt_row0; g.n_grids = sc->n_grids; g.n_goals = sc->n_goals; g.goal_row0 = sc->goal_row0; g.n = n; g.m = m; g.nnzA = an.Ap[n]; g.n_ids = nq;
   g.row0 = sc->row0; g.write_rows = write_rows;
-  g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.caps = sc->caps.p; g.cuboids = sc->cuboids.p; g.pairs = sc->pairs.p; g.tilts = sc->tilts.p; g.grids = sc->grids.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
+  g.ids = d_ids; g.balls = sc->balls.p; g.lines = sc->lines.p; g.caps = sc->caps.p; g.cuboids = sc->cuboids.p; g.pairs = sc->pairs.p; g.tilts = sc->tilts.p; g.grids = sc->grids.p; g.goals = sc->goals.p; g.goal_vals = sc->goal_vals.p; g.aidx = sc->aidx.p; g.traj = (const double *)sp.dev;
   for (int k = 0; k < 3; k++) { g.con_lo[k] = sc->con_lo[k]; g.con_hi[k] = sc->con_hi[k]; }
   g.A = sc->A.p; g.l = sc->l.p; g.u = sc->u.p; g.ok = sc->h_ok;
   g.chain = sc->chain;
@@ -3870,7 +3874,7 @@ static int gomp_launch(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, con
 // mi_gomp_scene_create (chain null: model 6 is refused as it always was), mi_gomp_scene_create_chain and
 // mi_gomp_scene_create_world (capsules besides), mi_gomp_scene_create_cuboids (cuboids besides those) and
 // mi_gomp_scene_create_pairs (ball pairs besides those), mi_gomp_scene_create_tilts (tilt limits besides those) and
-// mi_gomp_scene_create_grids (distance grids besides those).
+// mi_gomp_scene_create_grids (distance grids besides those), mi_gomp_scene_create_goals (grasp goals besides those).
 // Everything that can be refused is refused here on the host, the checks that need no handle first.
 // every node of a grid is a finite number: the message names the first that is not, by its indices
 static int gomp_grid_values_finite(const std::string &who, const int32_t *n, const double *values) {
@@ -3883,11 +3887,22 @@ static int gomp_grid_values_finite(const std::string &who, const int32_t *n, con
     }
   return 0;
 }
+// a goal scene re-linearises only QPs that have been told what they ask of the goals (ids out of range: cont_check_ids)
+static int gomp_goal_values_set(const mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids) {
+  if (!sc->n_goals) return 0;
+  for (int64_t j = 0; j < n_ids; j++)
+    if (ids[j] >= 0 && ids[j] < sc->h->B && !sc->goal_set[(size_t)ids[j]]) {
+      g_last_error = "QP " + std::to_string(ids[j]) + ": the goal values were never set (mi_gomp_scene_set_goal_values)";
+      return MI_OSQP_ERR_INVALID_DATA;
+    }
+  return 0;
+}
 static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain, bool chain_entry,
                              int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                              int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
                              int64_t n_pairs, const mi_gomp_pair *pairs, int64_t n_tilts, const mi_gomp_tilt *tilts,
-                             int64_t n_grids, const mi_gomp_grid *grids, const double *con_lo, const double *con_hi) {
+                             int64_t n_grids, const mi_gomp_grid *grids, int64_t n_goals, const mi_gomp_goal *goals,
+                             const double *con_lo, const double *con_hi) {
   if (!out) return MI_OSQP_ERR_NULL;
   *out = nullptr;
   if ((n_balls > 0 && !balls) || (n_lines > 0 && !lines)) return MI_OSQP_ERR_NULL;
@@ -4008,6 +4023,24 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
     grid_off.push_back(grid_total); grid_len.push_back(count);
     grid_total += count;
   }
+  // a grasp goal: the structure only; what each QP asks of it comes with mi_gomp_scene_set_goal_values
+  if (n_goals > 0 && !goals) { g_last_error = "n_goals > 0 and no goals"; return MI_OSQP_ERR_NULL; }
+  if (n_goals < 0 || n_goals > 4) { g_last_error = "n_goals must be 0 .. 4"; return MI_OSQP_ERR_INVALID_DATA; }
+  std::vector<GompGoalDev> hgoal((size_t)n_goals);
+  for (int64_t k = 0; k < n_goals; k++) {
+    const mi_gomp_goal &gl = goals[k];
+    const std::string who = "goal " + std::to_string(k);
+    if (gl.ball < 0 || gl.ball >= n_balls) { g_last_error = who + ": ball must be 0 .. n_balls - 1"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (gl.waypoint < 0 || gl.waypoint >= waypoints) { g_last_error = who + ": waypoint must be 0 .. waypoints - 1"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (gl.frame >= 1 && !chain) { g_last_error = who + " names a frame of the chain and the scene has no chain"; return MI_OSQP_ERR_NULL; }
+    if (gl.frame < 0 || gl.frame > hc.n_joints) { g_last_error = who + ": frame must be 0 .. n_joints"; return MI_OSQP_ERR_INVALID_DATA; }
+    if (!(std::isfinite(gl.axis[0]) && std::isfinite(gl.axis[1]) && std::isfinite(gl.axis[2]))) { g_last_error = who + " has an axis that is not finite"; return MI_OSQP_ERR_INVALID_DATA; }
+    const double na = std::sqrt(gl.axis[0] * gl.axis[0] + gl.axis[1] * gl.axis[1] + gl.axis[2] * gl.axis[2]);
+    if (gl.frame >= 1 && !(std::fabs(na - 1.0) <= 1e-9)) { g_last_error = who + ": axis is not a unit vector"; return MI_OSQP_ERR_INVALID_DATA; }
+    GompGoalDev &d = hgoal[(size_t)k];
+    d.ball = gl.ball; d.waypoint = gl.waypoint; d.frame = gl.frame; d.pad = 0;
+    for (int i = 0; i < 3; i++) d.axis[i] = gl.axis[i];
+  }
   if (!h) return MI_OSQP_ERR_NULL;
   const Analysis &an = (*h->anp);
   const int D = (int)dims, W = (int)waypoints;
@@ -4025,9 +4058,12 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
   rows3d += W * (int)n_pairs;
   const int tilt_row0 = row0 + rows3d;                             // the tilt rows: behind the pair rows, tilt-major
   rows3d += W * (int)n_tilts;
+  const int goal_row0 = row0 + rows3d;                             // the goal rows: behind the tilt rows, goal-major, four a goal
+  rows3d += 4 * (int)n_goals;
   if (row0 + rows3d > an.m) {
     g_last_error = "the constraint matrix does not hold the 3-D rows of this scene";
-    if (n_tilts > 0 && tilt_row0 <= an.m) g_last_error += " (tilt " + std::to_string((an.m - tilt_row0) / W) + ")";   // the first tilt without its rows
+    if (n_goals > 0 && goal_row0 <= an.m) g_last_error += " (goal " + std::to_string((an.m - goal_row0) / 4) + ")";   // the first goal without its rows
+    else if (n_tilts > 0 && tilt_row0 <= an.m) g_last_error += " (tilt " + std::to_string((an.m - tilt_row0) / W) + ")";   // the first tilt without its rows
     else if (n_grids > 0) {                                        // the first grid row the matrix lacks, if a grid row is the first
       int r = row0;
       for (int b = 0; b < (int)n_balls && r <= an.m; b++)
@@ -4043,7 +4079,7 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
   mi_gomp_scene *sc = new (std::nothrow) mi_gomp_scene();
   if (!sc) return MI_OSQP_ERR_ALLOC;
   std::unique_ptr<mi_gomp_scene> own(sc);
-  sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->n_caps = (int)n_capsules; sc->n_cuboids = (int)n_cuboids; sc->n_pairs = (int)n_pairs; sc->pair_row0 = pair_row0; sc->n_tilts = (int)n_tilts; sc->tilt_row0 = tilt_row0; sc->row0 = row0; sc->n_rows3d = rows3d; sc->n_grids = (int)n_grids;
+  sc->h = h; sc->dims = D; sc->W = W; sc->n_balls = (int)n_balls; sc->n_lines = (int)n_lines; sc->n_caps = (int)n_capsules; sc->n_cuboids = (int)n_cuboids; sc->n_pairs = (int)n_pairs; sc->pair_row0 = pair_row0; sc->n_tilts = (int)n_tilts; sc->tilt_row0 = tilt_row0; sc->row0 = row0; sc->n_rows3d = rows3d; sc->n_grids = (int)n_grids; sc->n_goals = (int)n_goals; sc->goal_row0 = goal_row0;
   sc->chain = hc;
   for (int k = 0; k < 3; k++) { sc->con_lo[k] = con_lo ? con_lo[k] : -1e30; sc->con_hi[k] = con_hi ? con_hi[k] : 1e30; }
   // where the entries of the 3-D rows sit in A's value array: row r of waypoint w holds D entries in the columns of q_w
@@ -4074,6 +4110,9 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
     for (int k = 0; k < (int)n_tilts; k++)
       for (int w = 0; w < W; w++, r++)
         if (!locate(w)) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene (tilt " + std::to_string(k) + ")"; return MI_OSQP_ERR_INVALID_DATA; }
+    for (int k = 0; k < (int)n_goals; k++)
+      for (int i = 0; i < 4; i++, r++)
+        if (!locate(goals[k].waypoint)) { g_last_error = "the constraint matrix does not hold the 3-D rows of this scene (goal " + std::to_string(k) + ")"; return MI_OSQP_ERR_INVALID_DATA; }
   }
   std::vector<GompBallDev> hb((size_t)n_balls);
   for (int b = 0; b < (int)n_balls; b++) { hb[b].model = balls[b].model; hb[b].is_gripper = balls[b].is_gripper; hb[b].radius = balls[b].radius; for (int k = 0; k < 12; k++) hb[b].param[k] = balls[b].param[k]; }
@@ -4114,6 +4153,11 @@ static int gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims
     if ((rc = sc->grids.upload(hgrid))) return rc;
     sc->grid_off = grid_off; sc->grid_len = grid_len;
   }
+  if (n_goals > 0) {
+    if ((rc = sc->goals.upload(hgoal)) || (rc = sc->goal_vals.alloc((size_t)h->B * (size_t)n_goals))) return rc;
+    for (int k = 0; k < (int)n_goals; k++) sc->goal_frame.push_back(goals[k].frame);
+    sc->goal_set.assign((size_t)h->B, 0);
+  }
   HIPCHK(hostpool::alloc((void **)&sc->h_ok, (size_t)h->B * sizeof(int), &sc->h_ok_cap));
   HIPCHK(hipEventCreateWithFlags(&sc->ev, hipEventDisableTiming));
   if (h->cont.keepA) { g_last_error = "the solver already has a scene"; return MI_OSQP_ERR_INVALID_DATA; }
@@ -4126,29 +4170,29 @@ extern "C" {
 
 int mi_gomp_scene_create(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, int64_t n_balls, const mi_gomp_ball *balls,
                          int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, nullptr, false, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_chain(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, true, n_balls, balls, n_lines, lines, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_world(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                int64_t n_capsules, const mi_gomp_capsule *capsules, const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_cuboids(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                  int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                  int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
                                  const double *con_lo, const double *con_hi) {
-  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_pairs(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
                                int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
                                int64_t n_pairs, const mi_gomp_pair *pairs, const double *con_lo, const double *con_hi) {
   return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids,
-                           n_pairs, pairs, 0, nullptr, 0, nullptr, con_lo, con_hi);
+                           n_pairs, pairs, 0, nullptr, 0, nullptr, 0, nullptr, con_lo, con_hi);
 }
 int mi_gomp_scene_create_tilts(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
                                int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
@@ -4164,7 +4208,53 @@ int mi_gomp_scene_create_grids(mi_gomp_scene **out, mi_osqp_batch *h, int64_t di
                                int64_t n_pairs, const mi_gomp_pair *pairs, int64_t n_tilts, const mi_gomp_tilt *tilts,
                                int64_t n_grids, const mi_gomp_grid *grids, const double *con_lo, const double *con_hi) {
   return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids,
-                           n_pairs, pairs, n_tilts, tilts, n_grids, grids, con_lo, con_hi);
+                           n_pairs, pairs, n_tilts, tilts, n_grids, grids, 0, nullptr, con_lo, con_hi);
+}
+int mi_gomp_scene_create_goals(mi_gomp_scene **out, mi_osqp_batch *h, int64_t dims, int64_t waypoints, const mi_gomp_chain *chain,
+                               int64_t n_balls, const mi_gomp_ball *balls, int64_t n_lines, const mi_gomp_line *lines,
+                               int64_t n_capsules, const mi_gomp_capsule *capsules, int64_t n_cuboids, const mi_gomp_cuboid *cuboids,
+                               int64_t n_pairs, const mi_gomp_pair *pairs, int64_t n_tilts, const mi_gomp_tilt *tilts,
+                               int64_t n_grids, const mi_gomp_grid *grids, int64_t n_goals, const mi_gomp_goal *goals,
+                               const double *con_lo, const double *con_hi) {
+  return gomp_scene_create(out, h, dims, waypoints, chain, chain != nullptr, n_balls, balls, n_lines, lines, n_capsules, capsules, n_cuboids, cuboids,
+                           n_pairs, pairs, n_tilts, tilts, n_grids, grids, n_goals, goals, con_lo, con_hi);
+}
+// what the listed QPs ask of the scene's goals: checked on the host, the cosines taken here in fp64, copied on the handle's
+// stream; kept rows are not touched (the next assemble / re-linearisation of such a QP reads the new values)
+int mi_gomp_scene_set_goal_values(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, const mi_gomp_goal_value *values) {
+  if (!sc || (n_ids > 0 && (!ids || !values))) return MI_OSQP_ERR_NULL;
+  if (sc->n_goals == 0) { g_last_error = "the scene has no goals"; return MI_OSQP_ERR_INVALID_DATA; }
+  if (n_ids < 0) { g_last_error = "n_ids is negative"; return MI_OSQP_ERR_INVALID_DATA; }
+  mi_osqp_batch *h = sc->h;
+  const size_t NG = (size_t)sc->n_goals;
+  std::vector<GompGoalValDev> hv((size_t)n_ids * NG);
+  for (int64_t j = 0; j < n_ids; j++) {
+    if (ids[j] < 0 || ids[j] >= h->B) { g_last_error = "id " + std::to_string(ids[j]) + ": the handle has QPs 0 .. " + std::to_string(h->B - 1); return MI_OSQP_ERR_INVALID_DATA; }
+    for (size_t k = 0; k < NG; k++) {
+      const mi_gomp_goal_value &v = values[(size_t)j * NG + k];
+      const std::string who = "goal " + std::to_string(k) + " of QP " + std::to_string(ids[j]);
+      bool finite = std::isfinite(v.max_angle);
+      for (int i = 0; i < 3; i++) finite = finite && std::isfinite(v.point[i]) && std::isfinite(v.tol[i]) && std::isfinite(v.ref[i]);
+      if (!finite) { g_last_error = who + " has a value that is not finite"; return MI_OSQP_ERR_INVALID_DATA; }
+      if (v.tol[0] < 0.0 || v.tol[1] < 0.0 || v.tol[2] < 0.0) { g_last_error = who + ": tol must not be negative"; return MI_OSQP_ERR_INVALID_DATA; }
+      if (sc->goal_frame[k] >= 1) {
+        const double nr = std::sqrt(v.ref[0] * v.ref[0] + v.ref[1] * v.ref[1] + v.ref[2] * v.ref[2]);
+        if (!(std::fabs(nr - 1.0) <= 1e-9)) { g_last_error = who + ": ref is not a unit vector"; return MI_OSQP_ERR_INVALID_DATA; }
+        if (!(v.max_angle > 0.0 && v.max_angle < M_PI)) { g_last_error = who + ": max_angle must lie in (0, pi)"; return MI_OSQP_ERR_INVALID_DATA; }
+      }
+      GompGoalValDev &d = hv[(size_t)j * NG + k];
+      for (int i = 0; i < 3; i++) { d.point[i] = v.point[i]; d.tol[i] = v.tol[i]; d.ref[i] = v.ref[i]; }
+      d.cos_lim = std::cos(v.max_angle);
+      d.cos_ok = std::cos(std::min(M_PI, v.max_angle + 1e-3));
+    }
+  }
+  if (!n_ids) return MI_OSQP_OK;
+  DevGuard guard(h->device);
+  for (int64_t j = 0; j < n_ids; j++)
+    HIPCHK(hipMemcpyAsync(sc->goal_vals.p + (size_t)ids[j] * NG, hv.data() + (size_t)j * NG, NG * sizeof(GompGoalValDev), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));          // (the staging array is pageable)
+  for (int64_t j = 0; j < n_ids; j++) sc->goal_set[(size_t)ids[j]] = 1;
+  return MI_OSQP_OK;
 }
 // a new camera frame: new node values of the same shape for grid k, on the handle's stream; kept rows are not touched
 int mi_gomp_scene_update_grid(mi_gomp_scene *sc, int64_t k, const double *values) {
@@ -4222,6 +4312,7 @@ int mi_gomp_scene_get_rows(mi_gomp_scene *sc, int64_t id, double *Av, double *l,
 int mi_gomp_assemble_some(mi_gomp_scene *sc, int64_t n_ids, const int64_t *ids, const double *x, int32_t *ok_out) {
   if (!sc || (n_ids > 0 && (!ids || !x || !ok_out))) return MI_OSQP_ERR_NULL;
   if (!n_ids) return MI_OSQP_OK;
+  if (int rg = gomp_goal_values_set(sc, n_ids, ids)) return rg;
   DevGuard guard(sc->h->device);
   int rc;
   if ((rc = cont_enter(sc->h)) || (rc = cont_check_ids(sc->h, n_ids, ids, false))) return rc;
@@ -4235,6 +4326,7 @@ int mi_gomp_relinearise_some(mi_gomp_scene *sc, int64_t n_ids, const int64_t *id
   CallTimer timer_("gomp_relinearise_some");
   if (!sc || (n_ids > 0 && (!ids || !x || !ok_out))) return MI_OSQP_ERR_NULL;
   if (!n_ids) return MI_OSQP_OK;
+  if (int rg = gomp_goal_values_set(sc, n_ids, ids)) return rg;
   mi_osqp_batch *h = sc->h;
   DevGuard guard(h->device);
   int rc;
